@@ -16,12 +16,18 @@ max-over-ranks wall time (weak scaling: per-GPU batch fixed).
             every one of their 512 positions masked in turn, one forward per (window, position) through
             pcad_forward_at -> softmax(a,c,g,t) at that position -> all-gather of [B, 4]
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step) and the
+run's configuration.  A plain run sets up, warms up, times --steps steps and prints that line, nothing else.  --full adds:
   roofline      dominant kernel class: ALGORITHMIC bytes|flops per launch (SURVEY.md §8(d)'s per-row share x rows per
                 launch) / its average launch duration measured with HIP events on the launch stream
                 during the timed region (pcad_profile_*).  For the VALU-bound scan also the arithmetic floor fractions.
   whole_step    SURVEY.md §8(d)'s flop and byte counts per sequence x sequences / the timed wall clock, vs chip peaks.
+  energy, box   board power sampled during the timed region; power and clock before and after it.
   cpu_baseline  the C/OpenMP oracle port (oracle/c) timed on this host's cores on a bounded sample.
+  parity_config the fp32 model with f32_gemm_split, timed for a few steps after the headline and checked against cpu_baseline.
+  host          host-side timings (tokeniser, host-to-device copies, writers).
+--dump-outputs DIR writes what the last timed step returned (rank 0: all ranks' rows) as DIR/<name>.npy in float32, so that two
+builds can be compared output for output: the inputs and the synthetic checkpoint are seeded, identical for identical arguments.
 """
 import argparse
 import json
@@ -56,7 +62,8 @@ SIMDS, CLOCK = 1024, 2.4e9
 CPU_REPEATS = 2                            # timed runs of the CPU baseline after one warm-up run (value = best, value_median beside it)
 CPU_MIN_SEQS = 16                          # windows of the CPU baseline's sample (>= 16: every operator of the port has work for all cores)
 CPU_BUDGET_S = 30.0                        # warm-up + timed runs of the CPU baseline stay inside this; the 2nd repeat is dropped if it would not fit
-PARITY_STEPS, PARITY_WARMUP = 3, 1         # the parity_config leg (fp32 model with f32_gemm_split) of the default run
+PARITY_STEPS, PARITY_WARMUP = 3, 1         # the parity_config leg (fp32 model with f32_gemm_split) of a --full run
+DUMP_LIMIT = 64 * 10 ** 6                  # bytes --dump-outputs may write in all
 
 
 def cpu_quota_from_text(cpu_max: str = "", cfs_quota_us: str = "", cfs_period_us: str = ""):
@@ -159,11 +166,18 @@ def host_peak_estimate(usable_cpus=None):
     return host_peak_from_cpuinfo(txt, khz, usable_cpus)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel HIP-event timings and roofline, "
+                         "whole-step fractions, board power, the CPU baseline, the parity_config leg, host-side timings "
+                         "(the options below that name these act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32; a fixed seeded "
+                         "sample of rows when it exceeds %d MB)" % (DUMP_LIMIT // 10 ** 6))
     ap.add_argument("--workload", default="zeroshot", choices=["zeroshot", "embed", "ism"])
     ap.add_argument("--model", default="l32", help="l20|l24|l28|l32 (BASELINE.json metric: l32) | pc2-small|pc2-medium|pc2-large (PlantCAD2 geometries)")
     ap.add_argument("--batch", type=int, default=1024, help="512-bp windows (ism: masked forwards) per GPU per step")
@@ -183,8 +197,28 @@ def parse():
                     help="windows for the host-side timings of the `host` object (tokeniser, H2D, writers); 0 = skip, -1 = 100000")
     ap.add_argument("--profile-stride", type=int, default=7,
                     help="HIP events around every N-th launch of each kernel class during the timed region (ODD: the scan class "
-                         "alternates forward / reverse launches, which differ by 14 %; an even stride samples one direction only)")
-    return ap.parse_args()
+                         "alternates forward / reverse launches, which differ by 14 %%; an even stride samples one direction only)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(dirpath, arrays, limit=DUMP_LIMIT, seed=0):
+    """Write {name: array} as dirpath/<name>.npy in float32.  When they hold more than `limit` bytes together, each keeps the same
+    fraction of its rows, chosen by a generator seeded with `seed`: the same rows on every run with the same shapes."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    budget = limit - 128 * len(arrays)                     # .npy headers
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = max(1, a.shape[0] * budget // total)
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def per_sequence_work(cfg, L, esz):
@@ -479,12 +513,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    box = {"idle": box_state(torch)} if rank == 0 else {}
+    box = {"idle": box_state(torch)} if rank == 0 and args.full else {}
     for _ in range(args.warmup):
         out = step()
-    if not args.no_profile:
+    profiled = args.full and not args.no_profile
+    if profiled:
         eng.profile(max(1, args.profile_stride))
-    sampler = PowerSampler(torch) if rank == 0 else None
+    sampler = PowerSampler(torch) if rank == 0 and args.full else None
     fence()
     if sampler:
         sampler.start()
@@ -493,13 +528,14 @@ def main():
         out = step()
     torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0                          # this rank's own K steps (before it waits for the others)
-    if rank == 0:
+    if rank == 0 and args.full:
         box["end_of_timed_region"] = box_state(torch)
     fence()
     dt = time.perf_counter() - t0
     if sampler:
         sampler.stop()
-    eng.profile(False)
+    if profiled:
+        eng.profile(False)
     eng.check_status()               # deferred input validation of the engine (device-side; raises on invalid ids / positions)
     ranks_seen, per_rank = [rank], [B * args.steps / dt_own]
     if dist_on:
@@ -518,8 +554,10 @@ def main():
         own = out[rank * B:(rank + 1) * B]
         assert torch.isfinite(own).all()
     assert torch.isfinite(out).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings" if args.workload == "embed" else "probs": out.float().cpu().numpy()})
 
-    stats = {} if args.no_profile else eng.profile_read()
+    stats = eng.profile_read() if profiled else {}
     if rank == 0:
         total = world * B * args.steps
         what = {"zeroshot": "zero-shot SNP scoring: masked-LM forward of %d synthetic %d-bp windows per GPU per step (both "
@@ -547,244 +585,245 @@ def main():
             "per_rank_seq_per_s": [round(v, 2) for v in per_rank],
             "engine_options": dict(kv.split("=", 1) for kv in args.opt),
         }
-        if sampler:
-            en = sampler.summary(dt, B * args.steps)
-            if en:
-                res["energy"] = en
-                res["energy_J_per_window"] = round(en["energy_J_per_window"], 4)
-        # ---- whole step against the chip peaks, from SURVEY.md §8(d)'s per-sequence counts ----------------------
-        fl_seq, by_seq = per_sequence_work(cfg, L, esz)
-        opts = dict(kv.split("=", 1) for kv in args.opt)
-        # fp32 model with "f32_gemm_split": in_proj / out_proj (98 % of the flops) run as three bf16 MFMA products per fp32 product
-        split = args.dtype == "f32" and opts.get("f32_gemm_split", "0") != "0"
-        peak_mfma = PEAK["bf16"] / 3.0 if split else PEAK[args.dtype]
-        if split:
-            res["mfma_peak_note"] = ("f32_gemm_split: the projections run on the bf16 matrix pipes at three products per fp32 product; "
-                                     "MFMA fractions are against bf16 peak / 3 = %.0f TFLOP/s of fp32-equivalent work" % peak_mfma)
-        shortcut = args.workload != "ism" and opts.get("last_layer_shortcut", "1") != "0"
-        fl_skip, scan_skip = executed_fraction_last_layer(cfg, L, p, shortcut)
-        # bytes the shortcut skips: the last layer's out_proj term (LE + LD) and scan_skip of its scan term (3LE), both strands
-        by_skip = 2.0 * esz * ((L * cfg.d_inner + L * cfg.d_model) + 3.0 * L * cfg.d_inner * scan_skip) if shortcut else 0.0
-        fl_exec, by_exec = fl_seq - fl_skip, by_seq - by_skip
-        res["whole_step"] = {"flops_per_seq": fl_seq, "hbm_bytes_per_seq": by_seq,
-                             "flops_per_seq_executed": fl_exec, "hbm_bytes_per_seq_executed": by_exec,
-                             "TFLOP/s": fl_exec * total / dt / 1e12 / world, "GB/s": by_exec * total / dt / 1e9 / world,
-                             "mfma_frac": fl_exec * total / dt / 1e12 / world / peak_mfma,
-                             "hbm_frac": by_exec * total / dt / 1e9 / world / PEAK_HBM,
-                             "note": "per GPU; SURVEY.md §8(d) algorithmic flops (tie-folded) and bytes (GEMM-boundary fusion) per "
-                                     "window MINUS what the last-layer shortcut does not execute (last out_proj except the evaluated "
-                                     "rows, the scans beyond the furthest evaluated row: %.2f %% of the flops), x windows / timed wall clock"
-                                     % (100.0 * fl_skip / fl_seq)}
-        res["box"] = box
-        chunk_max = max(1, ((((1 << 32) - (2 << 20)) // (cfg.d_inner * esz)) & ~7) // (2 * L))   # as api.hip chunk_row_limit
-        if args.chunk_seqs:
-            chunk_max = args.chunk_seqs
-        elif os.environ.get("PCAD_DEV") == "1" and os.environ.get("PCAD_CHUNK_SEQS"):
-            chunk_max = int(os.environ["PCAD_CHUNK_SEQS"])
-        nchunks = -(-B // chunk_max)
-        if not args.chunk_seqs and "workspace_limit_mb" not in opts:       # api.hip chunk_for: whole rounds of the persistent GEMMs
-            whole = lambda m: (2 * (-(-B // m)) * L) % 16384 == 0          # noqa: E731
-            if not whole(nchunks):
-                nchunks = next((m for m in range(nchunks + 1, min(2 * nchunks, B) + 1) if whole(m)), nchunks)
-        chunk = -(-B // nchunks)                                  # even split, as pcad_forward does
-        rows = 2 * chunk * L
-        work = algorithmic_work(cfg, rows, esz)
-        kern = {}
-        if stats.get("conv1d_bidir", (0, 0))[0] and not stats.get("gemm_x_proj", (0, 0))[0]:
-            stats = {("conv_xproj_fused" if k == "conv1d_bidir" else k): v for k, v in stats.items()}   # fused build
-        for name, (n, ms) in stats.items():
-            if n:
-                avg = ms / n
-                kern[name] = {"timed_launches": n, "timed_ms": round(ms, 3), "avg_ms": round(avg, 5),
-                              "TFLOP/s": round(work[name]["flops"] / (avg * 1e-3) / 1e12, 2),
-                              "GB/s": round(work[name]["bytes_8d"] / (avg * 1e-3) / 1e9, 1),
-                              "executed_GB/s": round(work[name]["bytes"] / (avg * 1e-3) / 1e9, 1)}
-        if kern:
-            nl = cfg.n_layer
-            full_out = nl - 1 if shortcut else nl                # full-size out_proj launches per chunk (the shortcut's is a 2B-row GEMM)
-            folded = "gemm_out_proj_res" in kern
-            # folded: layer 0 = the embedding kernel + the table gather of its in_proj output (both counted as add_rmsnorm), no GEMM
-            per_chunk = {"add_rmsnorm": 2 if folded else nl, "rstd_reduce": nl - 1 if folded else 0, "gemm_in_proj": nl - 1 if folded else nl, "conv1d_bidir": nl,
-                         "conv_xproj_fused": nl, "gemm_x_proj": 2 * nl, "selective_scan": 2 * nl,
-                         "gemm_out_proj": (0 if shortcut else 1) if folded else full_out,
-                         "gemm_out_proj_res": nl - 1 if folded else 0, "final_head": 0}     # launches per chunk
-            for name in kern:
-                kern[name]["est_ms_per_step"] = round(kern[name]["avg_ms"] * per_chunk.get(name, 0) * nchunks, 2)
-            dom = max(kern, key=lambda k: kern[k]["est_ms_per_step"])
-            avg_s = kern[dom]["avg_ms"] * 1e-3
-            if dom.startswith("gemm"):
-                a = work[dom]["flops"] / avg_s / 1e12
-                res["roofline"] = {"kernel": dom, "bound": "mfma", "achieved": a, "peak": peak_mfma,
-                                   "unit": "TFLOP/s", "frac": a / peak_mfma, "traffic": None,
-                                   "algorithmic_flops_per_launch": work[dom]["flops"]}
-            else:
-                a = work[dom]["bytes_8d"] / avg_s / 1e9
-                res["roofline"] = {"kernel": dom, "bound": "valu" if "valu_floor_cycles" in work[dom] else "hbm",
-                                   "achieved": a, "peak": PEAK_HBM, "unit": "GB/s",
-                                   "frac": a / PEAK_HBM, "traffic": None,
-                                   "algorithmic_bytes_per_launch": work[dom]["bytes_8d"],
-                                   "executed_bytes": work[dom]["bytes"]}
-                if "valu_floor_cycles" in work[dom]:
-                    # this kernel's limiter is neither HBM nor MFMA: VALU issue + the quarter-rate transcendental unit (PMC: VALU
-                    # busy ~0.9, MFMA busy < 2 %), hence bound = "valu"; achieved / peak / frac stay the HBM figures the contract
-                    # asks for (algorithmic bytes per launch / launch time / 8 TB/s), and next to them:
-                    #   valu_floor_frac  = (16 v_exp_f32 + 32 packed fp32 ops per (t, 64-channel wave) at the microbenchmarked time
-                    #                      of that mix, NOTHING else) / (launch time x 1024 SIMDs x 2.4 GHz nominal)
-                    #   trans_floor_frac = the 16 v_exp_f32 alone
-                    cyc = avg_s * SIMDS * CLOCK
-                    res["roofline"]["valu_floor_frac"] = work[dom]["valu_floor_cycles"] / cyc
-                    res["roofline"]["valu_floor_frac_from_instruction_counts"] = work[dom]["valu_floor_cycles_sum"] / cyc
-                    res["roofline"]["trans_floor_frac"] = work[dom]["trans_cycles"] / cyc
-                    res["roofline"]["note"] = ("frac = SURVEY.md §8(d) share (1.5*E*s + (R+2N)*s bytes per row per direction launch) / "
-                                               "launch time / 8 TB/s; the kernel is VALU/transcendental-bound, not HBM-bound: "
-                                               "valu_floor_frac / trans_floor_frac give its distance from the arithmetic floor "
-                                               "(8 state pairs x %.2f cycles at 2.4 GHz for 2 v_exp_f32 + 4 packed ops measured as one mix, "
-                                               "profiles/r04k_valu_power.txt; ..._from_instruction_counts: the same 16 + 32 instructions priced one by "
-                                               "one, v_exp_f32 %.2f + v_pk_mul_f32 %.2f + v_pk_fma_f32 %.2f per state; the launch itself clocks at "
-                                               "~2.1 GHz with the board at 96 %% of its power cap, profiles/r04k_power_probe.txt)"
-                                               % (CYC_PAIR_MIX, CYC_EXP, CYC_PK_MUL, CYC_PK_FMA))
-            res["roofline"]["rows_per_launch"] = rows
-            # HBM traffic per launch from the PMC counters (separate rocprofv3 --pmc passes; summary committed under profiles/).
-            # Only filled when the committed profile was measured on THIS build of the kernels (source hash match).
-            try:
-                import glob
-                pm = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
-                sh = source_hash()
-                hit = [f for f in pm if json.load(open(f)).get("src_hash") == sh]
-                if hit and args.model == "l32" and args.dtype == "bf16":
-                    pj = json.load(open(hit[-1]))
-                    key = dom if dom in pj["classes"] else ("gemm_in_out_proj" if dom in ("gemm_in_proj", "gemm_out_proj") else None)
-                    if key:
-                        prow = float(pj.get("rows_per_launch", 65536))
-                        res["roofline"]["traffic"] = int(pj["classes"][key]["traffic_bytes_per_launch"] * rows / prow)
-                        res["roofline"]["traffic_measured"] = "offline"     # separate rocprofv3 --pmc passes on this build, not this run
-                        res["roofline"]["traffic_source"] = (
-                            "profiled offline on this build (src_hash %s): %s, measured at %d rows per launch%s"
-                            % (sh, os.path.basename(hit[-1]), prow, "" if prow == rows else ", scaled to %d" % rows))
-                        if "effective_clock_GHz" in pj["classes"][key]:
-                            res["roofline"]["effective_clock_GHz_profiled"] = pj["classes"][key]["effective_clock_GHz"]
+        if args.full:                    # everything beyond the headline figure
+            if sampler:
+                en = sampler.summary(dt, B * args.steps)
+                if en:
+                    res["energy"] = en
+                    res["energy_J_per_window"] = round(en["energy_J_per_window"], 4)
+            # ---- whole step against the chip peaks, from SURVEY.md §8(d)'s per-sequence counts ----------------------
+            fl_seq, by_seq = per_sequence_work(cfg, L, esz)
+            opts = dict(kv.split("=", 1) for kv in args.opt)
+            # fp32 model with "f32_gemm_split": in_proj / out_proj (98 % of the flops) run as three bf16 MFMA products per fp32 product
+            split = args.dtype == "f32" and opts.get("f32_gemm_split", "0") != "0"
+            peak_mfma = PEAK["bf16"] / 3.0 if split else PEAK[args.dtype]
+            if split:
+                res["mfma_peak_note"] = ("f32_gemm_split: the projections run on the bf16 matrix pipes at three products per fp32 product; "
+                                         "MFMA fractions are against bf16 peak / 3 = %.0f TFLOP/s of fp32-equivalent work" % peak_mfma)
+            shortcut = args.workload != "ism" and opts.get("last_layer_shortcut", "1") != "0"
+            fl_skip, scan_skip = executed_fraction_last_layer(cfg, L, p, shortcut)
+            # bytes the shortcut skips: the last layer's out_proj term (LE + LD) and scan_skip of its scan term (3LE), both strands
+            by_skip = 2.0 * esz * ((L * cfg.d_inner + L * cfg.d_model) + 3.0 * L * cfg.d_inner * scan_skip) if shortcut else 0.0
+            fl_exec, by_exec = fl_seq - fl_skip, by_seq - by_skip
+            res["whole_step"] = {"flops_per_seq": fl_seq, "hbm_bytes_per_seq": by_seq,
+                                 "flops_per_seq_executed": fl_exec, "hbm_bytes_per_seq_executed": by_exec,
+                                 "TFLOP/s": fl_exec * total / dt / 1e12 / world, "GB/s": by_exec * total / dt / 1e9 / world,
+                                 "mfma_frac": fl_exec * total / dt / 1e12 / world / peak_mfma,
+                                 "hbm_frac": by_exec * total / dt / 1e9 / world / PEAK_HBM,
+                                 "note": "per GPU; SURVEY.md §8(d) algorithmic flops (tie-folded) and bytes (GEMM-boundary fusion) per "
+                                         "window MINUS what the last-layer shortcut does not execute (last out_proj except the evaluated "
+                                         "rows, the scans beyond the furthest evaluated row: %.2f %% of the flops), x windows / timed wall clock"
+                                         % (100.0 * fl_skip / fl_seq)}
+            res["box"] = box
+            chunk_max = max(1, ((((1 << 32) - (2 << 20)) // (cfg.d_inner * esz)) & ~7) // (2 * L))   # as api.hip chunk_row_limit
+            if args.chunk_seqs:
+                chunk_max = args.chunk_seqs
+            elif os.environ.get("PCAD_DEV") == "1" and os.environ.get("PCAD_CHUNK_SEQS"):
+                chunk_max = int(os.environ["PCAD_CHUNK_SEQS"])
+            nchunks = -(-B // chunk_max)
+            if not args.chunk_seqs and "workspace_limit_mb" not in opts:       # api.hip chunk_for: whole rounds of the persistent GEMMs
+                whole = lambda m: (2 * (-(-B // m)) * L) % 16384 == 0          # noqa: E731
+                if not whole(nchunks):
+                    nchunks = next((m for m in range(nchunks + 1, min(2 * nchunks, B) + 1) if whole(m)), nchunks)
+            chunk = -(-B // nchunks)                                  # even split, as pcad_forward does
+            rows = 2 * chunk * L
+            work = algorithmic_work(cfg, rows, esz)
+            kern = {}
+            if stats.get("conv1d_bidir", (0, 0))[0] and not stats.get("gemm_x_proj", (0, 0))[0]:
+                stats = {("conv_xproj_fused" if k == "conv1d_bidir" else k): v for k, v in stats.items()}   # fused build
+            for name, (n, ms) in stats.items():
+                if n:
+                    avg = ms / n
+                    kern[name] = {"timed_launches": n, "timed_ms": round(ms, 3), "avg_ms": round(avg, 5),
+                                  "TFLOP/s": round(work[name]["flops"] / (avg * 1e-3) / 1e12, 2),
+                                  "GB/s": round(work[name]["bytes_8d"] / (avg * 1e-3) / 1e9, 1),
+                                  "executed_GB/s": round(work[name]["bytes"] / (avg * 1e-3) / 1e9, 1)}
+            if kern:
+                nl = cfg.n_layer
+                full_out = nl - 1 if shortcut else nl                # full-size out_proj launches per chunk (the shortcut's is a 2B-row GEMM)
+                folded = "gemm_out_proj_res" in kern
+                # folded: layer 0 = the embedding kernel + the table gather of its in_proj output (both counted as add_rmsnorm), no GEMM
+                per_chunk = {"add_rmsnorm": 2 if folded else nl, "rstd_reduce": nl - 1 if folded else 0, "gemm_in_proj": nl - 1 if folded else nl, "conv1d_bidir": nl,
+                             "conv_xproj_fused": nl, "gemm_x_proj": 2 * nl, "selective_scan": 2 * nl,
+                             "gemm_out_proj": (0 if shortcut else 1) if folded else full_out,
+                             "gemm_out_proj_res": nl - 1 if folded else 0, "final_head": 0}     # launches per chunk
+                for name in kern:
+                    kern[name]["est_ms_per_step"] = round(kern[name]["avg_ms"] * per_chunk.get(name, 0) * nchunks, 2)
+                dom = max(kern, key=lambda k: kern[k]["est_ms_per_step"])
+                avg_s = kern[dom]["avg_ms"] * 1e-3
+                if dom.startswith("gemm"):
+                    a = work[dom]["flops"] / avg_s / 1e12
+                    res["roofline"] = {"kernel": dom, "bound": "mfma", "achieved": a, "peak": peak_mfma,
+                                       "unit": "TFLOP/s", "frac": a / peak_mfma, "traffic": None,
+                                       "algorithmic_flops_per_launch": work[dom]["flops"]}
                 else:
-                    res["roofline"]["traffic_source"] = "no committed PMC profile matches this build (src_hash %s)" % sh
-            except Exception:
-                pass
-            res["roofline"]["share_of_gpu_time"] = kern[dom]["est_ms_per_step"] / max(1e-9, sum(k["est_ms_per_step"] for k in kern.values()))
-            res["roofline"]["timing"] = ("HIP events on the launch stream around every %d-th launch of the class during the "
-                                         "timed region" % max(1, args.profile_stride))
-            res["kernels"] = kern
-        # ---- host-CPU baseline: the oracle port, same model / same kind of input, bounded sample ------
-        ncpu = args.cpu_seqs if world == 1 else 0                 # reported at N=1 only
-        cpu_logits = None                                          # oracle logits [ncpu, 8] at the evaluated position (parity leg's checker)
-        if ncpu != 0:
-            try:
-                from oracle.c_oracle import COracle
-                budget = host_cpu_budget()
-                hp = host_peak_estimate(budget["usable_cpus"])
-                co = COracle(sd, cfg, blas=True, threads=hp["usable_cores"])     # one thread per core the process may use
-                threads = co.threads
-                if ncpu < 0:
-                    ncpu = min(B, CPU_MIN_SEQS)
-                sample = ids_np[:ncpu]
-                t_leg = time.perf_counter()
-                t1 = time.perf_counter()
-                co.forward(ids_np[:1])                            # warm-up: OpenMP team, BLAS threads, first touch of the buffers
-                t_warm = time.perf_counter() - t1
-                times = []
-                for rep in range(CPU_REPEATS):
-                    # bounded: a repeat is only started if it fits the budget by the previous one's duration
-                    if rep and (time.perf_counter() - t_leg) + times[-1] > CPU_BUDGET_S:
-                        break
+                    a = work[dom]["bytes_8d"] / avg_s / 1e9
+                    res["roofline"] = {"kernel": dom, "bound": "valu" if "valu_floor_cycles" in work[dom] else "hbm",
+                                       "achieved": a, "peak": PEAK_HBM, "unit": "GB/s",
+                                       "frac": a / PEAK_HBM, "traffic": None,
+                                       "algorithmic_bytes_per_launch": work[dom]["bytes_8d"],
+                                       "executed_bytes": work[dom]["bytes"]}
+                    if "valu_floor_cycles" in work[dom]:
+                        # this kernel's limiter is neither HBM nor MFMA: VALU issue + the quarter-rate transcendental unit (PMC: VALU
+                        # busy ~0.9, MFMA busy < 2 %), hence bound = "valu"; achieved / peak / frac stay the HBM figures the contract
+                        # asks for (algorithmic bytes per launch / launch time / 8 TB/s), and next to them:
+                        #   valu_floor_frac  = (16 v_exp_f32 + 32 packed fp32 ops per (t, 64-channel wave) at the microbenchmarked time
+                        #                      of that mix, NOTHING else) / (launch time x 1024 SIMDs x 2.4 GHz nominal)
+                        #   trans_floor_frac = the 16 v_exp_f32 alone
+                        cyc = avg_s * SIMDS * CLOCK
+                        res["roofline"]["valu_floor_frac"] = work[dom]["valu_floor_cycles"] / cyc
+                        res["roofline"]["valu_floor_frac_from_instruction_counts"] = work[dom]["valu_floor_cycles_sum"] / cyc
+                        res["roofline"]["trans_floor_frac"] = work[dom]["trans_cycles"] / cyc
+                        res["roofline"]["note"] = ("frac = SURVEY.md §8(d) share (1.5*E*s + (R+2N)*s bytes per row per direction launch) / "
+                                                   "launch time / 8 TB/s; the kernel is VALU/transcendental-bound, not HBM-bound: "
+                                                   "valu_floor_frac / trans_floor_frac give its distance from the arithmetic floor "
+                                                   "(8 state pairs x %.2f cycles at 2.4 GHz for 2 v_exp_f32 + 4 packed ops measured as one mix, "
+                                                   "profiles/r04k_valu_power.txt; ..._from_instruction_counts: the same 16 + 32 instructions priced one by "
+                                                   "one, v_exp_f32 %.2f + v_pk_mul_f32 %.2f + v_pk_fma_f32 %.2f per state; the launch itself clocks at "
+                                                   "~2.1 GHz with the board at 96 %% of its power cap, profiles/r04k_power_probe.txt)"
+                                                   % (CYC_PAIR_MIX, CYC_EXP, CYC_PK_MUL, CYC_PK_FMA))
+                res["roofline"]["rows_per_launch"] = rows
+                # HBM traffic per launch from the PMC counters (separate rocprofv3 --pmc passes; summary committed under profiles/).
+                # Only filled when the committed profile was measured on THIS build of the kernels (source hash match).
+                try:
+                    import glob
+                    pm = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
+                    sh = source_hash()
+                    hit = [f for f in pm if json.load(open(f)).get("src_hash") == sh]
+                    if hit and args.model == "l32" and args.dtype == "bf16":
+                        pj = json.load(open(hit[-1]))
+                        key = dom if dom in pj["classes"] else ("gemm_in_out_proj" if dom in ("gemm_in_proj", "gemm_out_proj") else None)
+                        if key:
+                            prow = float(pj.get("rows_per_launch", 65536))
+                            res["roofline"]["traffic"] = int(pj["classes"][key]["traffic_bytes_per_launch"] * rows / prow)
+                            res["roofline"]["traffic_measured"] = "offline"     # separate rocprofv3 --pmc passes on this build, not this run
+                            res["roofline"]["traffic_source"] = (
+                                "profiled offline on this build (src_hash %s): %s, measured at %d rows per launch%s"
+                                % (sh, os.path.basename(hit[-1]), prow, "" if prow == rows else ", scaled to %d" % rows))
+                            if "effective_clock_GHz" in pj["classes"][key]:
+                                res["roofline"]["effective_clock_GHz_profiled"] = pj["classes"][key]["effective_clock_GHz"]
+                    else:
+                        res["roofline"]["traffic_source"] = "no committed PMC profile matches this build (src_hash %s)" % sh
+                except Exception:
+                    pass
+                res["roofline"]["share_of_gpu_time"] = kern[dom]["est_ms_per_step"] / max(1e-9, sum(k["est_ms_per_step"] for k in kern.values()))
+                res["roofline"]["timing"] = ("HIP events on the launch stream around every %d-th launch of the class during the "
+                                             "timed region" % max(1, args.profile_stride))
+                res["kernels"] = kern
+            # ---- host-CPU baseline: the oracle port, same model / same kind of input, bounded sample ------
+            ncpu = args.cpu_seqs if world == 1 else 0                 # reported at N=1 only
+            cpu_logits = None                                          # oracle logits [ncpu, 8] at the evaluated position (parity leg's checker)
+            if ncpu != 0:
+                try:
+                    from oracle.c_oracle import COracle
+                    budget = host_cpu_budget()
+                    hp = host_peak_estimate(budget["usable_cpus"])
+                    co = COracle(sd, cfg, blas=True, threads=hp["usable_cores"])     # one thread per core the process may use
+                    threads = co.threads
+                    if ncpu < 0:
+                        ncpu = min(B, CPU_MIN_SEQS)
+                    sample = ids_np[:ncpu]
+                    t_leg = time.perf_counter()
                     t1 = time.perf_counter()
-                    lg, hd = co.forward(sample, want_hidden=args.workload == "embed")
-                    times.append(time.perf_counter() - t1)
-                import statistics
-                tc, tmed = min(times), statistics.median(times)
-                hp.update(budget)
-                gf = fl_seq * ncpu / tc / 1e9
-                res["cpu_baseline"] = {"value": ncpu / tc, "unit": "sequences/s", "cores": threads, "kind": "port",
-                                       "value_median": ncpu / tmed, "repeats": len(times), "run_s": [round(t, 2) for t in times],
-                                       "warmup_s": round(t_warm, 2),
-                                       "GFLOP/s": gf,
-                                       "host_peak_gflops_est": round(hp["host_peak_gflops_est"], 1),
-                                       "frac_of_host_peak": gf / hp["host_peak_gflops_est"],
-                                       "host": hp,
-                                       "sample": "%d of the same synthetic %d-bp windows, PlantCaduceus_%s fp32, oracle/c "
-                                                 "(C + OpenMP norm/conv/scan, the four projections through the host BLAS sgemm via numpy; "
-                                                 "%d threads = the cores this process may use: %d CPUs visible, CFS quota %s): one 1-window "
-                                                 "warm-up run, then %d timed run(s) inside a %.0f s budget; value = best (%.1f s), "
-                                                 "value_median = median.  A scalar-source port: %.0f GFLOP/s = %.1f %% of the nominal fp32 "
-                                                 "peak of those cores (%d cores x %d flop/cycle x %.2f GHz = %.0f GFLOP/s, an estimate; the "
-                                                 "whole %d-core machine: %.0f) - a stated baseline, not a tuned CPU implementation"
-                                                 % (ncpu, L, args.model, threads, budget["affinity"],
-                                                    "none" if budget["cpu_quota"] is None else "%.1f CPUs" % budget["cpu_quota"],
-                                                    len(times), CPU_BUDGET_S, tc, gf, 100.0 * gf / hp["host_peak_gflops_est"],
-                                                    hp["usable_cores"], hp["flop_per_cycle_per_core"], hp["clock_GHz"], hp["host_peak_gflops_est"],
-                                                    hp["physical_cores"], hp["whole_host_peak_gflops_est"])}
-                # cross-check while we are here: GPU result vs the CPU port on the sample
-                gp = out[:ncpu].float().cpu().numpy()
-                if args.workload == "embed":
-                    e = hd[:, p, :]
-                    cp = (e[:, :D] + e[:, D:][:, ::-1]) / 2
-                    res["cpu_baseline"]["max_rel_diff"] = float(np.abs(gp - cp).max() / np.abs(cp).max())
-                else:
-                    cpu_logits = lg[np.arange(ncpu), pos_np[:ncpu] if pos_np is not None else p]
-                    cp = cpu_logits[:, 3:7]
-                    res["cpu_baseline"]["argmax_agree"] = float((gp.argmax(1) == cp.argmax(1)).mean())
-            except Exception as ex:   # the baseline is a reported extra; never lose the bench line over it
-                res["cpu_baseline"] = {"value": None, "unit": "sequences/s", "cores": os.cpu_count(), "kind": "port",
-                                       "sample": "failed: %r" % (ex,)}
-        # ---- parity_config: the configuration that meets north_star's accuracy clause, on the driver's record -------------------
-        # The headline is the bf16 model (what the reference's dtype rule selects on this GPU: src/zero_shot_score.py:69-85); bf16
-        # storage cannot meet "<= 1e-4 rel on logits".  The fp32 model with "f32_gemm_split" (projections as three bf16 MFMA products per
-        # fp32 product) does; it is timed here for a few steps on the SAME windows, after the headline's timed region, and its
-        # logits are compared with the CPU oracle's on the cpu_baseline sample.  The bf16 engine is released first.
-        if (world == 1 and not dist_on and not args.no_parity_leg and args.workload == "zeroshot"
-                and not (args.dtype == "f32" and split)):
-            try:
-                eng.close()
-                eng = None
-                torch.cuda.empty_cache()
-                cfg2 = make_config(args.model)
-                popts = {"f32_gemm_split": 1}
-                cfg2.engine_options = dict(popts)
-                eng2 = Engine(cfg2, sd, torch.float32, device)
+                    co.forward(ids_np[:1])                            # warm-up: OpenMP team, BLAS threads, first touch of the buffers
+                    t_warm = time.perf_counter() - t1
+                    times = []
+                    for rep in range(CPU_REPEATS):
+                        # bounded: a repeat is only started if it fits the budget by the previous one's duration
+                        if rep and (time.perf_counter() - t_leg) + times[-1] > CPU_BUDGET_S:
+                            break
+                        t1 = time.perf_counter()
+                        lg, hd = co.forward(sample, want_hidden=args.workload == "embed")
+                        times.append(time.perf_counter() - t1)
+                    import statistics
+                    tc, tmed = min(times), statistics.median(times)
+                    hp.update(budget)
+                    gf = fl_seq * ncpu / tc / 1e9
+                    res["cpu_baseline"] = {"value": ncpu / tc, "unit": "sequences/s", "cores": threads, "kind": "port",
+                                           "value_median": ncpu / tmed, "repeats": len(times), "run_s": [round(t, 2) for t in times],
+                                           "warmup_s": round(t_warm, 2),
+                                           "GFLOP/s": gf,
+                                           "host_peak_gflops_est": round(hp["host_peak_gflops_est"], 1),
+                                           "frac_of_host_peak": gf / hp["host_peak_gflops_est"],
+                                           "host": hp,
+                                           "sample": "%d of the same synthetic %d-bp windows, PlantCaduceus_%s fp32, oracle/c "
+                                                     "(C + OpenMP norm/conv/scan, the four projections through the host BLAS sgemm via numpy; "
+                                                     "%d threads = the cores this process may use: %d CPUs visible, CFS quota %s): one 1-window "
+                                                     "warm-up run, then %d timed run(s) inside a %.0f s budget; value = best (%.1f s), "
+                                                     "value_median = median.  A scalar-source port: %.0f GFLOP/s = %.1f %% of the nominal fp32 "
+                                                     "peak of those cores (%d cores x %d flop/cycle x %.2f GHz = %.0f GFLOP/s, an estimate; the "
+                                                     "whole %d-core machine: %.0f) - a stated baseline, not a tuned CPU implementation"
+                                                     % (ncpu, L, args.model, threads, budget["affinity"],
+                                                        "none" if budget["cpu_quota"] is None else "%.1f CPUs" % budget["cpu_quota"],
+                                                        len(times), CPU_BUDGET_S, tc, gf, 100.0 * gf / hp["host_peak_gflops_est"],
+                                                        hp["usable_cores"], hp["flop_per_cycle_per_core"], hp["clock_GHz"], hp["host_peak_gflops_est"],
+                                                        hp["physical_cores"], hp["whole_host_peak_gflops_est"])}
+                    # cross-check while we are here: GPU result vs the CPU port on the sample
+                    gp = out[:ncpu].float().cpu().numpy()
+                    if args.workload == "embed":
+                        e = hd[:, p, :]
+                        cp = (e[:, :D] + e[:, D:][:, ::-1]) / 2
+                        res["cpu_baseline"]["max_rel_diff"] = float(np.abs(gp - cp).max() / np.abs(cp).max())
+                    else:
+                        cpu_logits = lg[np.arange(ncpu), pos_np[:ncpu] if pos_np is not None else p]
+                        cp = cpu_logits[:, 3:7]
+                        res["cpu_baseline"]["argmax_agree"] = float((gp.argmax(1) == cp.argmax(1)).mean())
+                except Exception as ex:   # the baseline is a reported extra; never lose the bench line over it
+                    res["cpu_baseline"] = {"value": None, "unit": "sequences/s", "cores": os.cpu_count(), "kind": "port",
+                                           "sample": "failed: %r" % (ex,)}
+            # ---- parity_config: the configuration that meets the 1e-4 / exact-argmax accuracy goal, in the same result line ----------
+            # The headline is the bf16 model (what the reference's dtype rule selects on this GPU: src/zero_shot_score.py:69-85); bf16
+            # storage cannot meet "<= 1e-4 rel on logits".  The fp32 model with "f32_gemm_split" (projections as three bf16 MFMA products per
+            # fp32 product) does; it is timed here for a few steps on the SAME windows, after the headline's timed region, and its
+            # logits are compared with the CPU oracle's on the cpu_baseline sample.  The bf16 engine is released first.
+            if (world == 1 and not dist_on and not args.no_parity_leg and args.workload == "zeroshot"
+                    and not (args.dtype == "f32" and split)):
+                try:
+                    eng.close()
+                    eng = None
+                    torch.cuda.empty_cache()
+                    cfg2 = make_config(args.model)
+                    popts = {"f32_gemm_split": 1}
+                    cfg2.engine_options = dict(popts)
+                    eng2 = Engine(cfg2, sd, torch.float32, device)
 
-                def pstep():
-                    return eng2.forward(ids, positions=[p], want_logits=True)[0]
+                    def pstep():
+                        return eng2.forward(ids, positions=[p], want_logits=True)[0]
 
-                for _ in range(PARITY_WARMUP):
-                    plog = pstep()
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(PARITY_STEPS):
-                    plog = pstep()
-                torch.cuda.synchronize()
-                tp = time.perf_counter() - t1
-                eng2.check_status()
-                pl = plog[:, 0, :].float().cpu().numpy()
-                pc = {"dtype": "f32", "engine_options": popts, "value": B * PARITY_STEPS / tp, "unit": "sequences/s",
-                      "ms_per_step": 1e3 * tp / PARITY_STEPS, "steps": PARITY_STEPS, "warmup": PARITY_WARMUP, "batch_per_gpu": B,
-                      "max_rel_err_vs_cpu_sample": None, "argmax_agree": None,
-                      "note": "PlantCaduceus_%s fp32 weights / activations, in_proj / out_proj / x_proj / dt_proj as split-bf16 MFMA "
-                              "products (three per fp32 product, fp32 accumulation); same %d windows as the headline, timed after it; "
-                              "max_rel_err = max |logits - oracle| / max |oracle| over the 8 vocabulary logits at the masked index of the "
-                              "cpu_baseline sample (oracle/c fp32); argmax over a,c,g,t" % (args.model, B)}
-                if cpu_logits is not None:
-                    n = cpu_logits.shape[0]
-                    pc["max_rel_err_vs_cpu_sample"] = float(np.abs(pl[:n] - cpu_logits).max() / np.abs(cpu_logits).max())
-                    pc["argmax_agree"] = float((pl[:n, 3:7].argmax(1) == cpu_logits[:, 3:7].argmax(1)).mean())
-                    pc["sample_windows"] = int(n)
-                    # the headline (bf16) run against the same oracle rows, for the contrast the leg exists to show
-                    pc["headline_dtype_argmax_agree"] = res.get("cpu_baseline", {}).get("argmax_agree")
-                res["parity_config"] = pc
-                eng2.close()
-            except Exception as ex:
-                res["parity_config"] = {"value": None, "failed": repr(ex)}
-        nh = args.host_seqs if world == 1 else 0
-        if nh != 0:
-            try:
-                res["host"] = host_timings(100000 if nh < 0 else nh, L, device, torch, np)
-            except Exception as ex:
-                res["host"] = {"failed": repr(ex)}
+                    for _ in range(PARITY_WARMUP):
+                        plog = pstep()
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(PARITY_STEPS):
+                        plog = pstep()
+                    torch.cuda.synchronize()
+                    tp = time.perf_counter() - t1
+                    eng2.check_status()
+                    pl = plog[:, 0, :].float().cpu().numpy()
+                    pc = {"dtype": "f32", "engine_options": popts, "value": B * PARITY_STEPS / tp, "unit": "sequences/s",
+                          "ms_per_step": 1e3 * tp / PARITY_STEPS, "steps": PARITY_STEPS, "warmup": PARITY_WARMUP, "batch_per_gpu": B,
+                          "max_rel_err_vs_cpu_sample": None, "argmax_agree": None,
+                          "note": "PlantCaduceus_%s fp32 weights / activations, in_proj / out_proj / x_proj / dt_proj as split-bf16 MFMA "
+                                  "products (three per fp32 product, fp32 accumulation); same %d windows as the headline, timed after it; "
+                                  "max_rel_err = max |logits - oracle| / max |oracle| over the 8 vocabulary logits at the masked index of the "
+                                  "cpu_baseline sample (oracle/c fp32); argmax over a,c,g,t" % (args.model, B)}
+                    if cpu_logits is not None:
+                        n = cpu_logits.shape[0]
+                        pc["max_rel_err_vs_cpu_sample"] = float(np.abs(pl[:n] - cpu_logits).max() / np.abs(cpu_logits).max())
+                        pc["argmax_agree"] = float((pl[:n, 3:7].argmax(1) == cpu_logits[:, 3:7].argmax(1)).mean())
+                        pc["sample_windows"] = int(n)
+                        # the headline (bf16) run against the same oracle rows, for the contrast the leg exists to show
+                        pc["headline_dtype_argmax_agree"] = res.get("cpu_baseline", {}).get("argmax_agree")
+                    res["parity_config"] = pc
+                    eng2.close()
+                except Exception as ex:
+                    res["parity_config"] = {"value": None, "failed": repr(ex)}
+            nh = args.host_seqs if world == 1 else 0
+            if nh != 0:
+                try:
+                    res["host"] = host_timings(100000 if nh < 0 else nh, L, device, torch, np)
+                except Exception as ex:
+                    res["host"] = {"failed": repr(ex)}
         print(json.dumps(res))
     if dist_on:
         dist.barrier()

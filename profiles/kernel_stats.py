@@ -19,7 +19,7 @@ def main():
     note = sys.argv[3] if len(sys.argv) > 3 and not sys.argv[3].startswith("--") else ""
     df = pd.read_csv(src)
     if "--headline-only" in sys.argv:
-        # a default bench.py run also executes its parity_config leg (fp32 + f32_gemm_split model): keep the headline's kernels
+        # a bench.py --full run also executes its parity_config leg (fp32 + f32_gemm_split model): keep the headline's kernels
         # (bf16 storage) and recompute the percentages over them
         keep = ~(df["Name"].str.contains("<float") | df["Name"].str.contains("<unsigned short, float") | df["Name"].str.contains("split_rows|pack_split"))
         df = df[keep].copy()

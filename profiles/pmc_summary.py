@@ -80,7 +80,7 @@ def main():
         pass
     for c, ks in cls.items():
         ks = [k for k in ks if "FETCH_SIZE_KB" in res[k] and "WRITE_SIZE_KB" in res[k]]
-        # a default bench.py run also executes its parity_config leg (the fp32 + f32_gemm_split model: <float, ...> / <bf16, float, ...>
+        # a bench.py --full run also executes its parity_config leg (the fp32 + f32_gemm_split model: <float, ...> / <bf16, float, ...>
         # instantiations): the class figures are the HEADLINE's, i.e. the bf16-storage instantiations only, whenever there are any
         head = [k for k in ks if "<bf16" in k and "<bf16, float" not in k]
         if head:

@@ -357,6 +357,31 @@ def test_bench_cpu_budget_reads_the_cgroup_quota():
     assert os.environ["OMP_WAIT_POLICY"] and os.environ["OPENBLAS_THREAD_TIMEOUT"]      # set by bench before any runtime loads
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """A plain run is the headline only (--full off by default); --steps is the number of timed steps and must be >= 1; --dump-outputs
+    writes float32 .npy files within the byte limit, a seeded sample of rows (the same on every run) when the result is larger."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.steps == 3 and a.warmup == 1 and a.full is False and a.dump_outputs is None
+    b = bench.parse(["--steps", "2", "--full", "--dump-outputs", str(tmp_path / "d")])
+    assert b.full is True and b.dump_outputs == str(tmp_path / "d")
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+    small = np.arange(40, dtype=np.float64).reshape(10, 4)
+    bench.dump_outputs(str(tmp_path / "s"), {"probs": small})
+    got = np.load(tmp_path / "s" / "probs.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.arange(4000, dtype=np.float32).reshape(1000, 4)
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), {"probs": big, "embeddings": big[:, :2]}, limit=4096)
+    files = [tmp_path / d / (n + ".npy") for d in ("b1", "b2") for n in ("probs", "embeddings")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 4096
+    p1, e1, p2, e2 = (np.load(f) for f in files)
+    assert np.array_equal(p1, p2) and np.array_equal(e1, e2) and 0 < len(p1) < 1000
+    assert np.isin(p1[:, 0], big[:, 0]).all() and (np.diff(p1[:, 0]) > 0).all()       # whole rows, in their order
+
+
 def test_effective_batch_keeps_an_explicit_batch_size():
     """`-batchSize` given by the user bounds memory as in the reference and is used as is; only the default is raised to the
     model's preferred batch."""

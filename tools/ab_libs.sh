@@ -7,7 +7,7 @@ O=$ROOT/gpurun_out/$TAG; mkdir -p $O
 V="$ROOT/plantcaduceus_amd/variants"
 for n in $NAMES; do
   if [ "$n" = cur ]; then L=""; else L="$V/libpcad_$n.so"; fi
-  PCAD_ALLOW_STALE=1 PCAD_LIB="$L" timeout 400 python3 bench.py --cpu-seqs 0 --host-seqs 0 --no-parity-leg "$@" 2>>$O/err.txt | python3 -c "
+  PCAD_ALLOW_STALE=1 PCAD_LIB="$L" timeout 400 python3 bench.py --full --cpu-seqs 0 --host-seqs 0 --no-parity-leg "$@" 2>>$O/err.txt | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1])

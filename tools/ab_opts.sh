@@ -10,7 +10,7 @@ show() { python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', round(d['value'],1), round(d['ms_per_step'],1), {k:round(v.get('avg_ms',0),4) for k,v in d.get('kernels',{}).items()})"; }
-B="--steps 6 --warmup 2 --cpu-seqs 0 --host-seqs 0"
+B="--full --steps 6 --warmup 2 --cpu-seqs 0 --host-seqs 0"
 for r in $(seq $R); do
   for spec in "$@"; do
     IFS='|' read -r name envs bargs <<< "$spec"

@@ -8,7 +8,7 @@ show() { python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', round(d['value'],1), round(d['ms_per_step'],1), {k:round(v.get('avg_ms',0),4) for k,v in d.get('kernels',{}).items()})"; }
-B="--steps 4 --warmup 1 --cpu-seqs 0 --host-seqs 0"
+B="--full --steps 4 --warmup 1 --cpu-seqs 0 --host-seqs 0"
 for r in $(seq $R); do
   for n in "$@"; do
     if [ "$n" = cur ]; then timeout 300 python3 bench.py $B 2>&1 | show "cur" | tee -a "$O/ab.txt"

@@ -8,12 +8,12 @@ ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
 OUT="$ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python3 "$ROOT/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python3 "$ROOT/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"
 # kernel stats: the SAME process prints its own HIP-event roofline line (bench_under_rocprof.json), so the rocprofv3 average
 # duration of the dominant kernel and bench.py's `roofline.achieved` come from one run (a profiled run clocks ~3-6 % lower
 # than an un-profiled one: never compare across the two)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --cpu-seqs 0 --no-parity-leg > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --cpu-seqs 0 --no-parity-leg > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log"
 f=$(find "$OUT/stats" -name "*kernel_stats.csv" | head -1); cp "$f" "$OUT/kernel_stats.csv"; find "$OUT/stats" -type f ! -name "*kernel_stats.csv" -delete
 python3 -c "import sys; sys.path.insert(0, '$ROOT'); import bench; print(bench.source_hash())" > "$OUT/src_hash.txt"
 # PMC passes at the BENCHMARK's launch size (--batch 1024 = two chunks of 512 windows = 524288 token-rows per launch): no scaling
