@@ -220,6 +220,23 @@ int    pcad_forward_all_hidden(pcad_handle h, const int32_t* ids, int B, int L,
                                void* all_hidden, void* hidden_out, float* logits_out,
                                void* workspace, size_t workspace_bytes, pcad_stream stream);
 
+/* Sequence classification (fine-tuned PlantCAD2 models: CaduceusForSequenceClassification, RCPS, pooling_strategy).
+ * The same layer walk as pcad_forward with positions == NULL (every row of the last layer is consumed: no last-layer shortcut),
+ * ending in the pooled head instead of the LM head:
+ *   hs_s[p]    = norm_f(res + h) of strand s's own row p (s = 0: the window, s = 1: its reverse complement), rounded to cfg.dtype
+ *   pooled_s   = mean (fp32 sum / L, rounded once to cfg.dtype) / max / row 0 / row L-1 of hs_s over p  (pad tokens included)
+ *   logits[n]  = round(round(round(pooled_0 . W[n]) + round(pooled_1 . W[n])) / 2)      (round: to cfg.dtype; fp32 accumulation)
+ *   pooling    pcad_pooling;  score_w  DEVICE fp32 [num_labels, D], already rounded to cfg.dtype (the `score` Linear's weight);
+ *   num_labels 1..PCAD_MAX_LABELS;  pooled_out DEVICE fp32 [B, 2, D] or NULL;  logits_out DEVICE fp32 [B, num_labels] (required).
+ * The head's partials live in workspace buffers that are dead after the last out_proj: pcad_workspace_bytes is the forward's own.
+ * Token ids outside the vocabulary are reported through pcad_set_status_buffer as by pcad_forward.
+ * Replaces: CaduceusForSequenceClassification(...)(input_ids=ids).logits (HF-hub remote code, as loaded by the reference's
+ *           src/lora_fine_tune.py load_base_model + PeftModel.from_pretrained). */
+enum pcad_pooling { PCAD_POOL_MEAN = 0, PCAD_POOL_MAX = 1, PCAD_POOL_FIRST = 2, PCAD_POOL_LAST = 3 };
+#define PCAD_MAX_LABELS 256
+int    pcad_forward_pooled(pcad_handle h, const int32_t* ids, int B, int L, int pooling, const float* score_w, int num_labels,
+                           float* pooled_out, float* logits_out, void* workspace, size_t workspace_bytes, pcad_stream stream);
+
 /* ---- measurement: per-kernel-class timing with HIP events on the caller's stream -------------------- */
 enum pcad_kernel_class {
     PCAD_K_NORM = 0, PCAD_K_GEMM_IN, PCAD_K_CONV, PCAD_K_GEMM_X, PCAD_K_SCAN, PCAD_K_GEMM_OUT, PCAD_K_HEAD,
@@ -345,6 +362,17 @@ int pcad_final_head(const void* h, const void* res, const float* norm_weight, co
                     void* hidden_out, float* logits_out, int B, int L, int D, float eps, const int32_t* positions, int P,
                     const int32_t* pos_per_seq, int h_compact, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
                     int res_fragment_layout, pcad_stream stream);
+
+/* The pooled head of pcad_forward_pooled as one operator, with pcad_final_head's inputs: h / res [2B * L, D] (h: dtype, res:
+ * res_dtype; res_fragment_layout != 0: fp32 res in pcad_gemm_nt_residual's fragment layout, D % 256 == 0, 2 B L % 256 == 0),
+ * norm_weight fp32 [D]; score_w, num_labels, pooled_out, logits_out as in pcad_forward_pooled, except that either output may be NULL
+ * (not both; score_w may be NULL when logits_out is); ids / status as in pcad_final_head.  scratch: device buffer of
+ * pcad_pooled_head_scratch_bytes(B, L, D, pooling) bytes, 256-byte aligned (the per-segment partials). */
+size_t pcad_pooled_head_scratch_bytes(int B, int L, int D, int pooling);
+int pcad_pooled_head(const void* h, const void* res, const float* norm_weight, const float* score_w, int num_labels,
+                     float* pooled_out, float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids,
+                     int32_t* status, int dtype, int res_dtype, int res_fragment_layout, void* scratch, size_t scratch_bytes,
+                     pcad_stream stream);
 
 #ifdef __cplusplus
 }

@@ -509,9 +509,18 @@ size_t pcad_workspace_bytes(pcad_handle h, int batch, int seqlen) {
     return carve_workspace(h, nullptr, Bc, seqlen, batch).bytes;
 }
 
+// pcad_forward_pooled: the pooled classification head in place of the LM head (pool.hip)
+struct PoolRequest {
+    int pooling;
+    const float* score_w;
+    int num_labels;
+    float* pooled_out;
+    float* logits_out;
+};
+
 static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P,
                         const int32_t* pos_per_seq, void* all_hidden, void* hidden_out, float* logits_out, void* workspace, size_t ws_bytes,
-                        pcad_stream stream) {
+                        pcad_stream stream, const PoolRequest* pool = nullptr) {
     if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward: null handle");
     pcad_engine* e = h;
     if (!e->bound) return fail(PCAD_ERR_UNBOUND, "pcad_forward: weights not bound");
@@ -794,6 +803,21 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
         return PCAD_OK;
     };
     auto phase_head = [&](Lane& c) -> int {
+        if (pool) {
+            // the partials go to the buffers that are dead once the last out_proj has run (everything carved after h: xz, zb, xc,
+            // dtl, bc, y, ...), so the forward's workspace size is unchanged
+            char* part = (char*)c.w.xz;
+            const size_t avail = (size_t)((char*)workspace + c.w.bytes - part);
+            if (pool_partial_bytes(c.Bc, L, D, pool->pooling) > avail)
+                return fail(PCAD_ERR_WORKSPACE, "pcad_forward_pooled: the head's partials (%zu bytes) do not fit the dead buffers (%zu)",
+                            pool_partial_bytes(c.Bc, L, D, pool->pooling), avail);
+            ProfScope ps(e, PCAD_K_HEAD, cs);
+            HIP_TRY(launch_pooled_head(c.w.h, c.w.res, e->normf_w, pool->score_w, pool->num_labels,
+                                       pool->pooled_out ? pool->pooled_out + (size_t)c.b0 * 2 * D : nullptr,
+                                       pool->logits_out + (size_t)c.b0 * pool->num_labels, c.Bc, L, D, eps, pool->pooling,
+                                       ids + (int64_t)c.b0 * L, e->status, dt, rdt, c.fold ? Dp : 0, part, cs));
+            return PCAD_OK;
+        }
         void* hout = hidden_out ? (char*)hidden_out + ((size_t)c.b0 * Q * 2 * D) * esz : nullptr;
         float* lout = logits_out ? logits_out + (size_t)c.b0 * Q * e->V : nullptr;
         if (hout || lout) {
@@ -825,6 +849,16 @@ int pcad_forward(pcad_handle h, const int32_t* ids, int B, int L, const int32_t*
                  float* logits_out, void* workspace, size_t workspace_bytes, pcad_stream stream) {
     return forward_impl(h, ids, B, L, positions, P, nullptr, nullptr, hidden_out, logits_out, workspace, workspace_bytes,
                         stream);
+}
+
+int pcad_forward_pooled(pcad_handle h, const int32_t* ids, int B, int L, int pooling, const float* score_w, int num_labels,
+                        float* pooled_out, float* logits_out, void* workspace, size_t workspace_bytes, pcad_stream stream) {
+    if (pooling < PCAD_POOL_MEAN || pooling > PCAD_POOL_LAST) return fail(PCAD_ERR_INVALID, "pcad_forward_pooled: bad pooling %d", pooling);
+    if (num_labels < 1 || num_labels > PCAD_MAX_LABELS)
+        return fail(PCAD_ERR_INVALID, "pcad_forward_pooled: num_labels=%d out of range [1, %d]", num_labels, PCAD_MAX_LABELS);
+    if (!score_w || !logits_out) return fail(PCAD_ERR_INVALID, "pcad_forward_pooled: null score_w / logits_out");
+    const PoolRequest pr{pooling, score_w, num_labels, pooled_out, logits_out};
+    return forward_impl(h, ids, B, L, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, &pr);
 }
 
 int pcad_forward_at(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* pos_per_seq, void* hidden_out,
@@ -1043,6 +1077,33 @@ int pcad_final_head(const void* h, const void* res, const float* norm_weight, co
     if (B == 0) return PCAD_OK;
     HIP_TRY(launch_final_head(h, res, norm_weight, nullptr, emb_f32, complement, hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq,
                               dtype, res_dtype, (hipStream_t)stream, h_compact != 0, ids, status, res_fragment_layout ? D : 0));
+    return PCAD_OK;
+}
+
+size_t pcad_pooled_head_scratch_bytes(int B, int L, int D, int pooling) {
+    if (B <= 0 || L <= 0 || D <= 0 || pooling < PCAD_POOL_MEAN || pooling > PCAD_POOL_LAST) return 0;
+    return align_up(pool_partial_bytes(B, L, D, pooling));
+}
+
+int pcad_pooled_head(const void* h, const void* res, const float* norm_weight, const float* score_w, int num_labels,
+                     float* pooled_out, float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids,
+                     int32_t* status, int dtype, int res_dtype, int res_fragment_layout, void* scratch, size_t scratch_bytes,
+                     pcad_stream stream) {
+    if (!h || !res || !norm_weight || !scratch) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: null argument");
+    if (!pooled_out && !logits_out) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: no output requested");
+    if (logits_out && (!score_w || num_labels < 1 || num_labels > PCAD_MAX_LABELS))
+        return fail(PCAD_ERR_INVALID, "pcad_pooled_head: logits need score_w and 1 <= num_labels <= %d", PCAD_MAX_LABELS);
+    if (pooling < PCAD_POOL_MEAN || pooling > PCAD_POOL_LAST) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: bad pooling %d", pooling);
+    if (res_fragment_layout && (res_dtype != PCAD_F32 || D % 256 || ((int64_t)2 * B * L) % 256))
+        return fail(PCAD_ERR_INVALID, "pcad_pooled_head: the fragment layout needs an fp32 residual, D %% 256 == 0 and 2 B L %% 256 == 0");
+    if ((dtype != PCAD_F32 && dtype != PCAD_BF16) || (res_dtype != PCAD_F32 && res_dtype != PCAD_BF16) || (dtype == PCAD_F32 && res_dtype != PCAD_F32))
+        return fail(PCAD_ERR_INVALID, "pcad_pooled_head: bad dtype / res_dtype");
+    if (B < 0 || L <= 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: bad B / L / D");
+    if (B == 0) return PCAD_OK;
+    if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_pooled_head_scratch_bytes(B, L, D, pooling))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_pooled_head: scratch must be 256-byte aligned and pcad_pooled_head_scratch_bytes large");
+    HIP_TRY(launch_pooled_head(h, res, norm_weight, score_w, num_labels, pooled_out, logits_out, B, L, D, eps, pooling, ids, status,
+                               dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
     return PCAD_OK;
 }
 

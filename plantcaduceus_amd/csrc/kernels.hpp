@@ -50,6 +50,14 @@ hipError_t launch_final_head(const void* h, const void* res, const float* w, con
                              int B, int L, int D, float eps, Positions pos, const int32_t* pos_per_seq, int dt, int rdt,
                              hipStream_t s, bool h_compact = false, const int32_t* ids = nullptr, int32_t* status = nullptr,
                              int res_frag = 0);            // res_frag != 0: fp32 residual in the fragment layout (common.hpp res_frag_off) of that (padded) width
+// pool.hip: pooled sequence-classification head (pcad.h pcad_pooled_head).  pooling: POOL_* (= pcad.h pcad_pooling).  Stage 1 writes
+// pool_partial_bytes(B, L, D, pooling) bytes of fp32 partials to `part` (256-byte aligned); the segmentation depends on L only.
+enum { POOL_MEAN = 0, POOL_MAX = 1, POOL_FIRST = 2, POOL_LAST = 3 };
+int pool_segments(int L, int pooling);
+size_t pool_partial_bytes(int B, int L, int D, int pooling);
+hipError_t launch_pooled_head(const void* h, const void* res, const float* w, const float* score_w, int NL, float* pooled_out,
+                              float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids, int32_t* status,
+                              int dt, int rdt, int res_frag, void* part, hipStream_t s);
 // hidden_states[i] (block input = previous mixer output / embedding) assembled in RCPS layout.
 hipError_t launch_assemble_hidden(const void* h, void* out, int B, int L, int D, int dt, hipStream_t s);
 hipError_t launch_embed_only(const int32_t* ids, const void* emb, const int32_t* comp8, void* h, int B, int L,

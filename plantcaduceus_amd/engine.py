@@ -81,7 +81,17 @@ SIGNATURES = {
     "pcad_final_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pcad_forward_pooled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_pooled_head_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pcad_pooled_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+
+# include/pcad.h pcad_pooling (pooling_strategy of CaduceusForSequenceClassification)
+POOLING = {"mean": 0, "max": 1, "first": 2, "last": 3}
+MAX_LABELS = 256
 
 _lib = None
 
@@ -272,6 +282,42 @@ class Engine:
                 self._status_host.copy_(self._status, non_blocking=True)
                 self._status_event.record()
         return logits, hidden
+
+    def forward_pooled(self, input_ids: torch.Tensor, pooling: str, score_w: torch.Tensor, want_pooled: bool = False):
+        """Sequence classification (`pcad_forward_pooled`): ids [B, L] on this device -> logits fp32 [B, NL] (and, with
+        want_pooled, the pooled vectors fp32 [B, 2, D]: [:, 0] the window's strand, [:, 1] its reverse complement's).
+        pooling: "mean" / "max" / "first" / "last"; score_w: the `score` Linear's weight [NL, D] (any float dtype, any device),
+        rounded to the model dtype here as the reference's `nn.Linear` in that dtype holds it.  Chunking, workspace and
+        asynchronous input validation are those of `forward`."""
+        _require_gpu(input_ids, "input_ids")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        if input_ids.device != self.device:
+            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        if pooling not in POOLING:
+            raise ValueError(f"pooling must be one of {sorted(POOLING)}, got {pooling!r}")
+        D = self.config.d_model
+        if score_w.dim() != 2 or score_w.shape[1] != D or not 1 <= score_w.shape[0] <= MAX_LABELS:
+            raise ValueError(f"score weight must be [num_labels (1..{MAX_LABELS}), {D}], got {tuple(score_w.shape)}")
+        self._poll_status()
+        ids = input_ids.to(torch.int32).contiguous()
+        B, L = ids.shape
+        NL = int(score_w.shape[0])
+        with torch.cuda.device(self.device):
+            w = score_w.detach().to(self.device).to(self.dtype).float().contiguous()
+            logits = torch.empty((B, NL), dtype=torch.float32, device=self.device)
+            pooled = torch.empty((B, 2, D), dtype=torch.float32, device=self.device) if want_pooled else None
+            if B == 0:
+                return (logits, pooled) if want_pooled else logits
+            ws, ws_bytes = self._workspace(B, L)
+            try:
+                _check(self.lib.pcad_forward_pooled(self._h, ids.data_ptr(), B, L, POOLING[pooling], w.data_ptr(), NL,
+                                                    pooled.data_ptr() if pooled is not None else None, logits.data_ptr(),
+                                                    ws, ws_bytes, _stream_ptr()), "pcad_forward_pooled")
+            finally:
+                self._status_host.copy_(self._status, non_blocking=True)
+                self._status_event.record()
+        return (logits, pooled) if want_pooled else logits
 
     # -- asynchronous input validation (include/pcad.h pcad_set_status_buffer) ----------------------------------------
     def _raise_status(self, bits: int):

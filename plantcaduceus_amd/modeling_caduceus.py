@@ -15,18 +15,20 @@ There is no CPU execution path: calling the model with CPU tensors raises.
 from __future__ import annotations
 
 import json
+import logging
 import os
 from typing import Optional, Sequence
 
 import torch
 from torch import nn
 from transformers import PreTrainedModel
-from transformers.modeling_outputs import BaseModelOutputWithNoAttention, MaskedLMOutput
+from transformers.modeling_outputs import BaseModelOutputWithNoAttention, MaskedLMOutput, SequenceClassifierOutput
 
 from .checkpoint import load_state_dict, resolve_snapshot
 from .configuration_caduceus import CaduceusConfig, config_from_dict
-from .engine import Engine
+from .engine import POOLING, Engine
 
+logger = logging.getLogger(__name__)
 
 # ---- parameter holders with the reference's names --------------------------------------------------
 class _Weight(nn.Module):
@@ -147,6 +149,7 @@ class CaduceusPreTrainedModel(PreTrainedModel):
     supports_gradient_checkpointing = False
     supports_positions = True     # forward(..., positions=[p, ...]) evaluates the head at those rows only
     _no_split_modules = ["_Block"]
+    _optional_keys = ()           # tensors a snapshot may lack (reported as missing, initialised by the class: `score.weight`)
 
     def _init_weights(self, module):   # weights always come from a checkpoint
         pass
@@ -173,9 +176,14 @@ class CaduceusPreTrainedModel(PreTrainedModel):
             pre = cls.base_model_prefix + "."
             sd = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
         own = model.state_dict()
-        missing = [k for k in own if k not in sd and not k.startswith("lm_head.")]
+        missing = [k for k in own if k not in sd and not k.startswith("lm_head.") and k not in cls._optional_keys]
         if missing:
             raise KeyError(f"checkpoint {path} lacks {len(missing)} tensors, e.g. {missing[:3]}")
+        newly = [k for k in cls._optional_keys if k in own and k not in sd]
+        if newly:
+            logger.warning("Some weights of %s were not initialized from the checkpoint at %s and are newly initialized: %s",
+                           cls.__name__, path, newly)
+            model._init_optional(newly)
         for k, p in own.items():
             src = sd.get(k)
             if src is None:
@@ -328,16 +336,138 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
         return MaskedLMOutput(loss=None, logits=logits, hidden_states=hs)
 
 
+class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
+    """`AutoModelForSequenceClassification` class: `.logits` fp32 [B, num_labels] - the fine-tuned PlantCAD2 models
+    (reference src/lora_fine_tune.py load_base_model: `from_pretrained(base, trust_remote_code=True, num_labels=...,
+    problem_type=...)`, then the PEFT adapter: plantcaduceus_amd.adapters.load_adapter).
+
+    Restated from the public Caduceus hub remote code, which `/reference` does not contain (recalled, not copied; pinned by
+    tests/test_gpu_seqcls.py's RC-invariance and engine self-consistency tests): for the RCPS model,
+        hs = stack([H[..., :D], flip(H[..., D:], dims=[1, 2])], -1)          H = hidden_states[-1]  [B, L, 2D]
+        pooled = pool(hs, dim=1)                                            mean (default) / max / first / last
+        logits = (score(pooled[..., 0]) + score(pooled[..., 1])) / 2        score = nn.Linear(D, num_labels, bias=False)
+    In the engine's 2B-strand form `flip(H[..., D:], [1, 2])[p]` is the reverse-complement strand's own row p, so the head
+    pools each strand over its own rows (csrc/pool.hip; pad tokens are part of the mean: there is no attention mask).
+    The loss (when `labels` are given) is computed from the logits without gradient, by HF's `problem_type` rules, so that the
+    `evaluate` command has it; there is no training path.  `conjoin_train` / `conjoin_eval` (the non-RCPS [B, L, 2] input form)
+    are refused."""
+    _optional_keys = ("score.weight",)
+
+    def __init__(self, config: CaduceusConfig, pooling_strategy: str = "mean", conjoin_train: bool = False,
+                 conjoin_eval: bool = False, **kwargs):
+        super().__init__(config)
+        if conjoin_train or conjoin_eval:
+            raise NotImplementedError("conjoin_train / conjoin_eval (the [B, L, 2] input form) are not supported by the MI355X engine")
+        if pooling_strategy not in POOLING:
+            raise NotImplementedError(f"pooling_strategy {pooling_strategy!r} is not one of {sorted(POOLING)}")
+        self.pooling_strategy = pooling_strategy
+        self.num_labels = config.num_labels
+        self.caduceus = Caduceus(config)
+        self.score = nn.Linear(config.d_model, config.num_labels, bias=False)
+        self.score.weight.requires_grad_(False)
+        self._init_optional(["score.weight"])
+
+    def _init_optional(self, keys):
+        """HF initialises a head the checkpoint lacks from `initializer_range`; here deterministically (seed 0), so that two loads
+        of the same base agree.  The adapter loader then supplies the trained `score`."""
+        if "score.weight" in keys:
+            g = torch.Generator().manual_seed(0)
+            std = float(getattr(self.config, "initializer_range", 0.02) or 0.02)
+            w = torch.randn(self.score.weight.shape, generator=g) * std
+            with torch.no_grad():
+                self.score.weight.copy_(w.to(self.score.weight.dtype).to(self.score.weight.device))
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, config=None, num_labels=None, problem_type=None,
+                        id2label=None, label2id=None, pooling_strategy=None, **kwargs):
+        hub_kw = {k: kwargs[k] for k in ("revision", "cache_dir", "local_files_only", "token") if k in kwargs}
+        path = resolve_snapshot(pretrained_model_name_or_path, **hub_kw)
+        if config is None:
+            with open(os.path.join(path, "config.json")) as f:
+                config = config_from_dict(json.load(f))
+        if id2label is not None:
+            config.id2label = {int(k): v for k, v in id2label.items()}
+            config.label2id = dict(label2id) if label2id is not None else {v: k for k, v in config.id2label.items()}
+        if num_labels is not None:
+            config.num_labels = int(num_labels)
+        if problem_type is not None:
+            config.problem_type = problem_type
+        model = super().from_pretrained(path, *model_args, config=config, **kwargs)
+        if pooling_strategy is not None:
+            if pooling_strategy not in POOLING:
+                raise NotImplementedError(f"pooling_strategy {pooling_strategy!r} is not one of {sorted(POOLING)}")
+            model.pooling_strategy = pooling_strategy
+        return model
+
+    def tie_weights(self, *a, **k):
+        pass
+
+    def _backbone_owner(self):
+        return self.caduceus
+
+    def get_input_embeddings(self):
+        return self.caduceus.backbone.embeddings.word_embeddings.embedding
+
+    def problem_type_for(self, labels: torch.Tensor) -> str:
+        """HF `*ForSequenceClassification` rule: config.problem_type if set, else regression for one label, single-label
+        classification for integer labels, multi-label otherwise."""
+        pt = getattr(self.config, "problem_type", None)
+        if pt:
+            return pt
+        if self.num_labels == 1:
+            return "regression"
+        if labels.dtype in (torch.long, torch.int, torch.int16, torch.int8, torch.uint8):
+            return "single_label_classification"
+        return "multi_label_classification"
+
+    def loss_from_logits(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """HF's loss of `*ForSequenceClassification` on fp32 logits (no gradient): MSE on the squeezed logits, cross-entropy, or
+        BCE-with-logits."""
+        from torch.nn import functional as F
+        with torch.no_grad():
+            labels = labels.to(logits.device)
+            pt = self.problem_type_for(labels)
+            if pt == "regression":
+                if self.num_labels == 1:
+                    return F.mse_loss(logits.squeeze(), labels.squeeze().to(logits.dtype))
+                return F.mse_loss(logits, labels.to(logits.dtype))
+            if pt == "single_label_classification":
+                return F.cross_entropy(logits.view(-1, self.num_labels), labels.view(-1).long())
+            return F.binary_cross_entropy_with_logits(logits, labels.to(logits.dtype))
+
+    def forward(self, input_ids=None, inputs_embeds=None, labels=None, output_hidden_states=None, return_dict=None,
+                pooled_out: bool = False, **kwargs):
+        if inputs_embeds is not None:
+            raise NotImplementedError("inputs_embeds is not supported by the MI355X engine")
+        if output_hidden_states:
+            raise NotImplementedError("output_hidden_states: use CaduceusForMaskedLM / Caduceus for hidden states")
+        eng = self._engine()
+        w = self.score.weight
+        if pooled_out:
+            logits, pooled = eng.forward_pooled(input_ids, self.pooling_strategy, w, want_pooled=True)
+        else:
+            logits, pooled = eng.forward_pooled(input_ids, self.pooling_strategy, w), None
+        loss = self.loss_from_logits(logits, labels) if labels is not None else None
+        if return_dict is False:
+            out = (logits,) if pooled is None else (logits, pooled)
+            return ((loss,) + out) if loss is not None else out
+        res = SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=None)
+        if pooled is not None:
+            res["pooled"] = pooled
+        return res
+
+
 def register_auto_classes():
     """Make `AutoConfig/AutoModel/AutoModelForMaskedLM/AutoTokenizer.from_pretrained(dir)` resolve
     `model_type == "caduceus"` to this package (instead of the HF-hub remote code)."""
-    from transformers import AutoConfig, AutoModel, AutoModelForMaskedLM, AutoTokenizer
+    from transformers import AutoConfig, AutoModel, AutoModelForMaskedLM, AutoModelForSequenceClassification, AutoTokenizer
     from .tokenization_caduceus import CaduceusTokenizer
     try:
         AutoConfig.register("caduceus", CaduceusConfig)
     except ValueError:
         pass
-    for auto, klass in ((AutoModel, Caduceus), (AutoModelForMaskedLM, CaduceusForMaskedLM)):
+    for auto, klass in ((AutoModel, Caduceus), (AutoModelForMaskedLM, CaduceusForMaskedLM),
+                        (AutoModelForSequenceClassification, CaduceusForSequenceClassification)):
         try:
             auto.register(CaduceusConfig, klass)
         except ValueError:

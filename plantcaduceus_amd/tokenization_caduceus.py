@@ -13,6 +13,12 @@ vocabulary wins.
 
 `encode_batch` is the engine's host fast path: a vectorised byte->id LUT over a whole batch, replacing
 the reference's per-sequence Python tokenisation in the main process.
+
+Padding / truncation (the reference's `tokenize` command, src/lora_fine_tune.py:130-136:
+`tokenizer(seqs, padding="max_length", truncation=True, max_length=N, add_special_tokens=False)`): [PAD] (id 0) on
+`padding_side`, truncation on the right (`truncation_side`).  The padding side comes from the snapshot's tokenizer_config.json;
+without one it is "left" - the default of Caduceus' `CharacterTokenizer` (hub remote code, recalled; not in /reference).
+`encode_batch_padded` is the vectorised form.  Without padding, unequal lengths are still refused where they would be stacked.
 """
 from __future__ import annotations
 
@@ -43,6 +49,7 @@ class CaduceusTokenizer(PreTrainedTokenizer):
         kwargs.setdefault("mask_token", "[MASK]")
         kwargs.setdefault("unk_token", "[UNK]")
         kwargs.pop("add_prefix_space", None)
+        kwargs.setdefault("padding_side", "left")       # CharacterTokenizer's default (recalled); tokenizer_config.json overrides
         super().__init__(model_max_length=model_max_length, **kwargs)
         self._lut = self._build_lut()
 
@@ -82,9 +89,21 @@ class CaduceusTokenizer(PreTrainedTokenizer):
     def _encode_ids(self, text: str) -> np.ndarray:
         return self._lut[np.frombuffer(text.encode("latin-1", "replace"), dtype=np.uint8)]
 
-    def __call__(self, text, return_tensors=None, add_special_tokens=False, **kwargs):
+    def __call__(self, text, return_tensors=None, add_special_tokens=False, padding=False, truncation=None, max_length=None,
+                 **kwargs):
         single = isinstance(text, str)
         seqs = [text] if single else list(text)
+        if padding not in (False, None, "do_not_pad") or (truncation and max_length is not None):
+            arr = self.encode_batch_padded(seqs, max_length=max_length, padding=padding, truncation=bool(truncation))
+            if return_tensors == "pt":
+                return {"input_ids": torch.from_numpy(arr.astype(np.int64))}
+            if return_tensors == "np":
+                return {"input_ids": arr.astype(np.int64)}
+            if isinstance(arr, list):
+                out = [a.tolist() for a in arr]
+            else:
+                out = arr.tolist()
+            return {"input_ids": out[0] if single else out}
         ids = [self._encode_ids(s) for s in seqs]
         if return_tensors == "pt":
             if len({len(i) for i in ids}) != 1:
@@ -110,6 +129,54 @@ class CaduceusTokenizer(PreTrainedTokenizer):
                 lut[ord(tok.lower())] = idx
                 lut[ord(tok.upper())] = idx
         return lut
+
+    def encode_batch_padded(self, sequences: Sequence[str], max_length: Optional[int] = None, padding="max_length",
+                            truncation: bool = True, padding_side: Optional[str] = None):
+        """[N] strings -> int32 [N, T] with [PAD] on `padding_side` (default: the tokenizer's).  padding "max_length": T =
+        max_length; True / "longest": T = the longest (truncated) sequence; False: no padding (then every truncated length
+        must be equal, or a list of arrays is returned).  truncation keeps the first max_length tokens (truncation on the right)."""
+        side = padding_side or getattr(self, "padding_side", "left")
+        if side not in ("left", "right"):
+            raise ValueError(f"padding_side must be 'left' or 'right', got {side!r}")
+        if getattr(self, "truncation_side", "right") != "right":
+            raise NotImplementedError("truncation_side 'left' is not implemented")
+        n = len(sequences)
+        lens = np.fromiter((len(s) for s in sequences), dtype=np.int64, count=n)
+        if truncation:
+            if max_length is None:
+                raise ValueError("truncation needs max_length")
+            tl = np.minimum(lens, int(max_length))
+        else:
+            tl = lens
+        if padding in (True, "longest"):
+            T = int(tl.max()) if n else 0
+        elif padding == "max_length":
+            if max_length is None:
+                raise ValueError("padding='max_length' needs max_length")
+            T = int(max_length)
+            if n and int(tl.max()) > T:
+                raise ValueError(f"a sequence of {int(tl.max())} tokens exceeds max_length={T} and truncation is off")
+        elif padding in (False, None, "do_not_pad"):
+            buf = "".join(sequences).encode("latin-1", "replace")
+            ids = self._lut[np.frombuffer(buf, dtype=np.uint8)]
+            starts = np.r_[0, np.cumsum(lens)[:-1]] if n else np.zeros(0, np.int64)
+            return [ids[a:a + int(k)] for a, k in zip(starts, tl)]
+        else:
+            raise ValueError(f"unsupported padding={padding!r}")
+        buf = "".join(sequences).encode("latin-1", "replace")
+        if len(buf) != int(lens.sum()):
+            raise ValueError("sequences must be single-byte text")
+        ids = self._lut[np.frombuffer(buf, dtype=np.uint8)]
+        out = np.full((n, T), self.pad_token_id, dtype=np.int32)
+        total = int(tl.sum())
+        if total:
+            row = np.repeat(np.arange(n), tl)
+            starts = np.r_[0, np.cumsum(lens)[:-1]]                 # start of each sequence in `buf`
+            first = np.r_[0, np.cumsum(tl)[:-1]]                    # start of each row's run among the kept tokens
+            intra = np.arange(total) - np.repeat(first, tl)
+            col0 = (T - tl) if side == "left" else np.zeros(n, dtype=np.int64)
+            out[row, np.repeat(col0, tl) + intra] = ids[np.repeat(starts, tl) + intra]
+        return out
 
     def encode_batch(self, sequences: Sequence[str], mask_index: Optional[int] = None) -> np.ndarray:
         """[N] equal-length strings -> int32 [N, L]; optionally overwrite column `mask_index` with
