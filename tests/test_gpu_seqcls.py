@@ -1,7 +1,7 @@
 """Sequence classification on the MI355X: the pooled head (csrc/pool.hip) as an operator, inside the forward
 (pcad_forward_pooled / CaduceusForSequenceClassification), and the LoRA predict / evaluate commands end to end.
 
-The head's CPU restatement lives here (head_ref): the recalled Caduceus remote code's
+The head's CPU restatement lives in tests/seqcls_ref.py (head_ref): the recalled Caduceus remote code's
     hs = stack([H[..., :D], flip(H[..., D:], dims=[1, 2])], -1); pooled = pool(hs, 1); logits = (score(p0) + score(p1)) / 2
 with the rounding points of DESIGN.md §4f, applied to hidden states (the oracle's, or this engine's own)."""
 import ctypes as C
@@ -21,45 +21,12 @@ from plantcaduceus_amd.adapters import make_synthetic_adapter
 from plantcaduceus_amd.checkpoint import make_config, save_checkpoint, synthetic_state_dict
 from plantcaduceus_amd.modeling_caduceus import CaduceusForMaskedLM, CaduceusForSequenceClassification
 from plantcaduceus_amd.ops import to_res_fragment
+from seqcls_ref import head_ref, pool_strands, rnd, score_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POOLINGS = ("mean", "max", "first", "last")
-
-
-def rnd(x, dtype):
-    return x.to(dtype).float() if dtype == torch.bfloat16 else x.float()
-
-
-def pool_strands(hs_f, hs_r, pooling, dtype):
-    """hs_*: [B, L, D] fp32 values already rounded to `dtype` -> pooled [B, 2, D] fp32 (mean: fp64 sum / L, rounded once)."""
-    out = []
-    for hs in (hs_f, hs_r):
-        if pooling == "mean":
-            out.append(rnd((hs.double().sum(1) / hs.shape[1]).float(), dtype))
-        elif pooling == "max":
-            out.append(hs.max(1).values)
-        elif pooling == "first":
-            out.append(hs[:, 0])
-        else:
-            out.append(hs[:, -1])
-    return torch.stack(out, 1)
-
-
-def score_ref(pooled, W, dtype):
-    W = rnd(W.float(), dtype).double()
-    a0 = rnd((pooled[:, 0].double() @ W.T).float(), dtype)
-    a1 = rnd((pooled[:, 1].double() @ W.T).float(), dtype)
-    return rnd(rnd(a0 + a1, dtype) / 2, dtype)
-
-
-def head_ref(H, W, pooling, dtype):
-    """The recalled remote code on an RCPS hidden state H [B, L, 2D] (values in `dtype`)."""
-    D = H.shape[-1] // 2
-    H = H.float().cpu()
-    pooled = pool_strands(H[..., :D], torch.flip(H[..., D:], dims=[1, 2]), pooling, dtype)
-    return score_ref(pooled, W.cpu(), dtype), pooled
 
 
 def dot_scale(pooled, W):
