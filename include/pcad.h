@@ -174,8 +174,9 @@ int    pcad_set_option(pcad_handle h, const char* key, int64_t value);
  * through a caller-owned DEVICE word: bit PCAD_STATUS_BAD_TOKEN / PCAD_STATUS_BAD_POSITION is OR-ed into *status by the
  * forward's last kernel (such an id is embedded as id & 7, such a position is clamped, so nothing is read out of bounds and
  * the affected rows are simply wrong).  The caller zeroes the word, and reads it at its next synchronisation point.
- * NULL (default): no reporting. */
-enum pcad_status_bits { PCAD_STATUS_BAD_TOKEN = 1, PCAD_STATUS_BAD_POSITION = 2 };
+ * NULL (default): no reporting.  pcad_forward_loss adds PCAD_STATUS_BAD_LABEL: a label that is neither ignored nor inside the
+ * vocabulary (the reference's cross entropy raises a device assert); such a position contributes nothing. */
+enum pcad_status_bits { PCAD_STATUS_BAD_TOKEN = 1, PCAD_STATUS_BAD_POSITION = 2, PCAD_STATUS_BAD_LABEL = 4 };
 int    pcad_set_status_buffer(pcad_handle h, int32_t* status);
 
 /* Bytes of caller-owned device memory that pcad_bind_weights packs the model into (depends on "norm_fold" / "reference_order" as set
@@ -236,6 +237,25 @@ enum pcad_pooling { PCAD_POOL_MEAN = 0, PCAD_POOL_MAX = 1, PCAD_POOL_FIRST = 2, 
 #define PCAD_MAX_LABELS 256
 int    pcad_forward_pooled(pcad_handle h, const int32_t* ids, int B, int L, int pooling, const float* score_w, int num_labels,
                            float* pooled_out, float* logits_out, void* workspace, size_t workspace_bytes, pcad_stream stream);
+
+/* Masked-LM loss (CaduceusForMaskedLM with labels; the --do_eval / --do_test half of the reference's src/HF_pre_train.py; DESIGN.md
+ * §4g).  The same layer walk as pcad_forward with positions == NULL (every row may be consumed: no last-layer shortcut), ending in
+ * the loss head instead of the LM head.  For every position p of window b whose label is not ignored:
+ *   logit[v] = pcad_forward's logits_out[b, p, v]  (the same arithmetic and rounding points, bit for bit)
+ *   nll      = logsumexp_v(logit) - logit[label]   (fp32, over all `vocab` logits, as F.cross_entropy)
+ *   labels        DEVICE int32 [B, L]; ignored when == ignore_index or < 0; any other value outside [0, vocab) sets
+ *                 PCAD_STATUS_BAD_LABEL (pcad_set_status_buffer) and contributes nothing
+ *   loss_weights  DEVICE fp32 [B, L] per-token weights w, or NULL (w = 1); the weight of an ignored position is never read into a sum
+ *   sums_out      DEVICE fp32 [B, 4] (required), per window: sum w nll, sum w, number of labelled positions, number of labelled
+ *                 positions whose arg-max logit (first index on ties) equals the label
+ *   nll_out       DEVICE fp32 [B, L] or NULL: nll (unweighted), 0 at ignored positions
+ *   logits_out    DEVICE fp32 [B, L, vocab] or NULL: as pcad_forward writes them; when NULL, rows whose label is ignored are not read
+ * Two stages (per-segment partials, then one fixed-order sum per window), no floating-point atomics; the segmentation depends on L
+ * only, so with "scan_segments" 0 a window's results are bit-identical alone, in any batch and under any "chunk_seqs".  The partials
+ * live in workspace buffers that are dead after the last out_proj: pcad_workspace_bytes is the forward's own. */
+int    pcad_forward_loss(pcad_handle h, const int32_t* ids, const int32_t* labels, const float* loss_weights, int ignore_index,
+                         int B, int L, float* sums_out, float* nll_out, float* logits_out,
+                         void* workspace, size_t workspace_bytes, pcad_stream stream);
 
 /* ---- measurement: per-kernel-class timing with HIP events on the caller's stream -------------------- */
 enum pcad_kernel_class {
@@ -373,6 +393,15 @@ int pcad_pooled_head(const void* h, const void* res, const float* norm_weight, c
                      float* pooled_out, float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids,
                      int32_t* status, int dtype, int res_dtype, int res_fragment_layout, void* scratch, size_t scratch_bytes,
                      pcad_stream stream);
+
+/* The loss head of pcad_forward_loss as one operator, with pcad_final_head's inputs (all L positions; no positions / h_compact):
+ * labels, loss_weights, ignore_index, sums_out, nll_out, logits_out as in pcad_forward_loss.  scratch: device buffer of
+ * pcad_loss_head_scratch_bytes(B, L) bytes, 256-byte aligned (the per-segment partials). */
+size_t pcad_loss_head_scratch_bytes(int B, int L);
+int pcad_loss_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                   const int32_t* labels, const float* loss_weights, int ignore_index, float* sums_out, float* nll_out,
+                   float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                   int res_fragment_layout, void* scratch, size_t scratch_bytes, pcad_stream stream);
 
 #ifdef __cplusplus
 }

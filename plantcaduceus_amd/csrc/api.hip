@@ -518,9 +518,19 @@ struct PoolRequest {
     float* logits_out;
 };
 
+// pcad_forward_loss: the masked-LM loss head in place of the LM head (loss.hip)
+struct LossRequest {
+    const int32_t* labels;
+    const float* loss_weights;
+    int ignore_index;
+    float* sums_out;
+    float* nll_out;
+    float* logits_out;
+};
+
 static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P,
                         const int32_t* pos_per_seq, void* all_hidden, void* hidden_out, float* logits_out, void* workspace, size_t ws_bytes,
-                        pcad_stream stream, const PoolRequest* pool = nullptr) {
+                        pcad_stream stream, const PoolRequest* pool = nullptr, const LossRequest* loss = nullptr) {
     if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward: null handle");
     pcad_engine* e = h;
     if (!e->bound) return fail(PCAD_ERR_UNBOUND, "pcad_forward: weights not bound");
@@ -818,6 +828,22 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                                        ids + (int64_t)c.b0 * L, e->status, dt, rdt, c.fold ? Dp : 0, part, cs));
             return PCAD_OK;
         }
+        if (loss) {
+            // per-segment partials in the buffers that are dead once the last out_proj has run, as the pooled head's
+            char* part = (char*)c.w.xz;
+            const size_t avail = (size_t)((char*)workspace + c.w.bytes - part);
+            if (loss_partial_bytes(c.Bc, L) > avail)
+                return fail(PCAD_ERR_WORKSPACE, "pcad_forward_loss: the head's partials (%zu bytes) do not fit the dead buffers (%zu)",
+                            loss_partial_bytes(c.Bc, L), avail);
+            const size_t o = (size_t)c.b0 * L;
+            ProfScope ps(e, PCAD_K_HEAD, cs);
+            HIP_TRY(launch_loss_head(c.w.h, c.w.res, e->normf_w, e->emb_f32, e->comp, loss->labels + o,
+                                     loss->loss_weights ? loss->loss_weights + o : nullptr, loss->ignore_index,
+                                     loss->sums_out + (size_t)c.b0 * 4, loss->nll_out ? loss->nll_out + o : nullptr,
+                                     loss->logits_out ? loss->logits_out + o * e->V : nullptr, c.Bc, L, D, eps,
+                                     ids + (int64_t)c.b0 * L, e->status, dt, rdt, c.fold ? Dp : 0, part, cs));
+            return PCAD_OK;
+        }
         void* hout = hidden_out ? (char*)hidden_out + ((size_t)c.b0 * Q * 2 * D) * esz : nullptr;
         float* lout = logits_out ? logits_out + (size_t)c.b0 * Q * e->V : nullptr;
         if (hout || lout) {
@@ -859,6 +885,16 @@ int pcad_forward_pooled(pcad_handle h, const int32_t* ids, int B, int L, int poo
     if (!score_w || !logits_out) return fail(PCAD_ERR_INVALID, "pcad_forward_pooled: null score_w / logits_out");
     const PoolRequest pr{pooling, score_w, num_labels, pooled_out, logits_out};
     return forward_impl(h, ids, B, L, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, &pr);
+}
+
+int pcad_forward_loss(pcad_handle h, const int32_t* ids, const int32_t* labels, const float* loss_weights, int ignore_index, int B,
+                      int L, float* sums_out, float* nll_out, float* logits_out, void* workspace, size_t workspace_bytes,
+                      pcad_stream stream) {
+    if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward_loss: null handle");
+    if (B < 0 || L <= 0) return fail(PCAD_ERR_INVALID, "pcad_forward_loss: bad B=%d L=%d", B, L);
+    if (B > 0 && (!labels || !sums_out)) return fail(PCAD_ERR_INVALID, "pcad_forward_loss: null labels / sums_out");
+    const LossRequest lr{labels, loss_weights, ignore_index, sums_out, nll_out, logits_out};
+    return forward_impl(h, ids, B, L, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, &lr);
 }
 
 int pcad_forward_at(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* pos_per_seq, void* hidden_out,
@@ -1104,6 +1140,30 @@ int pcad_pooled_head(const void* h, const void* res, const float* norm_weight, c
         return fail(PCAD_ERR_WORKSPACE, "pcad_pooled_head: scratch must be 256-byte aligned and pcad_pooled_head_scratch_bytes large");
     HIP_TRY(launch_pooled_head(h, res, norm_weight, score_w, num_labels, pooled_out, logits_out, B, L, D, eps, pooling, ids, status,
                                dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+size_t pcad_loss_head_scratch_bytes(int B, int L) {
+    if (B <= 0 || L <= 0) return 0;
+    return align_up(loss_partial_bytes(B, L));
+}
+
+int pcad_loss_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                   const int32_t* labels, const float* loss_weights, int ignore_index, float* sums_out, float* nll_out,
+                   float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                   int res_fragment_layout, void* scratch, size_t scratch_bytes, pcad_stream stream) {
+    if (!h || !res || !norm_weight || !emb_f32 || !complement || !labels || !sums_out || !scratch)
+        return fail(PCAD_ERR_INVALID, "pcad_loss_head: null argument");
+    if (res_fragment_layout && (res_dtype != PCAD_F32 || D % 256 || ((int64_t)2 * B * L) % 256))
+        return fail(PCAD_ERR_INVALID, "pcad_loss_head: the fragment layout needs an fp32 residual, D %% 256 == 0 and 2 B L %% 256 == 0");
+    if ((dtype != PCAD_F32 && dtype != PCAD_BF16) || (res_dtype != PCAD_F32 && res_dtype != PCAD_BF16) || (dtype == PCAD_F32 && res_dtype != PCAD_F32))
+        return fail(PCAD_ERR_INVALID, "pcad_loss_head: bad dtype / res_dtype");
+    if (B < 0 || L <= 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "pcad_loss_head: bad B / L / D");
+    if (B == 0) return PCAD_OK;
+    if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_loss_head_scratch_bytes(B, L))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_loss_head: scratch must be 256-byte aligned and pcad_loss_head_scratch_bytes large");
+    HIP_TRY(launch_loss_head(h, res, norm_weight, emb_f32, complement, labels, loss_weights, ignore_index, sums_out, nll_out, logits_out,
+                             B, L, D, eps, ids, status, dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
     return PCAD_OK;
 }
 

@@ -58,6 +58,17 @@ size_t pool_partial_bytes(int B, int L, int D, int pooling);
 hipError_t launch_pooled_head(const void* h, const void* res, const float* w, const float* score_w, int NL, float* pooled_out,
                               float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids, int32_t* status,
                               int dt, int rdt, int res_frag, void* part, hipStream_t s);
+// loss.hip: masked-LM loss head (pcad.h pcad_loss_head): launch_final_head's logits at every position (positions == NULL form) + the cross
+// entropy of the labelled ones, reduced per window into sums_out [B, 4] = { sum w nll, sum w, labelled, arg-max hits }.  labels [B, L]
+// (ignored: == ignore_index or < 0; other values outside [0, 8) set status bit 4), loss_w [B, L] or nullptr (all 1); nll_out [B, L] and
+// logits_out [B, L, 8] may be nullptr.  Stage 1 writes loss_partial_bytes(B, L) bytes of fp32 partials to `part` (16-byte aligned);
+// the segmentation depends on L only.
+int loss_segments(int L);
+size_t loss_partial_bytes(int B, int L);
+hipError_t launch_loss_head(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8,
+                            const int32_t* labels, const float* loss_w, int ignore_index, float* sums_out, float* nll_out,
+                            float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dt, int rdt,
+                            int res_frag, void* part, hipStream_t s);
 // hidden_states[i] (block input = previous mixer output / embedding) assembled in RCPS layout.
 hipError_t launch_assemble_hidden(const void* h, void* out, int B, int L, int D, int dt, hipStream_t s);
 hipError_t launch_embed_only(const int32_t* ids, const void* emb, const int32_t* comp8, void* h, int B, int L,

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "head_row.hpp"
 #include "kernels.hpp"
 
 namespace pcad {
@@ -245,65 +246,11 @@ __global__ __launch_bounds__(128) void final_head_kernel(const T* __restrict__ h
     }
     const int64_t row = wv == 0 ? ((int64_t)b * L + p) : ((int64_t)(B + b) * L + (L - 1 - p));
     const int64_t hrow = h_compact ? ((int64_t)(wv == 0 ? b : B + b) * Q + q) : row;     // mixer output: full tensor or evaluated rows only
-    const int nchunk = D >> 3;
-    float v[MAXC][8];
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXC; ++j) {
-        const int c = lane + 64 * j;
-        if (c < nchunk) {
-            float r[8];
-            load8<T>(h + hrow * D + c * 8, v[j]);
-            if (res_frag) {                  // norm-folded form: fp32 residual in the GEMM's fragment layout (RT == float)
-                const float* rp = reinterpret_cast<const float*>(res) + res_frag_off(row, c * 8, res_frag);      // res_frag = padded width Dp
-                const f32x4 a = *reinterpret_cast<const f32x4*>(rp), b = *reinterpret_cast<const f32x4*>(rp + 256);
-                r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3]; r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-            } else {
-                load8<RT>(res + row * D + c * 8, r);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { v[j][i] += r[i]; ss += v[j][i] * v[j][i]; }
-        }
-    }
-    ss = wave_sum(ss);
-    const float rstd = rsqrtf(ss / (float)D + eps);
+    // the strand's row: add + norm_f + its half of hidden_states[-1] + its 8 partial logits (head_row.hpp, shared with loss.hip)
     float acc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXC; ++j) {
-        const int c = lane + 64 * j;
-        if (c < nchunk) {
-            float wvv[8], o[8];
-            load8<float>(w + c * 8, wvv);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = Elem<T>::round(v[j][i] * rstd * wvv[i]);
-            if (hidden_out != nullptr) {
-                T* dst = hidden_out + ((int64_t)b * Q + q) * 2 * D;
-                if (wv == 0) {
-                    store8<T>(dst + c * 8, o);
-                } else {
-                    float rv[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) rv[i] = o[7 - i];
-                    store8<T>(dst + D + (D - 8 - c * 8), rv);
-                }
-            }
-            if (logits_out != nullptr) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int er = wv == 0 ? k : (comp8[k] & 7);
-                    float e[8];
-                    load8<float>(emb + (int64_t)er * D + c * 8, e);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[k] += o[i] * e[i];
-                }
-            }
-        }
-    }
+    head_row<T, RT, MAXC>(h + hrow * D, res, row, w, emb, comp8, D, eps, res_frag, wv, lane,
+                          hidden_out != nullptr ? hidden_out + ((int64_t)b * Q + q) * 2 * D : nullptr, logits_out != nullptr, acc);
     if (logits_out != nullptr) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = Elem<T>::round(wave_sum(acc[k]));
         if (wv == 1 && lane < 8) {
             float mine = acc[0];
 #pragma unroll

@@ -87,6 +87,12 @@ SIGNATURES = {
     "pcad_pooled_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_forward_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_loss_head_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "pcad_loss_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # include/pcad.h pcad_pooling (pooling_strategy of CaduceusForSequenceClassification)
@@ -95,7 +101,7 @@ MAX_LABELS = 256
 
 _lib = None
 
-STATUS_BAD_TOKEN, STATUS_BAD_POSITION = 1, 2       # include/pcad.h pcad_status_bits
+STATUS_BAD_TOKEN, STATUS_BAD_POSITION, STATUS_BAD_LABEL = 1, 2, 4       # include/pcad.h pcad_status_bits
 
 
 def source_hash() -> str:
@@ -319,6 +325,48 @@ class Engine:
                 self._status_event.record()
         return (logits, pooled) if want_pooled else logits
 
+    def forward_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, loss_weights: Optional[torch.Tensor] = None,
+                     ignore_index: int = -100, want_nll: bool = False, want_logits: bool = False):
+        """Masked-LM loss (`pcad_forward_loss`): ids / labels [B, L] (any int dtype) and loss_weights [B, L] (any float dtype) or
+        None, on this device -> (sums fp32 [B, 4], nll fp32 [B, L] | None, logits fp32 [B, L, 8] | None).  sums[b] = (sum w nll,
+        sum w, labelled positions, labelled positions whose arg-max logit is the label) of window b; a label equal to
+        ignore_index or negative is ignored, any other label outside the vocabulary is reported like a bad token id
+        (`check_status`).  Chunking, workspace and asynchronous input validation are those of `forward`."""
+        _require_gpu(input_ids, "input_ids")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        if input_ids.device != self.device:
+            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        if not torch.is_tensor(labels) or tuple(labels.shape) != tuple(input_ids.shape) or labels.is_floating_point():
+            raise ValueError(f"labels must be an integer tensor of input_ids' shape {tuple(input_ids.shape)}")
+        if loss_weights is not None and (not torch.is_tensor(loss_weights) or tuple(loss_weights.shape) != tuple(input_ids.shape)):
+            raise ValueError(f"loss_weights must be a tensor of input_ids' shape {tuple(input_ids.shape)}")
+        if not -2 ** 31 <= int(ignore_index) < 2 ** 31:
+            raise ValueError("ignore_index must fit in 32 bits")
+        self._poll_status()
+        ids = input_ids.to(torch.int32).contiguous()
+        B, L = ids.shape
+        with torch.cuda.device(self.device):
+            # int64 labels are clamped before they are narrowed, so that a huge value cannot alias a valid one
+            lab = labels.to(self.device).clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+            w = loss_weights.to(self.device).to(torch.float32).contiguous() if loss_weights is not None else None
+            sums = torch.empty((B, 4), dtype=torch.float32, device=self.device)
+            nll = torch.empty((B, L), dtype=torch.float32, device=self.device) if want_nll else None
+            logits = torch.empty((B, L, 8), dtype=torch.float32, device=self.device) if want_logits else None
+            if B == 0:
+                return sums, nll, logits
+            ws, ws_bytes = self._workspace(B, L)
+            try:
+                _check(self.lib.pcad_forward_loss(self._h, ids.data_ptr(), lab.data_ptr(), w.data_ptr() if w is not None else None,
+                                                  int(ignore_index), B, L, sums.data_ptr(),
+                                                  nll.data_ptr() if nll is not None else None,
+                                                  logits.data_ptr() if logits is not None else None, ws, ws_bytes, _stream_ptr()),
+                       "pcad_forward_loss")
+            finally:
+                self._status_host.copy_(self._status, non_blocking=True)
+                self._status_event.record()
+        return sums, nll, logits
+
     # -- asynchronous input validation (include/pcad.h pcad_set_status_buffer) ----------------------------------------
     def _raise_status(self, bits: int):
         self._status.zero_()
@@ -329,6 +377,8 @@ class Engine:
             what.append(f"input_ids contain token ids outside [0, {V}): check the tokenizer's vocabulary against the model")
         if bits & STATUS_BAD_POSITION:
             what.append("a per-window position is outside [0, L)")
+        if bits & STATUS_BAD_LABEL:
+            what.append(f"labels contain values that are neither ignored (ignore_index or negative) nor inside [0, {V})")
         raise IndexError("; ".join(what) + " (detected on the device; results of that forward are invalid)")
 
     def _poll_status(self):

@@ -298,6 +298,17 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
     `config.materialize_all_hidden_states = True` for the full n_layer+1 tuple.
     Extra (non-HF) keyword `positions=[p, ...]` evaluates the head only at those positions
     (logits [B, P, 8]) — the engine's fast path for zero-shot scoring.
+
+    With `labels` [B, L] (and optionally `loss_weights` [B, L], the per-token weights of the reference's
+    `src/HF_pre_train.py:424-437`) the forward ends in the engine's fused loss head (csrc/loss.hip) and returns
+    `MaskedLMOutput(loss=..., logits=...)`.  Loss arithmetic restated from the public Caduceus hub remote code, which the reference
+    tree does not contain (recalled, not copied): without weights the mean of the per-token cross entropy over the positions whose
+    label is not `ignore_index` (default -100; negative labels are ignored too), with weights `sum(w nll) / sum(w)` with `w`
+    zeroed at ignored positions — both `sums[:, 0].sum() / sums[:, 1].sum()` of the kernel's per-window sums, formed on the device
+    (no host synchronisation); a batch without labelled positions gives nan, as `F.cross_entropy` does.  Further non-HF
+    keywords: `ignore_index=`, `output_logits=False` (do not write the [B, L, 8] logits: rows without a label are then not even
+    read), `return_token_nll=True` (attach `token_nll` fp32 [B, L], 0 at ignored positions) and `return_window_sums=True`
+    (attach `window_sums` fp32 [B, 4]: sum w nll, sum w, labelled, arg-max hits per window).  There is no backward pass.
     """
 
     def __init__(self, config: CaduceusConfig, **kwargs):
@@ -316,11 +327,28 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
         return self.caduceus.backbone.embeddings.word_embeddings.embedding
 
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, output_hidden_states=None,
-                return_dict=None, positions: Optional[Sequence[int]] = None, **kwargs):
+                return_dict=None, positions: Optional[Sequence[int]] = None, loss_weights=None, ignore_index: int = -100,
+                output_logits: bool = True, return_token_nll: bool = False, return_window_sums: bool = False, **kwargs):
         if inputs_embeds is not None:
             raise NotImplementedError("inputs_embeds is not supported by the MI355X engine")
+        if labels is None and loss_weights is not None:
+            raise ValueError("loss_weights need labels")
         if labels is not None:
-            raise NotImplementedError("this is an inference engine: loss/labels are not supported")
+            if positions is not None:
+                raise ValueError("labels together with positions= is not supported: the loss head evaluates the positions the labels select")
+            if output_hidden_states:
+                raise NotImplementedError("output_hidden_states together with labels: run the model a second time without labels")
+            sums, nll, logits = self._engine().forward_loss(input_ids, labels, loss_weights, ignore_index=ignore_index,
+                                                            want_nll=bool(return_token_nll), want_logits=bool(output_logits))
+            loss = sums[:, 0].sum() / sums[:, 1].sum()        # on the device, torch's fixed reduction order; 0 / 0 = nan
+            if return_dict is False:
+                return (loss,) + ((logits,) if logits is not None else ())
+            res = MaskedLMOutput(loss=loss, logits=logits, hidden_states=None)
+            if nll is not None:
+                res["token_nll"] = nll
+            if return_window_sums:
+                res["window_sums"] = sums
+            return res
         eng = self._engine()
         hs = None
         if output_hidden_states and getattr(self.config, "materialize_all_hidden_states", False):
