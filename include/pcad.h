@@ -257,6 +257,32 @@ int    pcad_forward_loss(pcad_handle h, const int32_t* ids, const int32_t* label
                          int B, int L, float* sums_out, float* nll_out, float* logits_out,
                          void* workspace, size_t workspace_bytes, pcad_stream stream);
 
+/* Nucleotide probabilities: the forward ending in the probability head instead of the LM head.  For every evaluated
+ * (window b, position p):
+ *   logit[v]  = pcad_forward's logits_out[b, q, v]  (the same arithmetic and rounding points, bit for bit)
+ *   probs[j]  = exp(logit[cols[j]] - m) / sum_j exp(logit[cols[j]] - m),  m = max_j logit[cols[j]]     (fp32, as torch.softmax; the
+ *               only roundings after the logits are fp32's own: four exp, three adds, four divisions)
+ * Exactly one position form per call.  Let Q = L, P or P:
+ *   1. positions == NULL, pos_per_window == NULL, P == 0: all L positions; pcad_forward's layer walk
+ *   2. positions HOST int32 [P], 1 <= P <= PCAD_MAX_POSITIONS, shared by every window (each inside [0, L), else PCAD_ERR_INVALID);
+ *      pcad_forward's layer walk, "last_layer_shortcut" included
+ *   3. pos_per_window DEVICE int32 [B, P], 1 <= P <= PCAD_MAX_POSITIONS: window b is evaluated at its own P positions (P == 1:
+ *      pcad_forward_at's form); a value outside [0, L) is clamped AND reported as PCAD_STATUS_BAD_POSITION; pcad_forward_at's
+ *      layer walk (the full last layer)
+ *   cols        HOST int32 [4]: the vocabulary columns of the four classes, each inside [0, vocab) (the reference: the token ids of
+ *               a, c, g, t)
+ *   probs_out   DEVICE fp32 [B, Q, 4], 16-byte aligned, or NULL;  logits_out  DEVICE fp32 [B, Q, vocab] or NULL (not both NULL)
+ * One wave computes one (window, position) from that window's rows only and stores it once: with "scan_segments" 0 a window's
+ * probabilities are bit-identical alone, in any batch and under any "chunk_seqs".  pcad_workspace_bytes is the forward's own.
+ * PCAD_ERR_INVALID: cols outside [0, vocab); P outside its range; both position forms given.  Token ids outside the vocabulary are
+ * reported through pcad_set_status_buffer as by pcad_forward.
+ * Replaces: torch.softmax(model(input_ids=ids).logits[..., cols], dim=-1) at the read positions - src/zero_shot_score.py:116-119,
+ *           _masked_probs / _unmasked_probs of src/zero-shot-eval.py:129-178, and the per-window boundary reads of its
+ *           sv_effect (:425-472) in form 3. */
+int    pcad_forward_probs(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P,
+                          const int32_t* pos_per_window, const int32_t* cols, float* probs_out, float* logits_out,
+                          void* workspace, size_t workspace_bytes, pcad_stream stream);
+
 /* ---- measurement: per-kernel-class timing with HIP events on the caller's stream -------------------- */
 enum pcad_kernel_class {
     PCAD_K_NORM = 0, PCAD_K_GEMM_IN, PCAD_K_CONV, PCAD_K_GEMM_X, PCAD_K_SCAN, PCAD_K_GEMM_OUT, PCAD_K_HEAD,
@@ -402,6 +428,17 @@ int pcad_loss_head(const void* h, const void* res, const float* norm_weight, con
                    const int32_t* labels, const float* loss_weights, int ignore_index, float* sums_out, float* nll_out,
                    float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
                    int res_fragment_layout, void* scratch, size_t scratch_bytes, pcad_stream stream);
+
+/* The probability head of pcad_forward_probs as one operator, with pcad_final_head's inputs (h_compact and res_fragment_layout
+ * included; no hidden_out): cols (HOST int32 [4], each inside [0, PCAD_MAX_VOCAB)), probs_out [B, Q, 4] (16-byte aligned) and
+ * logits_out [B, Q, vocab] (bit-equal to pcad_final_head's) as in pcad_forward_probs, either may be NULL (not both).  Positions:
+ * positions (HOST int32 [P]; P == 0: all L) or pos_per_window (DEVICE int32 [B, P], 1 <= P <= PCAD_MAX_POSITIONS; clamped and
+ * reported through `status`), never both; h_compact needs the shared list.
+ * Replaces: pcad_final_head's logits + the host's column selection and torch.softmax. */
+int pcad_probs_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                    const int32_t* cols, float* probs_out, float* logits_out, int B, int L, int D, float eps, const int32_t* positions,
+                    int P, const int32_t* pos_per_window, int h_compact, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                    int res_fragment_layout, pcad_stream stream);
 
 #ifdef __cplusplus
 }

@@ -528,9 +528,19 @@ struct LossRequest {
     float* logits_out;
 };
 
+// pcad_forward_probs: the nucleotide-probability head in place of the LM head (probs.hip)
+struct ProbsRequest {
+    const int32_t* pos_per_window;     // device [B, Pw] or nullptr (then the forward's own positions / P apply)
+    int Pw;
+    ProbCols cols;
+    float* probs_out;
+    float* logits_out;
+};
+
 static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P,
                         const int32_t* pos_per_seq, void* all_hidden, void* hidden_out, float* logits_out, void* workspace, size_t ws_bytes,
-                        pcad_stream stream, const PoolRequest* pool = nullptr, const LossRequest* loss = nullptr) {
+                        pcad_stream stream, const PoolRequest* pool = nullptr, const LossRequest* loss = nullptr,
+                        const ProbsRequest* probs = nullptr) {
     if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward: null handle");
     pcad_engine* e = h;
     if (!e->bound) return fail(PCAD_ERR_UNBOUND, "pcad_forward: weights not bound");
@@ -844,6 +854,16 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                                      ids + (int64_t)c.b0 * L, e->status, dt, rdt, c.fold ? Dp : 0, part, cs));
             return PCAD_OK;
         }
+        if (probs) {
+            const int Qp = probs->pos_per_window ? probs->Pw : Q;
+            ProfScope ps(e, PCAD_K_HEAD, cs);
+            HIP_TRY(launch_probs_head(c.w.h, c.w.res, e->normf_w, e->emb_f32, e->comp, probs->cols,
+                                      probs->probs_out ? probs->probs_out + (size_t)c.b0 * Qp * 4 : nullptr,
+                                      probs->logits_out ? probs->logits_out + (size_t)c.b0 * Qp * e->V : nullptr, c.Bc, L, D, eps, pos,
+                                      probs->pos_per_window ? probs->pos_per_window + (size_t)c.b0 * Qp : nullptr, probs->Pw, dt, rdt, cs,
+                                      walk_len > 0, ids + (int64_t)c.b0 * L, e->status, c.fold ? Dp : 0));
+            return PCAD_OK;
+        }
         void* hout = hidden_out ? (char*)hidden_out + ((size_t)c.b0 * Q * 2 * D) * esz : nullptr;
         float* lout = logits_out ? logits_out + (size_t)c.b0 * Q * e->V : nullptr;
         if (hout || lout) {
@@ -895,6 +915,31 @@ int pcad_forward_loss(pcad_handle h, const int32_t* ids, const int32_t* labels, 
     if (B > 0 && (!labels || !sums_out)) return fail(PCAD_ERR_INVALID, "pcad_forward_loss: null labels / sums_out");
     const LossRequest lr{labels, loss_weights, ignore_index, sums_out, nll_out, logits_out};
     return forward_impl(h, ids, B, L, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, &lr);
+}
+
+static int probs_cols_arg(const char* who, const int32_t* cols, int vocab, ProbCols* out) {
+    if (!cols) return fail(PCAD_ERR_INVALID, "%s: null cols", who);
+    for (int j = 0; j < 4; ++j) {
+        if (cols[j] < 0 || cols[j] >= vocab) return fail(PCAD_ERR_INVALID, "%s: cols[%d]=%d outside [0, %d)", who, j, cols[j], vocab);
+        out->c[j] = cols[j];
+    }
+    return PCAD_OK;
+}
+
+int pcad_forward_probs(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P, const int32_t* pos_per_window,
+                       const int32_t* cols, float* probs_out, float* logits_out, void* workspace, size_t workspace_bytes,
+                       pcad_stream stream) {
+    if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward_probs: null handle");
+    if (positions && pos_per_window) return fail(PCAD_ERR_INVALID, "pcad_forward_probs: positions and pos_per_window are exclusive");
+    if (P < 0 || P > PCAD_MAX_POSITIONS || (P > 0 && !positions && !pos_per_window) || (P == 0 && (positions || pos_per_window)))
+        return fail(PCAD_ERR_INVALID, "pcad_forward_probs: bad positions (P=%d)", P);
+    if (!probs_out && !logits_out) return fail(PCAD_ERR_INVALID, "pcad_forward_probs: no output requested");
+    if (((uintptr_t)probs_out) % 16) return fail(PCAD_ERR_INVALID, "pcad_forward_probs: probs_out must be 16-byte aligned");
+    ProbsRequest pr{pos_per_window, pos_per_window ? P : 0, {}, probs_out, logits_out};
+    if (int rc = probs_cols_arg("pcad_forward_probs", cols, h->V < PCAD_MAX_VOCAB ? h->V : PCAD_MAX_VOCAB, &pr.cols)) return rc;
+    // shared positions: pcad_forward's walk (last-layer shortcut included); per-window lists: pcad_forward_at's (the full last layer)
+    return forward_impl(h, ids, B, L, pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, nullptr, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, stream, nullptr, nullptr, &pr);
 }
 
 int pcad_forward_at(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* pos_per_seq, void* hidden_out,
@@ -1164,6 +1209,33 @@ int pcad_loss_head(const void* h, const void* res, const float* norm_weight, con
         return fail(PCAD_ERR_WORKSPACE, "pcad_loss_head: scratch must be 256-byte aligned and pcad_loss_head_scratch_bytes large");
     HIP_TRY(launch_loss_head(h, res, norm_weight, emb_f32, complement, labels, loss_weights, ignore_index, sums_out, nll_out, logits_out,
                              B, L, D, eps, ids, status, dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_probs_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                    const int32_t* cols, float* probs_out, float* logits_out, int B, int L, int D, float eps, const int32_t* positions,
+                    int P, const int32_t* pos_per_window, int h_compact, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                    int res_fragment_layout, pcad_stream stream) {
+    if (!h || !res || !norm_weight || !emb_f32 || !complement) return fail(PCAD_ERR_INVALID, "pcad_probs_head: null argument");
+    if (!probs_out && !logits_out) return fail(PCAD_ERR_INVALID, "pcad_probs_head: no output requested");
+    if (((uintptr_t)probs_out) % 16) return fail(PCAD_ERR_INVALID, "pcad_probs_head: probs_out must be 16-byte aligned");
+    if (res_fragment_layout && (res_dtype != PCAD_F32 || D % 256 || ((int64_t)2 * B * L) % 256))
+        return fail(PCAD_ERR_INVALID, "pcad_probs_head: the fragment layout needs an fp32 residual, D %% 256 == 0 and 2 B L %% 256 == 0");
+    if ((dtype != PCAD_F32 && dtype != PCAD_BF16) || (res_dtype != PCAD_F32 && res_dtype != PCAD_BF16) || (dtype == PCAD_F32 && res_dtype != PCAD_F32))
+        return fail(PCAD_ERR_INVALID, "pcad_probs_head: bad dtype / res_dtype");
+    if (B < 0 || L <= 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "pcad_probs_head: bad B / L / D");
+    if (positions && pos_per_window) return fail(PCAD_ERR_INVALID, "pcad_probs_head: positions and pos_per_window are exclusive");
+    if (P < 0 || P > PCAD_MAX_POSITIONS || (P > 0 && !positions && !pos_per_window) || (P == 0 && (positions || pos_per_window)))
+        return fail(PCAD_ERR_INVALID, "pcad_probs_head: bad positions (P=%d)", P);
+    if (h_compact && (pos_per_window || P == 0)) return fail(PCAD_ERR_INVALID, "pcad_probs_head: h_compact needs a shared list of positions");
+    ProbCols pc;
+    if (int rc = probs_cols_arg("pcad_probs_head", cols, PCAD_MAX_VOCAB, &pc)) return rc;
+    Positions pos;
+    if (int rc = positions_arg("pcad_probs_head", pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, L, &pos)) return rc;
+    if (B == 0) return PCAD_OK;
+    HIP_TRY(launch_probs_head(h, res, norm_weight, emb_f32, complement, pc, probs_out, logits_out, B, L, D, eps, pos, pos_per_window,
+                              pos_per_window ? P : 0, dtype, res_dtype, (hipStream_t)stream, h_compact != 0, ids, status,
+                              res_fragment_layout ? D : 0));
     return PCAD_OK;
 }
 

@@ -1,4 +1,4 @@
-// One strand's row of the LM head, shared by final_head_kernel (norm.hip) and loss_stage1_kernel (loss.hip) so that there is ONE
+// One strand's row of the LM head, shared by final_head_kernel (norm.hip), loss_stage1_kernel (loss.hip) and probs_head_kernel (probs.hip): ONE
 // head arithmetic:  v = h + res (fp32);  o = round(v * rstd(v) * w);  acc[k] = round(o . Emb[strand 0: k, strand 1: comp[k]]).
 // One wave per row, 8 columns per lane and step (16-byte accesses); `row` indexes the full [2B * L, D] residual tensor, h_row
 // points at the mixer output's row.  res_frag != 0: fp32 residual in the GEMM's fragment layout of that (padded) width.

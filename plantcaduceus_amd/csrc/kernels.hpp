@@ -69,6 +69,15 @@ hipError_t launch_loss_head(const void* h, const void* res, const float* w, cons
                             const int32_t* labels, const float* loss_w, int ignore_index, float* sums_out, float* nll_out,
                             float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dt, int rdt,
                             int res_frag, void* part, hipStream_t s);
+// probs.hip: nucleotide-probability head (pcad.h pcad_probs_head): launch_final_head's logits at the evaluated positions + the fp32
+// softmax over the four vocabulary columns `cols`, probs_out [B, Q, 4] (16-byte aligned); logits_out [B, Q, 8]; either may be nullptr.
+// Positions: all L (pos.n == 0), the shared list `pos` (h_compact allowed), or pos_per_window (device [B, Pw], 1 <= Pw <= 16, pos.n == 0;
+// values outside [0, L) are clamped and set status bit 2).
+struct ProbCols { int c[4]; };        // by-value kernel argument
+hipError_t launch_probs_head(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8, ProbCols cols,
+                             float* probs_out, float* logits_out, int B, int L, int D, float eps, Positions pos,
+                             const int32_t* pos_per_window, int Pw, int dt, int rdt, hipStream_t s, bool h_compact = false,
+                             const int32_t* ids = nullptr, int32_t* status = nullptr, int res_frag = 0);
 // hidden_states[i] (block input = previous mixer output / embedding) assembled in RCPS layout.
 hipError_t launch_assemble_hidden(const void* h, void* out, int B, int L, int D, int dt, hipStream_t s);
 hipError_t launch_embed_only(const int32_t* ids, const void* emb, const int32_t* comp8, void* h, int B, int L,

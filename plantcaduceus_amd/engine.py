@@ -93,11 +93,17 @@ SIGNATURES = {
     "pcad_loss_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_forward_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                     C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_probs_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 # include/pcad.h pcad_pooling (pooling_strategy of CaduceusForSequenceClassification)
 POOLING = {"mean": 0, "max": 1, "first": 2, "last": 3}
 MAX_LABELS = 256
+MAX_POSITIONS = 16      # include/pcad.h PCAD_MAX_POSITIONS
 
 _lib = None
 
@@ -366,6 +372,56 @@ class Engine:
                 self._status_host.copy_(self._status, non_blocking=True)
                 self._status_event.record()
         return sums, nll, logits
+
+    def forward_probs(self, input_ids: torch.Tensor, cols, positions=None, positions_per_window: Optional[torch.Tensor] = None,
+                      want_logits: bool = False):
+        """Nucleotide probabilities (`pcad_forward_probs`): ids [B, L] on this device -> probs fp32 [B, Q, 4] (and, with
+        want_logits, the logits fp32 [B, Q, 8] they were formed from): the softmax over the four vocabulary columns `cols` of the
+        LM head's logits, taken on the device.  positions: None (all L) or a short list shared by every window;
+        positions_per_window: an integer tensor [B, P] (1 <= P <= 16) on this device, window b's own positions - a value outside
+        [0, L) is clamped and reported like a bad token id (`check_status`).  At most one of the two.  Chunking, workspace and
+        asynchronous input validation are those of `forward`."""
+        _require_gpu(input_ids, "input_ids")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        if input_ids.device != self.device:
+            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        cols = [int(c) for c in cols]
+        if len(cols) != 4:
+            raise ValueError(f"cols must name four vocabulary columns, got {cols}")
+        if positions is not None and positions_per_window is not None:
+            raise ValueError("positions and positions_per_window are exclusive")
+        self._poll_status()
+        ids = input_ids.to(torch.int32).contiguous()
+        B, L = ids.shape
+        ppw = None
+        if positions_per_window is not None:
+            ppw = positions_per_window
+            if (not torch.is_tensor(ppw) or ppw.is_floating_point() or ppw.dim() != 2 or ppw.shape[0] != B
+                    or not 1 <= ppw.shape[1] <= MAX_POSITIONS or ppw.device != self.device):
+                raise ValueError(f"positions_per_window must be an integer tensor [B, 1..{MAX_POSITIONS}] on the engine's device")
+            # int64 positions are clamped before they are narrowed, so that a huge value cannot alias a valid one
+            ppw = ppw.clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+            P = int(ppw.shape[1])
+        else:
+            P = 0 if positions is None else len(positions)
+        Q = P if P else L
+        with torch.cuda.device(self.device):
+            probs = torch.empty((B, Q, 4), dtype=torch.float32, device=self.device)
+            logits = torch.empty((B, Q, 8), dtype=torch.float32, device=self.device) if want_logits else None
+            if B == 0:
+                return (probs, logits) if want_logits else probs
+            ws, ws_bytes = self._workspace(B, L)
+            pos_arr = (C.c_int32 * P)(*[int(p) for p in positions]) if (P and ppw is None) else None
+            try:
+                _check(self.lib.pcad_forward_probs(self._h, ids.data_ptr(), B, L, pos_arr, P, ppw.data_ptr() if ppw is not None else None,
+                                                   (C.c_int32 * 4)(*cols), probs.data_ptr(),
+                                                   logits.data_ptr() if logits is not None else None, ws, ws_bytes, _stream_ptr()),
+                       "pcad_forward_probs")
+            finally:
+                self._status_host.copy_(self._status, non_blocking=True)
+                self._status_event.record()
+        return (probs, logits) if want_logits else probs
 
     # -- asynchronous input validation (include/pcad.h pcad_set_status_buffer) ----------------------------------------
     def _raise_status(self, bits: int):

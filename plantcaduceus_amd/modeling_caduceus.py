@@ -309,7 +309,13 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
     keywords: `ignore_index=`, `output_logits=False` (do not write the [B, L, 8] logits: rows without a label are then not even
     read), `return_token_nll=True` (attach `token_nll` fp32 [B, L], 0 at ignored positions) and `return_window_sums=True`
     (attach `window_sums` fp32 [B, 4]: sum w nll, sum w, labelled, arg-max hits per window).  There is no backward pass.
+
+    `nucleotide_probs(input_ids, cols, ...)` (non-HF; `supports_nucleotide_probs`) returns `softmax(logits[..., cols])` over four
+    vocabulary columns, formed on the device by the engine's probability head (csrc/probs.hip) - at every position,
+    at a shared list of positions, or at a list of positions per window.
     """
+
+    supports_nucleotide_probs = True     # nucleotide_probs(...) evaluates the four-way probabilities on the device
 
     def __init__(self, config: CaduceusConfig, **kwargs):
         super().__init__(config)
@@ -325,6 +331,18 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
 
     def get_input_embeddings(self):
         return self.caduceus.backbone.embeddings.word_embeddings.embedding
+
+    def nucleotide_probs(self, input_ids, cols: Sequence[int], positions: Optional[Sequence[int]] = None,
+                         positions_per_window: Optional[torch.Tensor] = None, return_logits: bool = False):
+        """fp32 [B, Q, 4]: `torch.softmax(self(input_ids).logits[..., cols].float(), -1)` at the evaluated rows, without writing the
+        8-wide logits - what the reference's probability loops compute (src/zero_shot_score.py:116-119, src/zero-shot-eval.py
+        `_masked_probs` / `_unmasked_probs`).  cols: four vocabulary columns (the token ids of a, c, g, t).  positions: None (all L
+        positions) or up to 16 positions shared by every window; positions_per_window: integer tensor [B, P] (P <= 16) on the
+        model's device, each window's own positions - the boundary reads of `sv_effect`; a value outside the window is reported
+        by `check_status()`.  return_logits: also return the fp32 [B, Q, 8] logits the probabilities were formed from (bit-equal
+        to `forward`'s)."""
+        return self._engine().forward_probs(input_ids, cols, positions=positions, positions_per_window=positions_per_window,
+                                            want_logits=bool(return_logits))
 
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, output_hidden_states=None,
                 return_dict=None, positions: Optional[Sequence[int]] = None, loss_weights=None, ignore_index: int = -100,

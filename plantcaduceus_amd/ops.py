@@ -404,3 +404,35 @@ def final_head(h, res, norm_weight, emb, complement, B: int, L: int, eps: float,
                                    ids.data_ptr() if ids is not None else None, status.data_ptr() if status is not None else None,
                                    _dt(hf), _DT[rf.dtype], int(bool(res_fragment)), _stream_ptr()), "pcad_final_head")
     return hid, lg
+
+
+def probs_head(h, res, norm_weight, emb, complement, cols, B: int, L: int, eps: float, positions=None, positions_per_window=None,
+               h_compact: bool = False, want_probs: bool = True, want_logits: bool = False, ids=None, status=None,
+               res_fragment: bool = False):
+    """norm_f + tied RCPS LM head + fp32 softmax over the four vocabulary columns `cols`, at the requested positions
+    (include/pcad.h pcad_probs_head).  h / res / emb / ids / status as in `final_head`; positions: None (all L) or a shared list;
+    positions_per_window: integer tensor [B, P] on h's device (exclusive with positions).
+    -> (probs fp32 [B, Q, 4] | None, logits fp32 [B, Q, V] | None)."""
+    import ctypes as C
+    _require_gpu(h, "h")
+    lib = load_library()
+    D = h.shape[-1]
+    V = emb.shape[0]
+    ppw = positions_per_window.to(torch.int32).contiguous() if positions_per_window is not None else None
+    P = int(ppw.shape[1]) if ppw is not None else (0 if positions is None else len(positions))
+    Q = P if P else L
+    hf, rf = h.contiguous(), res.contiguous()
+    w = norm_weight.float().contiguous()
+    e32 = emb.to(h.dtype).float().contiguous()
+    comp = torch.as_tensor(list(complement), dtype=torch.int32, device=h.device)
+    pr = torch.empty((B, Q, 4), dtype=torch.float32, device=h.device) if want_probs else None
+    lg = torch.empty((B, Q, V), dtype=torch.float32, device=h.device) if want_logits else None
+    arr = (C.c_int32 * P)(*[int(p) for p in positions]) if positions is not None and len(positions) else None
+    with torch.cuda.device(h.device):
+        _check(lib.pcad_probs_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(),
+                                   (C.c_int32 * 4)(*[int(c) for c in cols]), pr.data_ptr() if pr is not None else None,
+                                   lg.data_ptr() if lg is not None else None, B, L, D, float(eps), arr, P,
+                                   ppw.data_ptr() if ppw is not None else None, int(bool(h_compact)),
+                                   ids.data_ptr() if ids is not None else None, status.data_ptr() if status is not None else None,
+                                   _dt(hf), _DT[rf.dtype], int(bool(res_fragment)), _stream_ptr()), "pcad_probs_head")
+    return pr, lg

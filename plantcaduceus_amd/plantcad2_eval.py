@@ -5,8 +5,11 @@
                   every sequence, softmax over a,c,g,t of the logits AT the masked positions -> [N * n_mask, 4], rows in
                   (sequence, ascending position) order (the order of the reference's `torch.masked_select`)
   unmasked_probs  `_unmasked_probs` (:143-178): per-position probabilities of the un-masked sequence -> [N, L, 4]
+  boundary_probs  the same probabilities at a list of positions PER window -> [N, P, 4]: what `sv_effect` reads of them
 
-Only the head rows that are read are evaluated (`positions=`); tokenisation is the vectorised LUT.
+Only the head rows that are read are evaluated (`positions=`); tokenisation is the vectorised LUT.  A model with
+`supports_nucleotide_probs` (the engine's `CaduceusForMaskedLM`) forms the four-way softmax on the device
+(`model.nucleotide_probs`); any other model goes through `.logits` and `torch.softmax`.
 
 Task metrics and drivers on top of them (same file, `:181-320` and `ZeroShotEval` `:323-530`), vectorised numpy, no
 sklearn: `true_tokens`, `token_accuracy`, `motif_accuracy`, `refprob_scores`, `auroc`, `average_precision`,
@@ -29,6 +32,7 @@ from .zero_shot import check_model_inputs, tokenize_masked
 NUCLEOTIDES_LOWER = ("a", "c", "g", "t")
 
 
+MAX_POSITIONS = 16       # positions per window a model's head evaluates in one call (include/pcad.h PCAD_MAX_POSITIONS)
 GATHER_CHUNK = 4096      # windows per rank between two all-gathers of the sharded loops (not per batch: one collective per chunk)
 
 
@@ -67,6 +71,7 @@ def masked_probs(model, tokenizer, sequences: Sequence[str], mask_idx: Union[int
     seqs = list(sequences)
     n = len(seqs)
     fast = bool(getattr(model, "supports_positions", False)) and len(idx) <= 16
+    fused = bool(getattr(model, "supports_nucleotide_probs", False)) and len(idx) <= MAX_POSITIONS
 
     def run_rows(lo, hi):
         if hi <= lo:
@@ -78,6 +83,9 @@ def masked_probs(model, tokenizer, sequences: Sequence[str], mask_idx: Union[int
         parts = []
         for b0 in range(0, ids.shape[0], batch_size):
             cur = ids[b0:b0 + batch_size].to(device)
+            if fused:               # softmax over a,c,g,t on the device, at the masked rows only
+                parts.append(model.nucleotide_probs(cur, cols, positions=idx))
+                continue
             lg = model(input_ids=cur, positions=idx).logits if fast else model(input_ids=cur).logits[:, idx, :]
             parts.append(torch.softmax(lg[..., cols].float(), dim=-1))
         return torch.cat(parts, dim=0)
@@ -98,6 +106,7 @@ def unmasked_probs(sequences: Sequence[str], tokenizer, model, device, batch_siz
     if len({len(s) for s in seqs}) > 1:
         raise ValueError("All sequences must have same length")
     L = len(seqs[0]) if seqs else 0
+    fused = bool(getattr(model, "supports_nucleotide_probs", False))
 
     def run_rows(lo, hi):
         if hi <= lo:
@@ -105,6 +114,9 @@ def unmasked_probs(sequences: Sequence[str], tokenizer, model, device, batch_siz
         ids = torch.from_numpy(tokenize_masked(seqs[lo:hi], tokenizer, None).astype(np.int64))
         parts = []
         for b0 in range(0, ids.shape[0], batch_size):
+            if fused:               # the head writes [B, L, 4] probabilities instead of [B, L, 8] logits
+                parts.append(model.nucleotide_probs(ids[b0:b0 + batch_size].to(device), cols))
+                continue
             lg = model(input_ids=ids[b0:b0 + batch_size].to(device)).logits[..., cols]
             parts.append(torch.softmax(lg.float(), dim=-1))
         return torch.cat(parts, dim=0)
@@ -114,6 +126,45 @@ def unmasked_probs(sequences: Sequence[str], tokenizer, model, device, batch_siz
     chunk = max(1, min(GATHER_CHUNK, (1 << 30) // max(1, L * 16)))
     with torch.inference_mode():
         _sharded_rows(len(seqs), run_rows, out, chunk)
+    check_model_inputs(model)
+    return out
+
+
+def boundary_probs(sequences: Sequence[str], positions_per_window, tokenizer, model, device, batch_size: int = 32) -> np.ndarray:
+    """Un-masked probabilities of window i at its own positions `positions_per_window[i]` ([n, P] integers, P <= MAX_POSITIONS)
+    -> [n, P, 4]: the rows `unmasked_probs(...)[i, positions_per_window[i]]`, evaluated by a model with `supports_nucleotide_probs`
+    without materialising (or gathering) the [n, L, 4] array.  Sharded under torchrun like unmasked_probs: P * 16 bytes per
+    window cross the all-gather instead of L * 16.  A position outside [0, L) raises IndexError on every rank before any
+    collective."""
+    if not getattr(model, "supports_nucleotide_probs", False):
+        raise TypeError("boundary_probs needs a model with supports_nucleotide_probs (nucleotide_probs(..., positions_per_window=))")
+    cols = [tokenizer.get_vocab()[n] for n in NUCLEOTIDES_LOWER]
+    seqs = [str(s) for s in sequences]
+    if len({len(s) for s in seqs}) > 1:
+        raise ValueError("All sequences must have same length")
+    L = len(seqs[0]) if seqs else 0
+    pos = np.array(positions_per_window, dtype=np.int64)          # a copy: the caller's may be a read-only broadcast view
+    if pos.ndim != 2 or pos.shape[0] != len(seqs) or not 1 <= pos.shape[1] <= MAX_POSITIONS:
+        raise ValueError(f"positions_per_window must be [n = {len(seqs)}, 1..{MAX_POSITIONS}], got {pos.shape}")
+    if pos.size and (pos.min() < 0 or pos.max() >= L):
+        bad = int(pos[(pos < 0) | (pos >= L)][0])
+        raise IndexError(f"index {bad} is out of bounds for axis 1 with size {L}")
+    P = pos.shape[1]
+
+    def run_rows(lo, hi):
+        if hi <= lo:
+            return torch.zeros((0, P, 4), dtype=torch.float32, device=device)
+        ids = torch.from_numpy(tokenize_masked(seqs[lo:hi], tokenizer, None).astype(np.int64))
+        at = torch.from_numpy(pos[lo:hi])
+        parts = []
+        for b0 in range(0, ids.shape[0], batch_size):
+            parts.append(model.nucleotide_probs(ids[b0:b0 + batch_size].to(device), cols,
+                                                positions_per_window=at[b0:b0 + batch_size].to(device)))
+        return torch.cat(parts, dim=0)
+
+    out = np.zeros((len(seqs), P, 4), dtype=np.float32)
+    with torch.inference_mode():
+        _sharded_rows(len(seqs), run_rows, out)
     check_model_inputs(model)
     return out
 
@@ -234,25 +285,48 @@ def avg_trueprob_scores(probs: np.ndarray, tokens, motif_len: int) -> np.ndarray
     return v.reshape(-1, motif_len).mean(axis=1)
 
 
+def _sv_positions(left, right, L: int, flanking: int):
+    """0-based rows `_sv_llr_boundary` reads: ref_pos [n, 2F] of the reference window (1-based `left`, `right`:
+    [left-flanking, left-1] and [right+1, right+flanking]) and mut_pos [2F], the central 2*flanking positions."""
+    c0 = L // 2
+    k = np.arange(flanking)
+    left = np.asarray(left, dtype=np.int64)
+    right = np.asarray(right, dtype=np.int64)
+    ref_pos = np.concatenate([left[:, None] - flanking + k[None, :] - 1, right[:, None] + k[None, :]], axis=1)   # 0-based
+    return ref_pos, np.arange(c0 - flanking, c0 + flanking)
+
+
+def _sv_llr_rows(mut_seqs, mut_pos, ref_rows: np.ndarray, mut_rows: np.ndarray) -> np.ndarray:
+    """The boundary LLR from the probabilities AT the read rows: ref_rows / mut_rows [n, 2F, 4] = ref_probs[i, ref_pos[i]] /
+    mut_probs[i, mut_pos] - selected from the dense arrays (sv_llr_boundary) or evaluated at those rows only (boundary_probs)."""
+    base = _codes(mut_seqs, mut_pos)                                                # [n, 2F]
+    rows = np.arange(base.shape[0])[:, None]
+    q = np.arange(base.shape[1])[None, :]
+    j = np.where(base >= 0, base, 0)
+    r = np.maximum(np.asarray(ref_rows)[rows, q, j], 1e-12)
+    m = np.maximum(np.asarray(mut_rows)[rows, q, j], 1e-12)
+    llr = np.where(base >= 0, np.log(m / r), 0.0)
+    return -llr.mean(axis=1)
+
+
 def sv_llr_boundary(left, right, mut_seqs, ref_probs: np.ndarray, mut_probs: np.ndarray, flanking: int) -> np.ndarray:
     """`_sv_llr_boundary` (:181-243): -mean over 2*flanking positions of log(p_mut / p_ref) of the MUTATED sequence's base;
     ref windows (1-based `left`, `right`): [left-flanking, left-1] and [right+1, right+flanking]; mut window: the central
     2*flanking positions of the mutated sequence; unknown bases contribute 0; probabilities floored at 1e-12."""
     ref_probs, mut_probs = np.asarray(ref_probs), np.asarray(mut_probs)
     n, L = ref_probs.shape[0], ref_probs.shape[1]
-    c0 = L // 2
-    k = np.arange(flanking)
-    left = np.asarray(left, dtype=np.int64)
-    right = np.asarray(right, dtype=np.int64)
-    ref_pos = np.concatenate([left[:, None] - flanking + k[None, :] - 1, right[:, None] + k[None, :]], axis=1)   # 0-based
-    mut_pos = np.arange(c0 - flanking, c0 + flanking)
-    base = _codes(mut_seqs, mut_pos)                                                # [n, 2F]
+    ref_pos, mut_pos = _sv_positions(left, right, L, flanking)
     rows = np.arange(n)[:, None]
-    j = np.where(base >= 0, base, 0)
-    r = np.maximum(ref_probs[rows, ref_pos, j], 1e-12)
-    m = np.maximum(mut_probs[rows, mut_pos[None, :], j], 1e-12)
-    llr = np.where(base >= 0, np.log(m / r), 0.0)
-    return -llr.mean(axis=1)
+    return _sv_llr_rows(mut_seqs, mut_pos, ref_probs[rows, ref_pos], mut_probs[rows, mut_pos[None, :]])
+
+
+def _wrap_index(pos: np.ndarray, size: int) -> np.ndarray:
+    """numpy's integer indexing of an axis of `size` rows: [-size, 0) counts from the end, anything else outside [0, size) raises."""
+    pos = np.asarray(pos, dtype=np.int64)
+    if pos.size and (pos.min() < -size or pos.max() >= size):
+        bad = int(pos[(pos < -size) | (pos >= size)].flat[0])
+        raise IndexError(f"index {bad} is out of bounds for axis 1 with size {size}")
+    return np.where(pos < 0, pos + size, pos)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -353,19 +427,38 @@ def core_noncore(data, model=None, tokenizer=None, device="cuda:0", mask_idx: Se
 
 def sv_effect(data, model, tokenizer, device="cuda:0", batch_size: int = 64, flanking: int = 5, output=None,
               save_ref_logits=None, save_mut_logits=None) -> Dict[str, float]:
-    """:430-476 - un-masked probabilities of RefSeq and MutSeq, boundary LLR per row, AUPRC against `label`."""
+    """:430-476 - un-masked probabilities of RefSeq and MutSeq, boundary LLR per row, AUPRC against `label`.  A model with
+    `supports_nucleotide_probs` evaluates only the 2 * flanking rows per window the LLR reads (boundary_probs) unless the dense
+    probabilities are to be saved (`save_ref_logits` / `save_mut_logits`) or 2 * flanking exceeds MAX_POSITIONS."""
     df = _frame(data)
     missing = [c for c in ("RefSeq", "MutSeq", "left", "right", "label") if c not in df.columns]
     if missing:
         raise KeyError(f"Missing required columns: {missing}")
-    ref_p = unmasked_probs(df["RefSeq"], tokenizer, model, device, batch_size)
-    mut_p = unmasked_probs(df["MutSeq"], tokenizer, model, device, batch_size)
     rank0 = sharding.world()[0] == 0
-    if save_ref_logits and rank0:
-        np.savez_compressed(save_ref_logits, logits=ref_p)
-    if save_mut_logits and rank0:
-        np.savez_compressed(save_mut_logits, logits=mut_p)
-    scores = sv_llr_boundary(df["left"], df["right"], df["MutSeq"], ref_p, mut_p, flanking)
+    sparse = (bool(getattr(model, "supports_nucleotide_probs", False)) and 1 <= 2 * flanking <= MAX_POSITIONS
+              and not save_ref_logits and not save_mut_logits and len(df) > 0)
+    if sparse:
+        # only the 2 * flanking rows per window that the LLR reads are evaluated, gathered and copied: 2F * 16 bytes per sequence
+        # instead of L * 16.  The positions are checked here as sv_llr_boundary's indexing checks them (numpy semantics), on every
+        # rank, before the first collective.
+        ref_seqs, mut_seqs = [str(x) for x in df["RefSeq"]], [str(x) for x in df["MutSeq"]]
+        if len({len(x) for x in ref_seqs}) > 1 or len({len(x) for x in mut_seqs}) > 1:
+            raise ValueError("All sequences must have same length")
+        ref_pos, mut_pos = _sv_positions(df["left"], df["right"], len(ref_seqs[0]), flanking)
+        ref_at = _wrap_index(ref_pos, len(ref_seqs[0]))
+        mut_at = _wrap_index(mut_pos, len(mut_seqs[0]))
+        _codes(mut_seqs, mut_pos)                       # the bases the LLR reads exist
+        ref_rows = boundary_probs(ref_seqs, ref_at, tokenizer, model, device, batch_size)
+        mut_rows = boundary_probs(mut_seqs, np.broadcast_to(mut_at, (len(mut_seqs), len(mut_at))), tokenizer, model, device, batch_size)
+        scores = _sv_llr_rows(mut_seqs, mut_pos, ref_rows, mut_rows)
+    else:
+        ref_p = unmasked_probs(df["RefSeq"], tokenizer, model, device, batch_size)
+        mut_p = unmasked_probs(df["MutSeq"], tokenizer, model, device, batch_size)
+        if save_ref_logits and rank0:
+            np.savez_compressed(save_ref_logits, logits=ref_p)
+        if save_mut_logits and rank0:
+            np.savez_compressed(save_mut_logits, logits=mut_p)
+        scores = sv_llr_boundary(df["left"], df["right"], df["MutSeq"], ref_p, mut_p, flanking)
     res = _emit({"AUPRC": average_precision(df["label"].astype(int).to_numpy(), scores)}, None)
     if output and rank0:
         out = df.copy()
