@@ -283,6 +283,30 @@ int    pcad_forward_probs(pcad_handle h, const int32_t* ids, int B, int L, const
                           const int32_t* pos_per_window, const int32_t* cols, float* probs_out, float* logits_out,
                           void* workspace, size_t workspace_bytes, pcad_stream stream);
 
+/* Per-layer hidden states at the evaluated positions: chosen levels of the reference's `hidden_states` tuple
+ * (output_hidden_states=True), only at the rows a caller reads, optionally as the reverse-complement-averaged fp32 embedding.
+ *   layers      HOST int32 [NL], strictly increasing indices into the tuple, 1 <= NL <= n_layer + 1: 0 = the RCPSEmbedding output,
+ *               k = the input of block k, n_layer = hidden_states[-1].  layers == NULL with NL == 0: all n_layer + 1 levels.
+ *   positions   exactly one form, 1 <= P <= PCAD_MAX_POSITIONS: positions HOST int32 [P] shared by every window (each inside
+ *               [0, L), else PCAD_ERR_INVALID), or pos_per_window DEVICE int32 [B, P] (a value outside [0, L) is clamped AND reported
+ *               as PCAD_STATUS_BAD_POSITION).  There is no all-positions form: that is pcad_forward_all_hidden.
+ *   out         DEVICE, 16-byte aligned.  average == 0: model dtype [NL, B, P, 2D], row = [forward strand's row | reverse-complement
+ *               strand's row with channels reversed] - the rows [b, p, :] of pcad_forward_all_hidden's levels.  average != 0: fp32
+ *               [NL, B, P, D] = (float(fwd[c]) + float(rc[c])) * 0.5f in straight channel order: what the reference's
+ *               extract_embeddings forms from the plain row ((e[:D] + flip(e[D:])) / 2 on fp32), bit for bit.
+ * Layer walk.  Only level n_layer requested: pcad_forward's walk for the shared list (norm fold and last-layer shortcut as that call
+ * chooses them; the plain output is bit-equal to its hidden_out) and the full last layer for per-window lists (P == 1:
+ * pcad_forward_at's walk and hidden_out).  Any level below n_layer requested: pcad_forward_all_hidden's walk (no norm fold, no
+ * shortcut), every level gathered right after it is produced: level k is bit-equal to all_hidden[k][b, p, :] (hidden_out[b, p, :] for
+ * k == n_layer) of that call on the same batch under the same options.
+ * pcad_workspace_bytes is the forward's own; nothing is allocated and nothing synchronises.  Token ids outside the vocabulary are
+ * reported through pcad_set_status_buffer as by pcad_forward.
+ * Replaces: model(input_ids=ids, output_hidden_states=True).hidden_states[k][:, p, :] and the strand averaging of
+ *           src/train_XGBoost.py:104-110 (extract_embeddings) at any level k. */
+int    pcad_forward_layers(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P,
+                           const int32_t* pos_per_window, const int32_t* layers, int NL, int average, void* out,
+                           void* workspace, size_t workspace_bytes, pcad_stream stream);
+
 /* ---- measurement: per-kernel-class timing with HIP events on the caller's stream -------------------- */
 enum pcad_kernel_class {
     PCAD_K_NORM = 0, PCAD_K_GEMM_IN, PCAD_K_CONV, PCAD_K_GEMM_X, PCAD_K_SCAN, PCAD_K_GEMM_OUT, PCAD_K_HEAD,
@@ -396,6 +420,15 @@ int pcad_gemm_nt_residual(const void* A, int64_t lda, const void* W, int64_t ldw
  * src/zero_shot_score.py:117, src/train_XGBoost.py:105.) */
 int pcad_gather_rows(const void* src, void* out, int B, int L, int E, const int32_t* positions, int P, int dtype,
                      pcad_stream stream);
+
+/* The row kernel of pcad_forward_layers as one operator.  src: plain rows [2B * L, D] (assembled == 0: strand b row p_q and strand
+ * B + b row L - 1 - p_q are read), or [B, P, 2D] rows already in hidden_states' layout (assembled != 0: pcad_final_head's
+ * hidden_out; the positions only give P).  out: dtype [B, P, 2D] (average == 0) or fp32 [B, P, D] = (fwd + rc) * 0.5f
+ * (average != 0).  positions (HOST int32 [P]) or pos_per_window (DEVICE int32 [B, P]; clamped and reported through `status`,
+ * which may be NULL), exactly one, 1 <= P <= PCAD_MAX_POSITIONS.  D % 8 == 0; src and out 16-byte aligned.
+ * Replaces: hidden_states[k][:, positions, :] (indexing + the flips of RCPSWrapper) and extract_embeddings' strand averaging. */
+int pcad_layer_rows(const void* src, void* out, int B, int L, int D, const int32_t* positions, int P,
+                    const int32_t* pos_per_window, int assembled, int average, int32_t* status, int dtype, pcad_stream stream);
 
 /* The forward's last kernel as one operator: res + h -> norm_f -> RC re-assembly of hidden_states[-1] -> tied RCPS LM head, at
  * the shared positions (HOST int32 [P], P = 0: all L) or one position per window (pos_per_seq, DEVICE int32 [B]; then

@@ -537,10 +537,21 @@ struct ProbsRequest {
     float* logits_out;
 };
 
+// pcad_forward_layers: chosen levels of hidden_states at the evaluated positions (layers.hip) in place of the LM head's outputs
+struct LayersRequest {
+    const int32_t* layers;             // host [NL], strictly increasing levels in [0, n_layer], or nullptr: all n_layer + 1
+    int NL;
+    bool inter;                        // a level below n_layer is requested: the unfolded full walk of pcad_forward_all_hidden
+    const int32_t* pos_per_window;     // device [B, Pw] or nullptr (then the forward's own positions / P apply)
+    int Pw;
+    bool average;
+    void* out;                         // [NL, B, P, 2D] model dtype, or (average) [NL, B, P, D] fp32
+};
+
 static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P,
                         const int32_t* pos_per_seq, void* all_hidden, void* hidden_out, float* logits_out, void* workspace, size_t ws_bytes,
                         pcad_stream stream, const PoolRequest* pool = nullptr, const LossRequest* loss = nullptr,
-                        const ProbsRequest* probs = nullptr) {
+                        const ProbsRequest* probs = nullptr, const LayersRequest* lay = nullptr) {
     if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward: null handle");
     pcad_engine* e = h;
     if (!e->bound) return fail(PCAD_ERR_UNBOUND, "pcad_forward: weights not bound");
@@ -614,7 +625,9 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
     // lo.hi, hi.lo; gemm.hip) with an fp32 result: operand error 2^-17, measured 4e-7 of the logits' range after 32 layers (fp32 MFMA:
     // 1e-6 from summation order alone).
     const bool sp = split_wanted(e) && e->split_packed;
-    bool fold_all = fold_wanted(e) && e->fold_packed && !all_hidden;
+    // pcad_forward_layers with a level below n_layer: hidden_states[i] are the mixer outputs, so the walk is pcad_forward_all_hidden's
+    const bool lay_inter = lay && lay->inter;
+    bool fold_all = fold_wanted(e) && e->fold_packed && !all_hidden && !lay_inter;
     for (int ck = 0; ck < nchunks && fold_all; ++ck) {
         const int Bc = (B - ck * chunk) < chunk ? (B - ck * chunk) : chunk;
         fold_all = gemm_fold_shapes_ok((int64_t)2 * Bc * L, D, E, dt);
@@ -626,6 +639,25 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
     // the reference-order out_proj); outputs are unchanged.
     auto reps = [&](int cls) -> int { return e->rep_class == cls ? e->rep_count : 1; };
     static const bool tab0 = dev_env("PCAD_NO_TAB0") == nullptr;     // layer 0's in_proj as a table look-up (phase_P); PCAD_DEV=1 A/B switch
+    // pcad_forward_layers: level `level` of the tuple (now in c.w.h as plain rows) -> its rows at the evaluated positions, if requested
+    const int layP = lay ? (lay->pos_per_window ? lay->Pw : P) : 0;
+    auto lay_slot = [&](int level) -> int {
+        if (!lay) return -1;
+        if (!lay->layers) return level;
+        for (int i = 0; i < lay->NL; ++i)
+            if (lay->layers[i] == level) return i;
+        return -1;
+    };
+    auto lay_dst = [&](int slot, int b0) -> void* {      // indexed by the chunk's first window, as all_hidden is
+        return (char*)lay->out + ((size_t)slot * B + b0) * layP * (lay->average ? (size_t)D * 4 : (size_t)2 * D * esz);
+    };
+    auto lay_gather = [&](Lane& c, int level) -> int {
+        const int slot = lay_slot(level);
+        if (slot < 0) return PCAD_OK;
+        HIP_TRY(launch_layer_rows(c.w.h, lay_dst(slot, c.b0), c.Bc, L, D, pos, lay->pos_per_window ? lay->pos_per_window + (size_t)c.b0 * layP : nullptr,
+                                  layP, false, 0, 0, lay->average, dt, e->status, cs));
+        return PCAD_OK;
+    };
     auto phase_N = [&](Lane& c, int li) -> int {        // residual add + norm (layer 0: RCPS embedding + norm)
         hipStream_t s = cs;
         const LayerWeights& W = e->layers[li];
@@ -643,6 +675,10 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
             if (all_hidden) {   // hidden_states[0] = RCPSEmbedding output
                 HIP_TRY(launch_embed_only(ids_c, e->emb, e->comp, c.w.h, c.Bc, L, D, dt, s));
                 HIP_TRY(launch_assemble_hidden(c.w.h, (char*)all_hidden + ((size_t)c.b0 * L * 2 * D) * esz, c.Bc, L, D, dt, s));
+            }
+            if (lay_slot(0) >= 0) {
+                HIP_TRY(launch_embed_only(ids_c, e->emb, e->comp, c.w.h, c.Bc, L, D, dt, s));
+                if (int rc = lay_gather(c, 0)) return rc;
             }
             ProfScope ps(e, PCAD_K_NORM, s);
             HIP_TRY(launch_embed_rmsnorm(ids_c, e->emb, e->comp, W.norm_w, c.w.u, c.w.res, c.Bc, L, D, eps, dt, rdt, s, nullptr, 0, sp));
@@ -689,7 +725,7 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
     // them, the right-to-left scan likewise (walk_len steps each), and the tied out_proj runs on the 2B * P gathered rows.  Same
     // arithmetic on the consumed rows (sequential walks, row-independent GEMM): results are bit-identical to the full layer.
     int walk_len = 0;
-    if (e->shortcut && P > 0 && !pos_per_seq && !all_hidden && (int64_t)P * E <= (int64_t)L * D) {
+    if (e->shortcut && P > 0 && !pos_per_seq && !all_hidden && !lay_inter && (int64_t)P * E <= (int64_t)L * D) {
         int pmin = pos.p[0], pmax = pos.p[0];
         for (int i = 1; i < P; ++i) { pmin = pos.p[i] < pmin ? pos.p[i] : pmin; pmax = pos.p[i] > pmax ? pos.p[i] : pmax; }
         const int need = (pmax + 1 > L - pmin) ? pmax + 1 : L - pmin;      // forward strands need row pmax, rc strands row L - 1 - pmin
@@ -792,6 +828,8 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                 char* dst = (char*)all_hidden + ((size_t)(li + 1) * B * L * 2 * D + (size_t)c.b0 * L * 2 * D) * esz;
                 HIP_TRY(launch_assemble_hidden(c.w.h, dst, c.Bc, L, D, dt, s));
             }
+            if (lay && li + 1 < e->nl)
+                if (int rc = lay_gather(c, li + 1)) return rc;
             return PCAD_OK;
         }
         if (last_short) {       // out_proj on the evaluated rows only: gather (-> u, dead since in_proj) and a small GEMM (-> first rows of h)
@@ -820,6 +858,8 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
             char* dst = (char*)all_hidden + ((size_t)(li + 1) * B * L * 2 * D + (size_t)c.b0 * L * 2 * D) * esz;
             HIP_TRY(launch_assemble_hidden(c.w.h, dst, c.Bc, L, D, dt, s));
         }
+        if (lay && li + 1 < e->nl)
+            if (int rc = lay_gather(c, li + 1)) return rc;
         return PCAD_OK;
     };
     auto phase_head = [&](Lane& c) -> int {
@@ -862,6 +902,39 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                                       probs->logits_out ? probs->logits_out + (size_t)c.b0 * Qp * e->V : nullptr, c.Bc, L, D, eps, pos,
                                       probs->pos_per_window ? probs->pos_per_window + (size_t)c.b0 * Qp : nullptr, probs->Pw, dt, rdt, cs,
                                       walk_len > 0, ids + (int64_t)c.b0 * L, e->status, c.fold ? Dp : 0));
+            return PCAD_OK;
+        }
+        if (lay) {
+            // hidden_states[-1]: the final head's assembled rows [Bc, P, 2D] (per-window lists with P > 1: [P, Bc, 2D], one launch per slot
+            // on that slot's column of the list) go to xz, the column copy of the chunk's per-window list behind them - both dead
+            // once the last out_proj has run, so the forward's workspace size is unchanged.  The head runs even when the last
+            // level is not requested: it is what validates the token ids.
+            const int32_t* ppw = lay->pos_per_window ? lay->pos_per_window + (size_t)c.b0 * layP : nullptr;
+            char* rows_tmp = (char*)c.w.xz;
+            const size_t avail = (size_t)((char*)workspace + c.w.bytes - rows_tmp);
+            const size_t slot_bytes = (size_t)c.Bc * 2 * D * esz, rows_bytes = align_up(slot_bytes * layP);
+            const bool columns = ppw && layP > 1;
+            if (rows_bytes + (columns ? align_up((size_t)c.Bc * layP * 4) : 0) > avail)
+                return fail(PCAD_ERR_WORKSPACE, "pcad_forward_layers: the last level's rows (%zu bytes) do not fit the dead buffers (%zu)", rows_bytes, avail);
+            const int slot = lay_slot(e->nl);
+            ProfScope ps(e, PCAD_K_HEAD, cs);
+            if (ppw) {
+                const int32_t* col = ppw;                // P == 1: the list is its own column (pcad_forward_at's launch)
+                if (columns) {
+                    col = (const int32_t*)(rows_tmp + rows_bytes);
+                    HIP_TRY(launch_position_columns(ppw, (int32_t*)(rows_tmp + rows_bytes), c.Bc, layP, cs));
+                }
+                for (int q = 0; q < layP; ++q)
+                    HIP_TRY(launch_final_head(c.w.h, c.w.res, e->normf_w, e->emb, e->emb_f32, e->comp, rows_tmp + slot_bytes * q, nullptr, c.Bc, L, D,
+                                              eps, pos, col + (size_t)q * c.Bc, dt, rdt, cs, false, ids + (int64_t)c.b0 * L, e->status, c.fold ? Dp : 0));
+                if (slot >= 0)
+                    HIP_TRY(launch_layer_rows(rows_tmp, lay_dst(slot, c.b0), c.Bc, L, D, pos, nullptr, layP, true, 1, c.Bc, lay->average, dt, nullptr, cs));
+            } else {
+                HIP_TRY(launch_final_head(c.w.h, c.w.res, e->normf_w, e->emb, e->emb_f32, e->comp, rows_tmp, nullptr, c.Bc, L, D, eps, pos, nullptr, dt,
+                                          rdt, cs, walk_len > 0, ids + (int64_t)c.b0 * L, e->status, c.fold ? Dp : 0));
+                if (slot >= 0)
+                    HIP_TRY(launch_layer_rows(rows_tmp, lay_dst(slot, c.b0), c.Bc, L, D, pos, nullptr, layP, true, layP, 1, lay->average, dt, nullptr, cs));
+            }
             return PCAD_OK;
         }
         void* hout = hidden_out ? (char*)hidden_out + ((size_t)c.b0 * Q * 2 * D) * esz : nullptr;
@@ -940,6 +1013,26 @@ int pcad_forward_probs(pcad_handle h, const int32_t* ids, int B, int L, const in
     // shared positions: pcad_forward's walk (last-layer shortcut included); per-window lists: pcad_forward_at's (the full last layer)
     return forward_impl(h, ids, B, L, pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, nullptr, nullptr, nullptr, nullptr,
                         workspace, workspace_bytes, stream, nullptr, nullptr, &pr);
+}
+
+int pcad_forward_layers(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* positions, int P, const int32_t* pos_per_window,
+                        const int32_t* layers, int NL, int average, void* out, void* workspace, size_t workspace_bytes, pcad_stream stream) {
+    if (!h) return fail(PCAD_ERR_INVALID, "pcad_forward_layers: null handle");
+    if ((positions != nullptr) == (pos_per_window != nullptr))
+        return fail(PCAD_ERR_INVALID, "pcad_forward_layers: exactly one of positions and pos_per_window (the all-positions form is pcad_forward_all_hidden)");
+    if (P < 1 || P > PCAD_MAX_POSITIONS) return fail(PCAD_ERR_INVALID, "pcad_forward_layers: bad positions (P=%d)", P);
+    const int nl = h->nl;
+    if (layers ? (NL < 1 || NL > nl + 1) : NL != 0) return fail(PCAD_ERR_INVALID, "pcad_forward_layers: bad layers (NL=%d, n_layer=%d)", NL, nl);
+    for (int i = 0; i < NL; ++i) {
+        if (layers[i] < 0 || layers[i] > nl) return fail(PCAD_ERR_INVALID, "pcad_forward_layers: level %d outside [0, %d]", layers[i], nl);
+        if (i > 0 && layers[i] <= layers[i - 1]) return fail(PCAD_ERR_INVALID, "pcad_forward_layers: levels must be strictly increasing");
+    }
+    if (!out || ((uintptr_t)out) % 16) return fail(PCAD_ERR_INVALID, "pcad_forward_layers: out must be a 16-byte aligned pointer");
+    const LayersRequest lr{layers, layers ? NL : nl + 1, !layers || layers[0] < nl, pos_per_window, pos_per_window ? P : 0, average != 0, out};
+    // the last level alone: pcad_forward's walk for a shared list (norm fold and last-layer shortcut as that call chooses them), the
+    // full last layer for per-window lists (P == 1: pcad_forward_at's walk); any level below it: pcad_forward_all_hidden's walk
+    return forward_impl(h, ids, B, L, pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, pos_per_window, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, &lr);
 }
 
 int pcad_forward_at(pcad_handle h, const int32_t* ids, int B, int L, const int32_t* pos_per_seq, void* hidden_out,
@@ -1138,6 +1231,23 @@ int pcad_gather_rows(const void* src, void* out, int B, int L, int E, const int3
     if (int rc = positions_arg("pcad_gather_rows", positions, P, L, &pos)) return rc;
     if (B == 0) return PCAD_OK;
     HIP_TRY(launch_gather_rows(src, out, B, L, E, pos, dtype, false, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_layer_rows(const void* src, void* out, int B, int L, int D, const int32_t* positions, int P, const int32_t* pos_per_window,
+                    int assembled, int average, int32_t* status, int dtype, pcad_stream stream) {
+    if (!src || !out) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad dtype");
+    if (B < 0 || L <= 0 || D <= 0 || D % 8) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad B / L / D (D must be a multiple of 8)");
+    if (((uintptr_t)src) % 16 || ((uintptr_t)out) % 16) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: src and out must be 16-byte aligned");
+    if ((positions != nullptr) == (pos_per_window != nullptr)) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: exactly one of positions and pos_per_window");
+    if (P < 1) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad positions (P=%d)", P);
+    Positions pos;
+    if (int rc = positions_arg("pcad_layer_rows", pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, L, &pos)) return rc;
+    if (P > PCAD_MAX_POSITIONS) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad positions (P=%d)", P);
+    if (B == 0) return PCAD_OK;
+    HIP_TRY(launch_layer_rows(src, out, B, L, D, pos, assembled ? nullptr : pos_per_window, P, assembled != 0, P, 1, average != 0, dtype, status,
+                              (hipStream_t)stream));
     return PCAD_OK;
 }
 

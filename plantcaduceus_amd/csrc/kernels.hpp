@@ -78,6 +78,15 @@ hipError_t launch_probs_head(const void* h, const void* res, const float* w, con
                              float* probs_out, float* logits_out, int B, int L, int D, float eps, Positions pos,
                              const int32_t* pos_per_window, int Pw, int dt, int rdt, hipStream_t s, bool h_compact = false,
                              const int32_t* ids = nullptr, int32_t* status = nullptr, int res_frag = 0);
+// layers.hip: one level of hidden_states at the evaluated positions only (pcad.h pcad_layer_rows).  src: plain rows [2B * L, D] (a mixer
+// output h / the RCPS embedding), or - assembled - rows of 2D elements already in the reference's layout, the row of (window b, slot q)
+// at row index b * sb + q * sq (final_head_kernel's hidden_out; positions are not read).  out: model dtype [B, P, 2D] =
+// launch_assemble_hidden's rows (b, p_q), or - average - fp32 [B, P, D] = (fwd + rc) * 0.5 in straight channel order.  Positions: the
+// shared list `pos` (pos.n == P) or pos_per_window (device [B, P]; values outside [0, L) are clamped and set status bit 2).
+hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* pos_per_window, int P,
+                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s);
+// dst [P, B] = the columns of src [B, P] (device int32): slot q's positions of every window as one contiguous list
+hipError_t launch_position_columns(const int32_t* src, int32_t* dst, int B, int P, hipStream_t s);
 // hidden_states[i] (block input = previous mixer output / embedding) assembled in RCPS layout.
 hipError_t launch_assemble_hidden(const void* h, void* out, int B, int L, int D, int dt, hipStream_t s);
 hipError_t launch_embed_only(const int32_t* ids, const void* emb, const int32_t* comp8, void* h, int B, int L,

@@ -1,0 +1,146 @@
+// Per-layer hidden states at the evaluated positions: the rows of one level of the reference's `hidden_states`
+// tuple that a caller reads, gathered from the 2B-strand activation tensor right after the level is produced.
+//
+//   source        plain rows [2B * L, D]: the mixer output h of a layer, or the RCPS embedding (level 0);
+//                 or (assembled) rows [.., 2D] that final_head_kernel already wrote in the reference's layout (the last level)
+//   rows read     (window b, slot q, position p): strand b row p ("fwd") and strand B + b row L - 1 - p ("rc")
+//   plain form    model dtype [B, P, 2D]: [0, D) = fwd, [D, 2D) = rc with channels reversed - assemble_hidden_kernel's row (b, p), bit for bit
+//   averaged form fp32 [B, P, D]: (float(fwd[c]) + float(rc[c])) * 0.5f - one fp32 add and one exact multiply: the value
+//                 embeddings.extract_embeddings forms with torch from the plain row ((e[:D] + flip(e[D:])) / 2 on fp32), bit for bit
+//
+// Positions: a shared by-value list, or a device list per window (pos_per_window [B, P]; a value outside [0, L) is clamped and
+// reported).  One WAVE per (window, slot): it reads both rows itself in 16-byte pieces and stores every output element once in
+// 16-byte pieces - no hand-over between waves, no atomics on data, so a window's rows depend on that window only.
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace pcad {
+
+constexpr int LAYERS_STATUS_BAD_POSITION_BIT = 2;     // = pcad.h PCAD_STATUS_BAD_POSITION
+constexpr int LAYERS_WAVES = 4;                       // (window, slot) items per block
+
+// one 16-byte piece = EPV elements of T, as raw bits (a copy never passes through a float conversion)
+template <typename T> struct Piece;
+template <> struct Piece<float> {
+    static constexpr int EPV = 4;
+    static __device__ __forceinline__ u32x4 reversed(u32x4 v) { return u32x4{v[3], v[2], v[1], v[0]}; }
+    static __device__ __forceinline__ void to_f32(u32x4 v, float (&f)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = __uint_as_float(v[i]);
+    }
+};
+template <> struct Piece<bf16_t> {
+    static constexpr int EPV = 8;
+    static __device__ __forceinline__ u32x4 reversed(u32x4 v) {
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = (v[3 - i] >> 16) | (v[3 - i] << 16);
+        return r;
+    }
+    static __device__ __forceinline__ void to_f32(u32x4 v, float (&f)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { f[2 * i] = bf16lo_to_f32(v[i]); f[2 * i + 1] = bf16hi_to_f32(v[i]); }
+    }
+};
+
+// ASM: src holds assembled rows of 2D elements, row of (b, q) at index b * sb + q * sq; else plain rows [2B * L, D]
+template <typename T, bool AVG, bool ASM>
+__global__ __launch_bounds__(64 * LAYERS_WAVES) void layer_rows_kernel(const T* __restrict__ src, void* __restrict__ out, int B, int L, int D,
+                                                                       Positions pos, const int32_t* __restrict__ pos_per_window, int P,
+                                                                       int64_t sb, int64_t sq, int32_t* __restrict__ status) {
+    constexpr int EPV = Piece<T>::EPV;
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * LAYERS_WAVES + (threadIdx.x >> 6);      // = b * P + q, wave-uniform
+    if (item >= (int64_t)B * P) return;
+    const int b = (int)(item / P), q = (int)(item - (int64_t)b * P);
+    const T *fwd, *rc;
+    if constexpr (ASM) {
+        fwd = src + (b * sb + q * sq) * 2 * D;
+        rc = fwd + D;
+    } else {
+        int p = 0;
+        if (pos_per_window) {
+            const int raw = pos_per_window[item];
+            if (status != nullptr && lane == 0 && (unsigned)raw >= (unsigned)L) atomicOr(status, LAYERS_STATUS_BAD_POSITION_BIT);
+            p = min(max(raw, 0), L - 1);         // clamped: nothing is read out of bounds
+        } else {
+            // uniform select from the by-value array (avoids runtime-indexed kernarg scratch)
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (i == q) p = pos.p[i];
+        }
+        fwd = src + ((int64_t)b * L + p) * D;
+        rc = src + ((int64_t)(B + b) * L + (L - 1 - p)) * D;
+    }
+    const int npiece = D / EPV;
+    if constexpr (!AVG) {
+        T* o = (T*)out + item * 2 * D;
+        for (int c = lane; c < npiece; c += 64) {
+            const u32x4 f = *reinterpret_cast<const u32x4*>(fwd + c * EPV);
+            const u32x4 r = *reinterpret_cast<const u32x4*>(rc + c * EPV);
+            *reinterpret_cast<u32x4*>(o + c * EPV) = f;
+            if constexpr (ASM) *reinterpret_cast<u32x4*>(o + D + c * EPV) = r;        // already channel-reversed
+            else *reinterpret_cast<u32x4*>(o + D + (npiece - 1 - c) * EPV) = Piece<T>::reversed(r);
+        }
+    } else {
+        float* o = (float*)out + item * D;
+        for (int c = lane; c < npiece; c += 64) {
+            const u32x4 f = *reinterpret_cast<const u32x4*>(fwd + c * EPV);
+            // the rc strand's channels c * EPV ..: straight in the plain rows, mirrored (and reversed) in an assembled row
+            u32x4 r = *reinterpret_cast<const u32x4*>(rc + (ASM ? npiece - 1 - c : c) * EPV);
+            if constexpr (ASM) r = Piece<T>::reversed(r);
+            float a[EPV], m[EPV];
+            Piece<T>::to_f32(f, a);
+            Piece<T>::to_f32(r, m);
+#pragma unroll
+            for (int k = 0; k < EPV; k += 4)
+                *reinterpret_cast<f32x4*>(o + c * EPV + k) = f32x4{(a[k] + m[k]) * 0.5f, (a[k + 1] + m[k + 1]) * 0.5f,
+                                                                    (a[k + 2] + m[k + 2]) * 0.5f, (a[k + 3] + m[k + 3]) * 0.5f};
+        }
+    }
+}
+
+template <typename T>
+static hipError_t launch_layer_rows_t(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* ppw, int P,
+                                      bool assembled, int64_t sb, int64_t sq, bool average, int32_t* status, hipStream_t s) {
+    const int64_t items = (int64_t)B * P;
+    const dim3 grid((unsigned)((items + LAYERS_WAVES - 1) / LAYERS_WAVES)), blk(64 * LAYERS_WAVES);
+#define PCAD_LAYER_ROWS(AVG, ASM) \
+    hipLaunchKernelGGL((layer_rows_kernel<T, AVG, ASM>), grid, blk, 0, s, (const T*)src, out, B, L, D, pos, ppw, P, sb, sq, status)
+    if (average) { if (assembled) PCAD_LAYER_ROWS(true, true); else PCAD_LAYER_ROWS(true, false); }
+    else { if (assembled) PCAD_LAYER_ROWS(false, true); else PCAD_LAYER_ROWS(false, false); }
+#undef PCAD_LAYER_ROWS
+    return hipGetLastError();
+}
+
+hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* pos_per_window, int P,
+                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s) {
+    if (D <= 0 || D % 8 || L <= 0 || P < 1 || P > 16) return hipErrorInvalidValue;
+    if (!assembled && !pos_per_window && pos.n != P) return hipErrorInvalidValue;
+    if (!assembled && !pos_per_window)
+        for (int i = 0; i < P; ++i)
+            if (pos.p[i] < 0 || pos.p[i] >= L) return hipErrorInvalidValue;
+    if (((uintptr_t)src) % 16 || ((uintptr_t)out) % 16) return hipErrorInvalidValue;      // 16-byte pieces
+    if (B <= 0) return hipSuccess;
+    if (((int64_t)B * P + LAYERS_WAVES - 1) / LAYERS_WAVES > 0x7fffffff) return hipErrorInvalidValue;
+    if (dt == BF16) return launch_layer_rows_t<bf16_t>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s);
+    if (dt == F32) return launch_layer_rows_t<float>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s);
+    return hipErrorInvalidValue;
+}
+
+// dst [P, B] = transpose of src [B, P]: one contiguous per-window position list per slot, the form final_head_kernel reads
+__global__ __launch_bounds__(256) void position_columns_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst, int B, int P) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * P) return;
+    const int b = (int)(i / P), q = (int)(i - (int64_t)b * P);
+    dst[(int64_t)q * B + b] = src[i];
+}
+
+hipError_t launch_position_columns(const int32_t* src, int32_t* dst, int B, int P, hipStream_t s) {
+    if (B <= 0 || P <= 0) return hipSuccess;
+    const int64_t n = (int64_t)B * P;
+    hipLaunchKernelGGL(position_columns_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, B, P);
+    return hipGetLastError();
+}
+
+}  // namespace pcad

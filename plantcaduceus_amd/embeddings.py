@@ -32,8 +32,44 @@ def load_data(filepath):
     return data["sequences"].tolist(), data["label"].tolist()
 
 
+def resolve_layers(layer, n_layer: int):
+    """`layer` (an int or a list of ints; negative counts from the end, as indexing the n_layer + 1 entries of `hidden_states`
+    would) -> the levels as non-negative ints, in the caller's order."""
+    out = []
+    for k in ([layer] if isinstance(layer, (int, np.integer)) else list(layer)):
+        k = int(k)
+        if not -(n_layer + 1) <= k <= n_layer:
+            raise IndexError(f"layer {k} is outside the {n_layer + 1} levels of hidden_states")
+        out.append(k + n_layer + 1 if k < 0 else k)
+    if not out:
+        raise ValueError("layer: an empty list")
+    return out
+
+
+def with_layer(name: str, layer) -> str:
+    """File name of a cache / result of `-layer K` runs: `_layer<K>` before the extension (layer None: the name as it is), so that
+    caches of different layers never collide with each other or with the default run's."""
+    if layer is None:
+        return name
+    stem, ext = os.path.splitext(name)
+    return f"{stem}_layer{int(layer)}{ext}"
+
+
+def layer_arg(value: str) -> int:
+    """argparse type of `-layer K`: a level of `hidden_states`, 0 (the embedding output) .. n_layer (the last hidden state)."""
+    k = int(value)
+    if k < 0:
+        raise ValueError("-layer counts from 0 (the embedding output); the last level is n_layer")
+    return k
+
+
 def extract_embeddings(model, sequences, device, tokenIdx: int, tokenizer=None, batch_size: int = 128,
-                       batch_explicit: bool = False) -> np.ndarray:
+                       batch_explicit: bool = False, layer=None) -> np.ndarray:
+    """layer=None: the reference's embedding, from hidden_states[-1].  layer=K / [K, ...] (negative: from the end): the same
+    strand-averaged fp32 embedding of level K of `hidden_states` -> [N, d_model] / [N, NL, d_model], formed on the device by
+    `model.hidden_states_at(..., average=True)` (models with `supports_layer_hidden`)."""
+    if layer is not None:
+        return _extract_layer_embeddings(model, sequences, device, tokenIdx, tokenizer, batch_size, batch_explicit, layer)
     logging.info("Extracting embeddings")
     n_total = len(sequences)
     rank, ws = sharding.world()
@@ -61,6 +97,35 @@ def extract_embeddings(model, sequences, device, tokenIdx: int, tokenizer=None, 
     out = emb.cpu().numpy()
     check_model_inputs(model)
     return out
+
+
+def _extract_layer_embeddings(model, sequences, device, tokenIdx, tokenizer, batch_size, batch_explicit, layer) -> np.ndarray:
+    if not getattr(model, "supports_layer_hidden", False):
+        raise NotImplementedError("layer=: the model has no hidden_states_at (supports_layer_hidden); intermediate levels of another "
+                                  "model are read from model(..., output_hidden_states=True).hidden_states")
+    n_layer = int(model.config.n_layer)
+    levels = resolve_layers(layer, n_layer)
+    single = isinstance(layer, (int, np.integer))
+    order = sorted(set(levels))                     # the engine takes strictly increasing levels; the caller's order is restored below
+    pick = [order.index(k) for k in levels]
+    logging.info(f"Extracting embeddings of hidden_states level(s) {levels}")
+    n_total = len(sequences)
+    rank, ws = sharding.world()
+    start, stop, per = sharding.shard_bounds(n_total, rank, ws)
+    if n_total:
+        batch_size = effective_batch(model, batch_size, _window_len(sequences), batch_explicit)
+    model.eval()
+    d = int(model.config.d_model)
+    outs = []
+    with torch.inference_mode():
+        for cur in iter_device_batches(sequences, start, stop, per if ws > 1 else 0, batch_size, tokenizer, None, device):
+            e = model.hidden_states_at(cur, layers=order, positions=[tokenIdx], average=True)          # fp32 [NLu, b, 1, D]
+            outs.append(e[:, :, 0, :].permute(1, 0, 2)[:, pick, :].reshape(e.shape[1], len(pick) * d))
+        emb = torch.cat(outs, dim=0) if outs else torch.empty((0, len(pick) * d), dtype=torch.float32, device=device)
+        emb = sharding.all_gather_rows(emb, n_total)     # one gather of the rows flattened to [N, NL * D]
+    out = emb.cpu().numpy()
+    check_model_inputs(model)
+    return out if single else out.reshape(n_total, len(pick), d)
 
 
 def save_embedding_cache(path: str, compresslevel: int = 1, **arrays):

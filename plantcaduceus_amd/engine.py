@@ -98,12 +98,46 @@ SIGNATURES = {
     "pcad_probs_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pcad_forward_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                      C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_layer_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                  C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 # include/pcad.h pcad_pooling (pooling_strategy of CaduceusForSequenceClassification)
 POOLING = {"mean": 0, "max": 1, "first": 2, "last": 3}
 MAX_LABELS = 256
 MAX_POSITIONS = 16      # include/pcad.h PCAD_MAX_POSITIONS
+
+
+
+def check_layer_request(layers, n_layer: int, positions, positions_per_window, batch: Optional[int] = None):
+    """The host-side argument rules of `Engine.forward_layers` / `hidden_states_at` (include/pcad.h pcad_forward_layers), raised as
+    ValueError before anything is launched: layers None or strictly increasing indices inside [0, n_layer]; exactly one position
+    form; 1..MAX_POSITIONS positions.  -> (levels list or None, P)."""
+    lv = None
+    if layers is not None:
+        lv = [int(k) for k in layers]
+        if not 1 <= len(lv) <= n_layer + 1:
+            raise ValueError(f"layers must name 1..{n_layer + 1} levels, got {len(lv)}")
+        if any(k < 0 or k > n_layer for k in lv):
+            raise ValueError(f"layers must lie inside [0, {n_layer}] (0: the embedding output, {n_layer}: hidden_states[-1]), got {lv}")
+        if any(b <= a for a, b in zip(lv, lv[1:])):
+            raise ValueError(f"layers must be strictly increasing, got {lv}")
+    if (positions is None) == (positions_per_window is None):
+        raise ValueError("exactly one of positions and positions_per_window (all positions: output_hidden_states with "
+                         "config.materialize_all_hidden_states)")
+    if positions_per_window is not None:
+        ppw = positions_per_window
+        if (not torch.is_tensor(ppw) or ppw.is_floating_point() or ppw.dim() != 2 or (batch is not None and ppw.shape[0] != batch)
+                or not 1 <= ppw.shape[1] <= MAX_POSITIONS):
+            raise ValueError(f"positions_per_window must be an integer tensor [B, 1..{MAX_POSITIONS}]")
+        return lv, int(ppw.shape[1])
+    P = len(positions)
+    if not 1 <= P <= MAX_POSITIONS:
+        raise ValueError(f"positions must name 1..{MAX_POSITIONS} positions, got {P}")
+    return lv, P
+
 
 _lib = None
 
@@ -422,6 +456,51 @@ class Engine:
                 self._status_host.copy_(self._status, non_blocking=True)
                 self._status_event.record()
         return (probs, logits) if want_logits else probs
+
+    def forward_layers(self, input_ids: torch.Tensor, layers=None, positions=None, positions_per_window: Optional[torch.Tensor] = None,
+                       average: bool = False):
+        """Hidden states of chosen levels at the evaluated positions (`pcad_forward_layers`): ids [B, L] on this device ->
+        [NL, B, P, 2D] in the model dtype, or - average - the reverse-complement-averaged fp32 embedding [NL, B, P, D].
+        layers: None (all n_layer + 1 levels of the reference's `hidden_states` tuple) or strictly increasing indices into it (0: the
+        embedding output, n_layer: hidden_states[-1]).  Exactly one of positions (1..16 positions shared by every window) and
+        positions_per_window (an integer tensor [B, 1..16] on this device; a value outside [0, L) is clamped and reported like a bad
+        token id, `check_status`).  Only the last level asked for: `forward`'s own walk; any level below it: the unfolded walk of
+        `forward(all_hidden=True)`, whose levels the rows are bit-equal to.  Chunking, workspace and asynchronous input validation
+        are those of `forward`."""
+        _require_gpu(input_ids, "input_ids")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        if input_ids.device != self.device:
+            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        lv, P = check_layer_request(layers, self.config.n_layer, positions, positions_per_window, int(input_ids.shape[0]))
+        self._poll_status()
+        ids = input_ids.to(torch.int32).contiguous()
+        B, L = ids.shape
+        ppw = None
+        if positions_per_window is not None:
+            if positions_per_window.device != self.device:
+                raise ValueError("positions_per_window must be on the engine's device")
+            # int64 positions are clamped before they are narrowed, so that a huge value cannot alias a valid one
+            ppw = positions_per_window.clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+        else:
+            positions = [int(p) for p in positions]
+        D = self.config.d_model
+        NL = len(lv) if lv is not None else self.config.n_layer + 1
+        with torch.cuda.device(self.device):
+            out = torch.empty((NL, B, P, D if average else 2 * D), dtype=torch.float32 if average else self.dtype, device=self.device)
+            if B == 0:
+                return out
+            ws, ws_bytes = self._workspace(B, L)
+            pos_arr = (C.c_int32 * P)(*positions) if ppw is None else None
+            lay_arr = (C.c_int32 * NL)(*lv) if lv is not None else None
+            try:
+                _check(self.lib.pcad_forward_layers(self._h, ids.data_ptr(), B, L, pos_arr, P, ppw.data_ptr() if ppw is not None else None,
+                                                    lay_arr, NL if lv is not None else 0, int(bool(average)), out.data_ptr(), ws, ws_bytes,
+                                                    _stream_ptr()), "pcad_forward_layers")
+            finally:
+                self._status_host.copy_(self._status, non_blocking=True)
+                self._status_event.record()
+        return out
 
     # -- asynchronous input validation (include/pcad.h pcad_set_status_buffer) ----------------------------------------
     def _raise_status(self, bits: int):

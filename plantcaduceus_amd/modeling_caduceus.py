@@ -256,6 +256,8 @@ class CaduceusPreTrainedModel(PreTrainedModel):
 class Caduceus(CaduceusPreTrainedModel):
     """`AutoModel` class: backbone only; `.last_hidden_state` is [B, L, 2*d_model]."""
 
+    supports_layer_hidden = True     # hidden_states_at(...) returns chosen levels of hidden_states at the evaluated positions
+
     def __init__(self, config: CaduceusConfig, **kwargs):
         super().__init__(config)
         self.backbone = _MixerModel(config)
@@ -272,6 +274,19 @@ class Caduceus(CaduceusPreTrainedModel):
 
     def tie_weights(self, *a, **k):
         pass
+
+    def hidden_states_at(self, input_ids, layers: Optional[Sequence[int]] = None, positions: Optional[Sequence[int]] = None,
+                         positions_per_window: Optional[torch.Tensor] = None, average: bool = False):
+        """Chosen levels of `hidden_states` at the evaluated positions only (non-HF; `supports_layer_hidden`; csrc/layers.hip, DESIGN.md
+        §4i): `torch.stack([self(input_ids, output_hidden_states=True).hidden_states[k][:, positions, :] for k in layers])`,
+        [NL, B, P, 2*d_model] in the model dtype, without materialising any [B, L, 2*d_model] level.  layers: None (all n_layer + 1
+        levels) or strictly increasing indices into the tuple (0: the embedding output, n_layer: hidden_states[-1]).  Exactly one of
+        positions (up to 16, shared by every window) and positions_per_window (integer tensor [B, P], P <= 16, on the model's
+        device; a value outside the window is reported by `check_status()`).  average=True: the reverse-complement-averaged fp32
+        embedding [NL, B, P, d_model] that the reference's `extract_embeddings` forms from such a row
+        (`(e[:D] + flip(e[D:])) / 2` on fp32), bit for bit."""
+        return self._engine().forward_layers(input_ids, layers=layers, positions=positions, positions_per_window=positions_per_window,
+                                             average=bool(average))
 
     def forward(self, input_ids=None, inputs_embeds=None, output_hidden_states=None, return_dict=None,
                 positions: Optional[Sequence[int]] = None, **kwargs):
@@ -310,12 +325,17 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
     read), `return_token_nll=True` (attach `token_nll` fp32 [B, L], 0 at ignored positions) and `return_window_sums=True`
     (attach `window_sums` fp32 [B, 4]: sum w nll, sum w, labelled, arg-max hits per window).  There is no backward pass.
 
+    `hidden_states_at(input_ids, layers, positions=... | positions_per_window=..., average=False)` (non-HF;
+    `supports_layer_hidden`) returns chosen levels of the `hidden_states` tuple at the evaluated positions only - or their
+    reverse-complement-averaged fp32 embeddings - without materialising a [B, L, 2*d_model] level (csrc/layers.hip).
+
     `nucleotide_probs(input_ids, cols, ...)` (non-HF; `supports_nucleotide_probs`) returns `softmax(logits[..., cols])` over four
     vocabulary columns, formed on the device by the engine's probability head (csrc/probs.hip) - at every position,
     at a shared list of positions, or at a list of positions per window.
     """
 
     supports_nucleotide_probs = True     # nucleotide_probs(...) evaluates the four-way probabilities on the device
+    supports_layer_hidden = True         # hidden_states_at(...) returns chosen levels of hidden_states at the evaluated positions
 
     def __init__(self, config: CaduceusConfig, **kwargs):
         super().__init__(config)
@@ -343,6 +363,13 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
         to `forward`'s)."""
         return self._engine().forward_probs(input_ids, cols, positions=positions, positions_per_window=positions_per_window,
                                             want_logits=bool(return_logits))
+
+    def hidden_states_at(self, input_ids, layers: Optional[Sequence[int]] = None, positions: Optional[Sequence[int]] = None,
+                         positions_per_window: Optional[torch.Tensor] = None, average: bool = False):
+        """`Caduceus.hidden_states_at`: chosen levels of `hidden_states` at the evaluated positions only, [NL, B, P, 2*d_model], or -
+        average=True - the reverse-complement-averaged fp32 embedding [NL, B, P, d_model] (csrc/layers.hip)."""
+        return self.caduceus.hidden_states_at(input_ids, layers=layers, positions=positions, positions_per_window=positions_per_window,
+                                              average=average)
 
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, output_hidden_states=None,
                 return_dict=None, positions: Optional[Sequence[int]] = None, loss_weights=None, ignore_index: int = -100,

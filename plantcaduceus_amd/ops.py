@@ -436,3 +436,25 @@ def probs_head(h, res, norm_weight, emb, complement, cols, B: int, L: int, eps: 
                                    ids.data_ptr() if ids is not None else None, status.data_ptr() if status is not None else None,
                                    _dt(hf), _DT[rf.dtype], int(bool(res_fragment)), _stream_ptr()), "pcad_probs_head")
     return pr, lg
+
+
+def layer_rows(src, B: int, L: int, positions=None, positions_per_window=None, assembled: bool = False, average: bool = False,
+               status=None):
+    """One level of hidden_states at the evaluated positions (include/pcad.h pcad_layer_rows).  src [2B*L, D] plain rows (a mixer
+    output / the RCPS embedding), or - assembled - [B, P, 2D] rows already in hidden_states' layout; positions: a shared list, or
+    positions_per_window: integer tensor [B, P] on src's device (exactly one).  -> [B, P, 2D] in src's dtype, or - average - the
+    strand-averaged fp32 [B, P, D]."""
+    import ctypes as C
+    _require_gpu(src, "src")
+    lib = load_library()
+    D = src.shape[-1] // 2 if assembled else src.shape[-1]
+    ppw = positions_per_window.to(torch.int32).contiguous() if positions_per_window is not None else None
+    P = int(ppw.shape[1]) if ppw is not None else len(positions)
+    srcf = src.contiguous()
+    out = torch.empty((B, P, D if average else 2 * D), dtype=torch.float32 if average else src.dtype, device=src.device)
+    arr = (C.c_int32 * max(P, 1))(*[int(p) for p in positions]) if positions is not None else None
+    with torch.cuda.device(src.device):
+        _check(lib.pcad_layer_rows(srcf.data_ptr(), out.data_ptr(), B, L, D, arr, P, ppw.data_ptr() if ppw is not None else None,
+                                   int(bool(assembled)), int(bool(average)), status.data_ptr() if status is not None else None,
+                                   _dt(srcf), _stream_ptr()), "pcad_layer_rows")
+    return out

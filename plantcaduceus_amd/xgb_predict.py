@@ -133,6 +133,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("-tokenIdx", type=int, default=255, help="The index of the nucleotide")
     p.add_argument("-save_memory", action="store_true", help="Flag to save memory, it only works for testing")
     p.add_argument("-chunk_size", type=int, default=100000, help="The chunk size for testing, with -save_memory")
+    from .embeddings import layer_arg
+    p.add_argument("-layer", type=layer_arg, default=None,
+                   help="Embed from level K of hidden_states (0: the embedding output .. n_layer) instead of the last hidden state; "
+                        "cache and result files then carry a _layer<K> suffix")
     args = p.parse_args(argv)
     args.batchExplicit = args.batchSize is not None
     if args.batchSize is None:
@@ -143,7 +147,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
 def main(argv: Optional[Sequence[str]] = None):
     import pandas as pd
     from . import sharding
-    from .embeddings import extract_embeddings, load_data
+    from .embeddings import extract_embeddings, load_data, with_layer
     from .zero_shot import load_model_and_tokenizer
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s", datefmt="%Y-%m-%d %H:%M:%S")
     args = parse_args(argv)
@@ -167,7 +171,7 @@ def main(argv: Optional[Sequence[str]] = None):
                 return None
             logging.info(f"Found pre-computed embeddings, loading from file {cache}")
             return np.load(cache)["test"]
-        emb = extract_embeddings(model, seqs, args.device, args.tokenIdx, tokenizer, args.batchSize, args.batchExplicit)
+        emb = extract_embeddings(model, seqs, args.device, args.tokenIdx, tokenizer, args.batchSize, args.batchExplicit, layer=args.layer)
         if rank == 0:
             pending.append(writer.submit(save_embedding_cache, cache, test=emb))
         return emb
@@ -176,12 +180,12 @@ def main(argv: Optional[Sequence[str]] = None):
         if args.save_memory:
             preds = []
             for i in range(0, len(test_sequences), args.chunk_size):
-                emb = embeddings_for(test_sequences[i:i + args.chunk_size], os.path.join(args.output, f"{prefix}_chunk_{i}_embeddings.npz"))
+                emb = embeddings_for(test_sequences[i:i + args.chunk_size], os.path.join(args.output, with_layer(f"{prefix}_chunk_{i}_embeddings.npz", args.layer)))
                 if rank == 0:                                # the classifier step is host work on rank 0 (the only writer below)
                     preds.append(infer_xgboost_model(clf, emb))
             predictions = np.concatenate(preds, axis=0) if preds else np.zeros(0, dtype=np.float32)
         else:
-            emb = embeddings_for(test_sequences, os.path.join(args.output, prefix + "_embeddings.npz"))
+            emb = embeddings_for(test_sequences, os.path.join(args.output, with_layer(prefix + "_embeddings.npz", args.layer)))
             predictions = infer_xgboost_model(clf, emb) if rank == 0 else None
         # every rank leaves the process group after the last all-gather (rank 0's table writing below is host work; see
         # zero_shot.main)
@@ -191,9 +195,9 @@ def main(argv: Optional[Sequence[str]] = None):
     finally:
         writer.shutdown(wait=True)
     if rank == 0:
-        pd.DataFrame({"label": test_labels, "prediction": predictions}).to_csv(
-            os.path.join(args.output, f"{prefix}_predictions.tsv"), sep="\t", index=False)
-        logging.info(f"Saved predictions to {os.path.join(args.output, f'{prefix}_predictions.tsv')}")
+        table = os.path.join(args.output, with_layer(f"{prefix}_predictions.tsv", args.layer))
+        pd.DataFrame({"label": test_labels, "prediction": predictions}).to_csv(table, sep="\t", index=False)
+        logging.info(f"Saved predictions to {table}")
 
 
 if __name__ == "__main__":

@@ -47,6 +47,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("-save_memory", action="store_true", help="Flag to save memory, it only works for testing")
     p.add_argument("-chunk_size", type=int, default=100000, help="The chunk size for testing, with -save_memory")
     p.add_argument("-seed", type=int, default=42, help="The random seed to train XGBoost model")
+    from .embeddings import layer_arg
+    p.add_argument("-layer", type=layer_arg, default=None,
+                   help="Embed from level K of hidden_states (0: the embedding output .. n_layer) instead of the last hidden state; "
+                        "cache and result files then carry a _layer<K> suffix")
     args = p.parse_args(argv)
     args.batchExplicit = args.batchSize is not None
     if args.batchSize is None:
@@ -120,7 +124,7 @@ def write_metrics(predictions, labels, output_dir: str, prefix: str, random_stat
 
 def main(argv: Optional[Sequence[str]] = None):
     from . import sharding
-    from .embeddings import extract_embeddings, load_data, save_embedding_cache
+    from .embeddings import extract_embeddings, load_data, save_embedding_cache, with_layer
     from .zero_shot import load_model_and_tokenizer
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s", datefmt="%Y-%m-%d %H:%M:%S")
     args = parse_args(argv)
@@ -129,7 +133,7 @@ def main(argv: Optional[Sequence[str]] = None):
         return
     args.device = sharding.init_from_env(args.device)
     os.makedirs(args.output, exist_ok=True)
-    out = lambda name: os.path.join(args.output, name)                                   # noqa: E731
+    out = lambda name: os.path.join(args.output, with_layer(name, args.layer))           # noqa: E731
     model_json = out(f"seed_{args.seed}_XGBoost.json")
     rank, _ = sharding.world()
     if args.test_only:
@@ -152,7 +156,7 @@ def main(argv: Optional[Sequence[str]] = None):
     model, tokenizer = load_model_and_tokenizer(args.model, args.device)
 
     def embed(seqs):
-        return extract_embeddings(model, seqs, args.device, args.tokenIdx, tokenizer, args.batchSize, args.batchExplicit)
+        return extract_embeddings(model, seqs, args.device, args.tokenIdx, tokenizer, args.batchSize, args.batchExplicit, layer=args.layer)
 
     # ---- every forward first (collectives: all ranks), host-only work afterwards (rank 0) --------------------------------
     train_labels = valid_labels = train_emb = valid_emb = None
@@ -207,13 +211,13 @@ def main(argv: Optional[Sequence[str]] = None):
         xgb_model.save_model(model_json)
         valid_predictions = infer_xgboost_model(xgb_model, valid_emb)
         np.savez_compressed(out(f"seed_{args.seed}_valid_predictions.npz"), predictions=valid_predictions)
-        write_metrics(valid_predictions, valid_labels, args.output, os.path.basename(args.valid).split(".")[0], args.seed)
+        write_metrics(valid_predictions, valid_labels, args.output, with_layer(os.path.basename(args.valid).split(".")[0], args.layer), args.seed)
         clf = XGBJsonClassifier().load_model(model_json)          # the test tables go through the saved file, as in the reference (:218-220)
     if args.test:
         preds = [infer_xgboost_model(clf, np.load(c)["test"] if isinstance(c, str) else c) for c in test_chunks]
         predictions = np.concatenate(preds, axis=0) if preds else np.zeros(0, dtype=np.float32)
         np.savez_compressed(out(f"seed_{args.seed}_{prefix}_predictions.npz"), predictions=predictions)
-        roc_auc, prauc = write_metrics(predictions, test_labels, args.output, prefix, args.seed)
+        roc_auc, prauc = write_metrics(predictions, test_labels, args.output, with_layer(prefix, args.layer), args.seed)
         logging.info(f"{prefix}: ROC AUC {roc_auc:.4f}, PRAUC {prauc:.4f}")
 
 
