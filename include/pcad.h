@@ -49,7 +49,10 @@ enum pcad_status {
 
 enum pcad_dtype { PCAD_F32 = 0, PCAD_BF16 = 1 };
 
-/* Model geometry (HF config.json of the snapshot; replaces CaduceusConfig -> Mamba(**ssm_cfg)). */
+/* Model geometry (HF config.json of the snapshot; replaces CaduceusConfig -> Mamba(**ssm_cfg)).
+ * pcad_create accepts d_model a multiple of 64 up to 2048, n_layer >= 1, expand >= 1, dt_rank 1 .. 256, both dtypes and
+ * residual_in_fp32 0 or 1 (read on the bf16 model only; a bf16 residual stream is never norm-folded); anything else is
+ * PCAD_ERR_INVALID with a message that names the field and its value. */
 typedef struct pcad_config {
     int32_t d_model;            /* D */
     int32_t n_layer;

@@ -281,8 +281,9 @@ int pcad_create(const pcad_config* cfg, pcad_handle* out) {
     if (cfg->vocab != 8) return fail(PCAD_ERR_INVALID, "padded vocab=%d unsupported (8 only)", cfg->vocab);
     if (cfg->d_model <= 0 || cfg->d_model % 64 || cfg->d_model > 2048)
         return fail(PCAD_ERR_INVALID, "d_model=%d must be a multiple of 64, <= 2048", cfg->d_model);
-    if (cfg->expand < 1 || cfg->n_layer < 1 || cfg->dt_rank < 1 || cfg->dt_rank > 256)
-        return fail(PCAD_ERR_INVALID, "bad expand/n_layer/dt_rank");
+    if (cfg->expand < 1) return fail(PCAD_ERR_INVALID, "expand=%d must be >= 1", cfg->expand);
+    if (cfg->n_layer < 1) return fail(PCAD_ERR_INVALID, "n_layer=%d must be >= 1", cfg->n_layer);
+    if (cfg->dt_rank < 1 || cfg->dt_rank > 256) return fail(PCAD_ERR_INVALID, "dt_rank=%d must be in 1 .. 256", cfg->dt_rank);
     if (cfg->dtype != PCAD_F32 && cfg->dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "bad dtype %d", cfg->dtype);
     for (int i = 0; i < 8; ++i)
         if (cfg->complement[i] < 0 || cfg->complement[i] > 7) return fail(PCAD_ERR_INVALID, "bad complement map");

@@ -96,10 +96,10 @@ def chunk_for(B, L, E, bf16, chunk_seqs=0):
     return _cdiv(B, n)
 
 
-def predict(D, dt_rank, bf16, B, L, chunk_seqs=0, scan_segments_on=True):
+def predict(D, dt_rank, bf16, B, L, chunk_seqs=0, scan_segments_on=True, expand=2):
     """The forms a pcad_forward call of B windows of L positions runs, and the scratch bytes they carve:
     dict(G, seg_blocks, pair, ks, chunk, scratch)."""
-    E = 2 * D
+    E = expand * D
     Rp = padded_dt_rank(dt_rank)
     convx = Rp in (64, 96)                     # the fused conv + x_proj kernel (every width here has the blocked layouts)
     S, Sc = 2 * B, 2 * chunk_for(B, L, E, bf16, chunk_seqs)
@@ -116,8 +116,8 @@ def predict(D, dt_rank, bf16, B, L, chunk_seqs=0, scan_segments_on=True):
     return dict(G=G, seg_blocks=sb, pair=pair, ks=ks, chunk=Sc // 2, scratch=scratch)
 
 
-def _handle(lib, D, n_layer, dt_rank, bf16, opts):
-    c = engine.PcadConfig(d_model=D, n_layer=n_layer, d_state=16, d_conv=4, expand=2, dt_rank=dt_rank, vocab=8, eps=1e-5,
+def _handle(lib, D, n_layer, dt_rank, bf16, opts, expand=2):
+    c = engine.PcadConfig(d_model=D, n_layer=n_layer, d_state=16, d_conv=4, expand=expand, dt_rank=dt_rank, vocab=8, eps=1e-5,
                           dtype=1 if bf16 else 0, residual_in_fp32=1, complement=(C.c_int32 * 8)(0, 1, 2, 6, 5, 4, 3, 7))
     h = C.c_void_p()
     assert lib.pcad_create(C.byref(c), C.byref(h)) == 0, lib.pcad_last_error()
@@ -130,10 +130,10 @@ class Probe:
     """Two handles of one geometry and option set, the second with "scan_segments" 0: scratch(B, L) is the library's own
     form scratch for a call of B windows of L positions."""
 
-    def __init__(self, lib, D, dt_rank, bf16, n_layer=2, **opts):
-        self.lib, self.D, self.dt_rank, self.bf16, self.opts = lib, D, dt_rank, bf16, dict(opts)
-        self.on = _handle(lib, D, n_layer, dt_rank, bf16, opts)
-        self.off = _handle(lib, D, n_layer, dt_rank, bf16, dict(opts, scan_segments=0))
+    def __init__(self, lib, D, dt_rank, bf16, n_layer=2, expand=2, **opts):
+        self.lib, self.D, self.dt_rank, self.bf16, self.expand, self.opts = lib, D, dt_rank, bf16, expand, dict(opts)
+        self.on = _handle(lib, D, n_layer, dt_rank, bf16, opts, expand)
+        self.off = _handle(lib, D, n_layer, dt_rank, bf16, dict(opts, scan_segments=0), expand)
 
     def scratch(self, B, L):
         a, b = self.lib.pcad_workspace_bytes(self.on, B, L), self.lib.pcad_workspace_bytes(self.off, B, L)
@@ -142,7 +142,7 @@ class Probe:
 
     def predict(self, B, L):
         return predict(self.D, self.dt_rank, self.bf16, B, L, chunk_seqs=int(self.opts.get("chunk_seqs", 0)),
-                       scan_segments_on=bool(self.opts.get("scan_segments", 1)))
+                       scan_segments_on=bool(self.opts.get("scan_segments", 1)), expand=self.expand)
 
     def close(self):
         self.lib.pcad_destroy(self.on)
@@ -150,10 +150,10 @@ class Probe:
 
 
 def engaged_forms(lib, cfg, B, L, dtype=torch.float32, **opts):
-    """The forms a call of B windows of L positions runs on a model of `cfg` (d_model, n_layer, dt_rank) in `dtype` under the
+    """The forms a call of B windows of L positions runs on a model of `cfg` (d_model, n_layer, dt_rank, expand) in `dtype` under the
     engine options `opts`, as predicted here - after asserting that the library's scratch bytes equal the prediction.
     -> dict(G, seg_blocks, pair, ks, chunk, scratch)."""
-    p = Probe(lib, cfg.d_model, cfg.dt_rank, dtype == torch.bfloat16, n_layer=cfg.n_layer, **opts)
+    p = Probe(lib, cfg.d_model, cfg.dt_rank, dtype == torch.bfloat16, n_layer=cfg.n_layer, expand=cfg.expand, **opts)
     try:
         want = p.predict(B, L)
         got = p.scratch(B, L)

@@ -69,13 +69,35 @@ def test_causal_conv1d_fp32(ops, L):
     assert relerr(yr.transpose(1, 2), ref_rev) < 1e-5
 
 
+@pytest.mark.parametrize("E", [128, 384])
+@pytest.mark.parametrize("L", [5, 77])
+def test_causal_conv1d_bf16(ops, L, E):
+    """the unfused conv kernel (conv.hip) in bf16 - what the engine's dt_rank > 96 walk runs - against the oracle rounding its
+    output to bf16: one bf16 ulp of slack on a bf16 output, both directions; L = 77 ragged, E = 384 three 128-channel groups."""
+    g = torch.Generator().manual_seed(L + E)
+    Bsz = 3
+    x = O.round_bf16(torch.randn(Bsz, E, L, generator=g))
+    w, w2 = (torch.randn(E, 4, generator=g) * 0.5 for _ in range(2))
+    b, b2 = (torch.randn(E, generator=g) * 0.5 for _ in range(2))
+    ref = O.causal_conv1d_fn(x, w, b, activation="silu", rnd=O.round_bf16)
+    ref_rev = O.causal_conv1d_fn(x.flip(-1), w2, b2, activation="silu", rnd=O.round_bf16).flip(-1)
+    out = ops.causal_conv1d_fn(x.bfloat16().to(DEV), w.to(DEV), b.to(DEV), activation="silu")
+    assert out.dtype == torch.bfloat16 and relerr(out, ref) < 2 ** -7
+    yf, yr = ops.causal_conv1d_bidir(x.bfloat16().transpose(1, 2).contiguous().to(DEV), w.to(DEV), b.to(DEV), w2.to(DEV), b2.to(DEV))
+    assert yf.dtype == torch.bfloat16
+    assert relerr(yf.transpose(1, 2), ref) < 2 ** -7
+    assert relerr(yr.transpose(1, 2), ref_rev) < 2 ** -7
+
+
 @pytest.mark.parametrize("S,L,E,R,dtype", [(3, 24, 128, 8, torch.float32), (2, 512, 768, 24, torch.float32),
                                            (2, 203, 256, 16, torch.float32), (1, 1, 128, 8, torch.float32),
                                            (2, 5, 128, 8, torch.float32), (4, 512, 2048, 64, torch.bfloat16),
                                            (3, 77, 768, 24, torch.bfloat16), (2, 133, 1536, 48, torch.float32),
                                            # dt_rank 65..96 (PlantCAD2 Large: d_inner 3072, dt_rank 96): the 8-fragment variant, one Wx slab
                                            (2, 512, 3072, 96, torch.bfloat16), (3, 200, 512, 80, torch.float32),
-                                           (2, 77, 1024, 96, torch.bfloat16), (1, 384, 3072, 96, torch.float32), (2, 5, 256, 65, torch.float32)])
+                                           (2, 77, 1024, 96, torch.bfloat16), (1, 384, 3072, 96, torch.float32), (2, 5, 256, 65, torch.float32),
+                                           # E = 64 (expand 1 at d_model 64): the channel walk is a single K-tile in bf16, two in fp32
+                                           (3, 64, 64, 4, torch.bfloat16), (2, 45, 64, 4, torch.float32)])
 def test_conv_xproj_fused(ops, S, L, E, R, dtype):
     """pcad_conv_xproj_bidir — the kernel the engine actually runs for conv1d+SiLU and x_proj (convx.hip): both directions
     against causal_conv1d_fn + einsum of the oracle (mamba_inner's head).  fp32: 1e-5 (conv) / 3e-5 (x_dbl, K = E sums);
@@ -147,7 +169,9 @@ def test_selective_scan_fp32(ops, L):
                                        (256, 64, torch.bfloat16), (45, 24, torch.bfloat16),
                                        # dt_rank 65..96: K of the in-kernel dt_proj padded to 96 (PlantCAD2 Large), up to 128 generically
                                        (512, 96, torch.bfloat16), (100, 80, torch.float32), (64, 96, torch.float32), (39, 80, torch.bfloat16),
-                                       (48, 128, torch.float32)])
+                                       (48, 128, torch.float32),
+                                       # dt_rank 129 and 256 (K padded to 160 / 256: the largest dt_rank pcad_create takes)
+                                       (40, 129, torch.bfloat16), (33, 256, torch.float32), (64, 256, torch.bfloat16)])
 def test_selective_scan_fused_dtproj(ops, L, R, dtype):
     """engine form: delta = dt_proj.weight @ dt_low on MFMA inside the scan (mamba_inner_fn tail), both directions."""
     u, _, A, Bm, Cm, D, z, db = _scan_inputs(L + R, 2, 128, L)

@@ -54,6 +54,31 @@ def test_abi_create_validates_config_without_gpu(lib):
     assert lib.pcad_create(None, None) == -1
 
 
+def test_abi_create_geometry_edges(lib):
+    """The edges of the geometry pcad_create takes (include/pcad.h pcad_config): d_model up to 2048, dt_rank 1..256, any
+    expand >= 1, residual_in_fp32 0 - accepted, with a workspace and an arena to size; one step past each edge is refused with a
+    message that names the field."""
+    def cfg(**kw):
+        base = dict(d_model=128, n_layer=2, d_state=16, d_conv=4, expand=2, dt_rank=8, vocab=8, eps=1e-5, dtype=1,
+                    residual_in_fp32=1, complement=(C.c_int32 * 8)(0, 1, 2, 6, 5, 4, 3, 7))
+        base.update(kw)
+        return engine.PcadConfig(**base)
+    for ok in (dict(d_model=2048, dt_rank=128), dict(dt_rank=256), dict(dt_rank=1), dict(expand=1), dict(d_model=64, expand=1),
+               dict(expand=3), dict(expand=4), dict(residual_in_fp32=0), dict(dt_rank=97), dict(dt_rank=129)):
+        for dtype in (0, 1):
+            h = C.c_void_p()
+            assert lib.pcad_create(C.byref(cfg(dtype=dtype, **ok)), C.byref(h)) == 0, (ok, lib.pcad_last_error())
+            assert lib.pcad_weight_arena_bytes(h) > 0 and lib.pcad_workspace_bytes(h, 3, 45) > 0, ok
+            lib.pcad_destroy(h)
+    for bad, word in ((dict(dt_rank=257), b"dt_rank=257"), (dict(dt_rank=0), b"dt_rank=0"), (dict(d_model=2112), b"d_model=2112"),
+                      (dict(expand=0), b"expand=0"), (dict(expand=-2), b"expand=-2"), (dict(n_layer=0), b"n_layer=0")):
+        h = C.c_void_p()
+        assert lib.pcad_create(C.byref(cfg(**bad)), C.byref(h)) == -1, bad
+        msg = lib.pcad_last_error()
+        assert msg.startswith(word), (bad, msg)                    # the offending field and its value, and no other field
+        assert not h
+
+
 def test_two_handles_share_no_state(lib):
     """include/pcad.h: distinct handles are independent.  Options, geometry and sizing of one handle never leak into another
     (the per-device launch state - CU count, dynamic-LDS attribute - is keyed by device ordinal inside the library, csrc/pack.hip)."""

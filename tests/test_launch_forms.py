@@ -58,6 +58,59 @@ def test_restatement_matches_library_on_the_grid(lib):
             (False, False, False)} <= forms, forms
 
 
+def test_restatement_matches_library_off_the_shipped_geometry(lib):
+    """pcad_create also takes `expand` 1, 3, 4 (E = D, 3D, 4D: another wave count per strand, another K-tile count of the fused conv +
+    x_proj kernel, another chunk cap, other scratch sizes) and `dt_rank` up to 256 (Rp 128, 160, 256: no fused kernel, hence neither
+    the pair walk nor the K-split; the segmented scan stays).  The library's form scratch must equal the restatement there too:
+    tests/test_gpu_geometries.py names the walk of each of its cases through `engaged_forms` (sizing only; the kernels are
+    checked there)."""
+    n, forms = 0, set()
+    for D in (64, 128, 256, 1024):
+        for expand in (1, 2, 3, 4):
+            for R in (dt_rank(D), 100, 129, 256):
+                if expand == 2 and R == dt_rank(D):
+                    continue                                  # the grid above
+                for bf16 in (False, True):
+                    p = Probe(lib, D, R, bf16, expand=expand)
+                    try:
+                        for L in (63, 128, 256, 300, 512, 2080):
+                            bs = {1, 2, 3, 9}
+                            for waves in (512, 768, 3584):    # waves per direction = 2B * E / 64
+                                b = waves * 32 // (expand * D)
+                                bs |= {b, b + 1}
+                            for B in sorted(x for x in bs if x >= 1):
+                                want = p.predict(B, L)
+                                got = p.scratch(B, L)
+                                assert got == want["scratch"], (D, expand, R, "bf16" if bf16 else "fp32", L, B, got, want)
+                                if R > 96:
+                                    assert not want["pair"] and want["ks"] == 1
+                                forms.add((expand, R > 96, want["G"] > 1, want["pair"], want["ks"] > 1))
+                                n += 1
+                    finally:
+                        p.close()
+    assert n > 3000
+    for expand in (1, 3, 4):
+        # every form is reached off E = 2D as well: segmented, pair, K-split on the fused walk; segmented and plain on the other
+        got = {f[2:] for f in forms if f[0] == expand and not f[1]}
+        assert {(True, False, False), (False, True, False), (False, False, True), (False, False, False)} <= got, (expand, got)
+        assert {f[2:] for f in forms if f[0] == expand and f[1]} == {(True, False, False), (False, False, False)}, expand
+
+
+def test_smallest_shapes_that_reach_each_form_off_the_shipped_geometry():
+    """The restatement itself at the smallest shapes that reach each form with dt_rank > 96 or expand != 2 (hand-counted from
+    csrc/kernels.hpp, like test_bounds_are_where_the_header_says)."""
+    # dt_rank 100 (Rp 128), d_model 128: 2 windows of 300 bp = 16 waves -> 10 segments of one 32-step block, no K-split
+    assert predict(128, 100, False, 2, 300)["G"] == 10 and predict(128, 100, True, 2, 300)["ks"] == 1
+    assert predict(64, 100, False, 1, 2080)["G"] == 4              # one long window: segments of >= 16 blocks
+    for bf16 in (False, True):
+        f = predict(64, 4, bf16, 3, 128, expand=4)                 # E = 256: 24 waves, L % 64 == 0, L < 256 -> the pair walk
+        assert f["pair"] and f["G"] == 1
+        f = predict(64, 4, bf16, 3, 64, expand=1)                  # E = 64: one wave per strand, L < 128 -> the plain walk
+        assert (f["G"], f["pair"], f["ks"]) == (1, False, 1)
+    assert convx_ksplit(6, 64, 64, True) == 1 and convx_ksplit(6, 64, 64, False) == 1       # E = 64: one / two K-tiles, nothing to split
+    assert scan_segments(6, 64, 64)[0] == 1
+
+
 def test_bounds_are_where_the_header_says():
     """The restatement itself, at the bounds include/pcad.h documents (a guard against editing both sides into agreement with
     each other but not with the documentation)."""
