@@ -133,6 +133,18 @@ void   pcad_destroy(pcad_handle h);
  *                 the GEMMs' K-tile cursor wraps around them (hi.hi, lo.hi, hi.lo), so the chunk cap is the fp32 model's own,
  *                 (2^32 - 2 MiB) / (4 d_inner) token-rows.  "last_layer_shortcut" runs the evaluated rows through the same
  *                 split-bf16 product (bit-identical to the full layer).
+ *   "untied_directions"  1: mamba_fwd and mamba_rev each have their own in_proj / out_proj (per-direction LoRA deltas merged into the
+ *                 weights; a model trained with bidirectional_weight_tie = False).  pcad_bind_weights then REQUIRES
+ *                 `mamba_rev.in_proj.weight` / `mamba_rev.out_proj.weight` of every layer (PCAD_ERR_INVALID names a missing one) and packs
+ *                 them beside mamba_fwd's (with "f32_gemm_split" also their [hi | lo] copies): set it before pcad_weight_arena_bytes /
+ *                 pcad_bind_weights (afterwards pcad_forward refuses).  Every forward entry then walks each layer in the strict
+ *                 reference order ("reference_order" 2) with per-direction operands: one add + RMSNorm, in_proj twice, per direction
+ *                 conv + SiLU on its own x (pcad_causal_conv1d_silu_dir), x_proj, the scan gated with its own z, its own out_proj
+ *                 rounded to the model dtype; the two are summed and rounded.  The norm-folded form, the layer-0 table, the fused
+ *                 conv + x_proj kernel and the pair walks are off (they read one x / z for both directions); the segmented scan, the
+ *                 last-layer shortcut, chunking and "f32_gemm_split" work as usual.  pcad_workspace_bytes grows by the second x / z
+ *                 pair.  0 (default): the tied form; of a pair of tied tensors the engine reads mamba_fwd's.  Nothing about the
+ *                 tied form (launches, arena and workspace sizes, results) depends on this option existing.
  *   "reference_order"  one switch over the options above, for users who want every rounding point where the reference has it
  *                 (BiMambaWrapper "add" of two Mamba calls, rms_norm_fn(prenorm=True, residual_in_fp32=True), mamba_inner_fn):
  *                 0 (default): the engine's defaults ("gate_each" 0, "norm_fold" default, layer 0's in_proj as a table);
@@ -188,7 +200,7 @@ size_t pcad_weight_arena_bytes(pcad_handle h);
 
 /* Pack the reference-named tensors (fp32 or bf16, device pointers) into `arena` in the engine's layouts
  * (padded x_proj / dt_proj, pre-exponentiated A, tied in_proj/out_proj stored once).  Tied duplicates
- * (`mamba_rev.in_proj/out_proj`, `lm_head`) may be absent.  The arena must outlive the handle. */
+ * (`mamba_rev.in_proj/out_proj`, `lm_head`) may be absent (not `mamba_rev.in_proj/out_proj` under "untied_directions" 1).  The arena must outlive the handle. */
 int    pcad_bind_weights(pcad_handle h, const pcad_tensor* tensors, int n,
                          void* arena, size_t arena_bytes, pcad_stream stream);
 
@@ -345,6 +357,15 @@ int pcad_add_rmsnorm(const void* x, const void* residual_in, const float* weight
 int pcad_causal_conv1d_silu(const void* x, int64_t ldx, const float* w_fwd, const float* b_fwd,
                             const float* w_rev, const float* b_rev, void* y_fwd, void* y_rev,
                             int S, int L, int E, int dtype, pcad_stream stream);
+
+/* causal_conv1d_fn(x, weight, bias, activation="silu") of ONE direction, token-major (what "untied_directions" runs per direction):
+ *   reverse 0: y[t] = silu(b + sum_k w[k] x[t-3+k]) (causal);  1: y[t] = silu(b + sum_k w[k] x[t+3-k]) (anti-causal: the causal conv of
+ *   the flipped strand, flipped back), per output in pcad_causal_conv1d_silu's arithmetic order (same taps, same x: same bits).
+ *   x [S, L, ldx >= E] / y [S, L, ldy >= E] dtype, plain rows, or - x_blocked / y_blocked - the BLOCKED layout of pcad_conv_xproj_bidir
+ *   below over the S * L rows (rows8 = S * L rounded up to 8; the ld is ignored; E * elem a multiple of 128 bytes);
+ *   w fp32 [E, 4], b fp32 [E]; x, y, w 16-byte aligned; E, ldx, ldy multiples of 16 bytes. */
+int pcad_causal_conv1d_silu_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy,
+                                int S, int L, int E, int reverse, int x_blocked, int y_blocked, int dtype, pcad_stream stream);
 
 /* The form the engine runs for the head of mamba_inner_fn — causal_conv1d_fn(x, w, b, "silu") of BOTH directions fused with
  * BOTH `x_dbl = x_proj(conv_out)` GEMMs, x read once (one kernel instead of causal_conv1d_fwd x2 + cuBLAS x2):

@@ -16,8 +16,10 @@ PEFT wraps, and the wrapper's `.weight` is the base weight.  PEFT initialises `l
 gradient, so an adapter trained there carries lora_B == 0 and is "frozen trunk + trained score".  `lora_deltas`:
   "auto"   (default) all lora_B exactly zero: bind the base weights (logged); otherwise ValueError naming the tensors
   "ignore" bind the base weights whatever the deltas are (what the pinned fast path computes)
-Merging non-zero deltas is not implemented: per-direction deltas would untie in_proj / out_proj between mamba_fwd and mamba_rev
-(DESIGN.md §9).
+  "apply"  merge the deltas into the weights (`merge_lora`: W + lora_alpha / r * B A per direction, in fp32, cast once) - what an
+           environment computes in which `Mamba.forward` calls the wrapped modules (no causal-conv1d, use_fast_path=False, a newer
+           stack).  Per-direction in_proj / out_proj deltas untie the two directions: the engine is then bound with
+           "untied_directions" 1; x_proj is per direction anyway and merges into the tied form.
 """
 from __future__ import annotations
 
@@ -119,6 +121,48 @@ def lora_delta_report(lora: Dict[tuple, Dict[str, torch.Tensor]], r: int, alpha:
     return {"nonzero": nonzero, "max_abs_delta": worst}
 
 
+def merge_lora(base_sd: Dict[str, torch.Tensor], lora: Dict[tuple, Dict[str, torch.Tensor]], r: int, alpha: float,
+               dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
+    """The base state dict (reference key names, `caduceus.backbone. ...`) with the LoRA deltas merged in: for each
+    (layer, direction, module) with factors, `W_dir = W + (alpha / r) * B @ A`, formed in fp32 on the host.  x_proj merges into
+    that direction's own x_proj; in_proj / out_proj - one tied tensor in the base - come back as distinct `mamba_fwd.*` /
+    `mamba_rev.*` tensors, a direction without factors keeping W (a tied duplicate missing from base_sd is taken from mamba_fwd's).
+    dtype: cast the merged tensors to the model dtype - once, after the merge; the other tensors are returned as they are."""
+    scale = float(alpha) / float(r)
+    out = dict(base_sd)
+    for (layer, direction, mod), ab in sorted(lora.items()):
+        key = f"caduceus.backbone.layers.{layer}.mixer.submodule.mamba_{direction}.{mod}.weight"
+        src = key if key in base_sd else key.replace(".mamba_rev.", ".mamba_fwd.")
+        W = base_sd[src].detach().to("cpu", torch.float32)
+        delta = scale * (ab["B"].detach().to("cpu", torch.float32) @ ab["A"].detach().to("cpu", torch.float32))
+        if tuple(delta.shape) != tuple(W.shape):
+            raise ValueError(f"{key}: LoRA delta {tuple(delta.shape)} does not match the weight {tuple(W.shape)}")
+        merged = W + delta
+        out[key] = merged.to(dtype) if dtype is not None else merged
+        if mod != "x_proj":      # the other direction's name must exist too, and must not alias the merged tensor
+            other = key.replace(f".mamba_{direction}.", ".mamba_rev." if direction == "fwd" else ".mamba_fwd.")
+            if (int(layer), "rev" if direction == "fwd" else "fwd", mod) not in lora:
+                Wo = base_sd[other] if other in base_sd else base_sd[src]
+                out[other] = Wo.detach().to("cpu", torch.float32).to(dtype) if dtype is not None else Wo.detach().clone()
+    return out
+
+
+def untie_directions(model) -> None:
+    """Give every layer's mamba_rev its own in_proj / out_proj parameters (copies of mamba_fwd's) and make the engine bind with
+    "untied_directions" 1.  Must run before the model's engine exists (the option is read when the weights are bound)."""
+    owner = model._backbone_owner()
+    if getattr(owner, "_pcad_engine", None) is not None:
+        raise RuntimeError("untie_directions: the engine is already bound; untie before the first forward")
+    for blk in owner.backbone.layers:
+        bm = blk.mixer.submodule
+        for mod in ("in_proj", "out_proj"):
+            src = getattr(bm.mamba_fwd, mod).weight
+            getattr(bm.mamba_rev, mod).weight = torch.nn.Parameter(src.detach().clone(), requires_grad=False)
+    opts = dict(getattr(model.config, "engine_options", None) or {})
+    opts["untied_directions"] = 1
+    model.config.engine_options = opts
+
+
 def load_adapter(dir_or_hub_id: str, task_type: str = "classification", num_labels: Optional[int] = None,
                  lora_deltas: str = "auto", base: Optional[str] = None, dtype=torch.float32, device=None,
                  pooling_strategy: str = "mean", **hub_kwargs):
@@ -129,8 +173,8 @@ def load_adapter(dir_or_hub_id: str, task_type: str = "classification", num_labe
     from .modeling_caduceus import CaduceusForSequenceClassification
     if task_type not in TASKS:
         raise ValueError(f"task_type must be one of {list(TASKS)}, got {task_type!r}")
-    if lora_deltas not in ("auto", "ignore"):
-        raise ValueError(f"lora_deltas must be 'auto' or 'ignore', got {lora_deltas!r}")
+    if lora_deltas not in ("auto", "ignore", "apply"):
+        raise ValueError(f"lora_deltas must be 'auto', 'ignore' or 'apply', got {lora_deltas!r}")
     nl, problem_type = TASKS[task_type]
     if task_type == "multi_label":
         if num_labels is None or int(num_labels) <= 1:
@@ -154,13 +198,37 @@ def load_adapter(dir_or_hub_id: str, task_type: str = "classification", num_labe
         raise ValueError(f"adapter score weight {tuple(aud['score'].shape)} does not match num_labels={nl}, "
                          f"d_model={model.config.d_model} {tuple(model.score.weight.shape)}")
     rep = lora_delta_report(aud["lora"], cfg["r"], cfg["lora_alpha"])
-    if rep["nonzero"]:
+    applied = None
+    if lora_deltas == "apply":
+        from .checkpoint import load_state_dict
+        # only the pairs that change anything are merged: a null delta neither moves a weight nor unties a direction
+        live = {k: ab for k, ab in aud["lora"].items() if torch.count_nonzero(ab["B"]).item()}
+        untied = any(mod != "x_proj" for (_, _, mod) in live)
+        if live:
+            # from the snapshot's own precision, so that a bf16 model's merged weights are rounded once
+            base_sd = {k: v for k, v in load_state_dict(base_path).items() if k.startswith("caduceus.")}
+            merged = merge_lora(base_sd, live, cfg["r"], cfg["lora_alpha"], dtype=dtype)
+            if untied:
+                untie_directions(model)
+            own = model.state_dict()
+            with torch.no_grad():
+                for (layer, direction, mod) in live:
+                    names = [f"caduceus.backbone.layers.{layer}.mixer.submodule.mamba_{direction}.{mod}.weight"]
+                    if mod != "x_proj":
+                        names.append(names[0].replace(f".mamba_{direction}.", ".mamba_rev." if direction == "fwd" else ".mamba_fwd."))
+                    for k in names:
+                        own[k].copy_(merged[k].to(own[k].dtype))
+        applied = {"merged_pairs": len(live), "untied_directions": bool(untied)}
+        logger.info("%d LoRA factor pair(s) of %s merged into the weights (lora_deltas='apply'; largest |lora_alpha / r * B A| = %.3e); "
+                    "bound %s", len(live), path, rep["max_abs_delta"],
+                    "with untied_directions 1 (per-direction in_proj / out_proj)" if untied else "in the tied form")
+    elif rep["nonzero"]:
         msg = (f"{len(rep['nonzero'])} LoRA B factor(s) of {path} are non-zero, e.g. {rep['nonzero'][:3]}; largest "
                f"|lora_alpha / r * B A| = {rep['max_abs_delta']:.3e}")
         if lora_deltas == "auto":
-            raise ValueError(msg + ". Merging non-zero deltas is not supported (they would untie in_proj / out_proj between the "
-                             "two directions); pass lora_deltas='ignore' (--lora-deltas ignore) to bind the base weights, which is "
-                             "what the reference's pinned mamba-ssm fast path computes (it never reads the LoRA modules)")
+            raise ValueError(msg + ". Pass lora_deltas='ignore' (--lora-deltas ignore) to bind the base weights, which is what the "
+                             "reference's pinned mamba-ssm fast path computes (it never reads the LoRA modules), or lora_deltas='apply' "
+                             "(--lora-deltas apply) to merge the deltas, which is what a run that calls the wrapped modules computes")
         logger.warning("%s; binding the base weights (lora_deltas='ignore')", msg)
     elif aud["lora"]:
         logger.info("%d LoRA factor pairs of %s have lora_B == 0: the deltas are null, the base weights are bound",
@@ -170,6 +238,8 @@ def load_adapter(dir_or_hub_id: str, task_type: str = "classification", num_labe
     model.adapter_info = {"path": path, "base": base_path, "r": cfg["r"], "lora_alpha": cfg["lora_alpha"],
                           "target_modules": cfg["target_modules"], "lora_pairs": len(aud["lora"]),
                           "nonzero_lora_B": rep["nonzero"], "max_abs_delta": rep["max_abs_delta"]}
+    if applied is not None:
+        model.adapter_info.update(lora_deltas="apply", **applied)
     if device is not None:
         model.to(device)
     return model

@@ -114,7 +114,7 @@ def save_checkpoint(path: str, config: CaduceusConfig, sd: Dict[str, torch.Tenso
     for k, v in sd.items():
         if k == LMHEAD_KEY:
             continue
-        if ".mamba_rev.in_proj." in k or ".mamba_rev.out_proj." in k:
+        if (".mamba_rev.in_proj." in k or ".mamba_rev.out_proj." in k) and getattr(config, "bidirectional_weight_tie", True):
             continue
         out[k] = v.contiguous().clone()
     save_file(out, os.path.join(path, "model.safetensors"), metadata={"format": "pt"})
@@ -224,7 +224,8 @@ def audit_snapshot(path: str, strict: bool = True) -> dict:
         for i in range(cfg.n_layer):
             f, r = layer_keys(i, "fwd"), layer_keys(i, "rev")
             for nm in ("in_proj", "out_proj"):
-                if not torch.equal(sd[f[nm]], sd[r[nm]]):
+                # bidirectional_weight_tie=False: mamba_rev's own tensors are the model ("untied_directions"), not a problem
+                if cfg.bidirectional_weight_tie and not torch.equal(sd[f[nm]], sd[r[nm]]):
                     untied.append(r[nm])
         cm = [k for k in extra if k.endswith("complement_map")]
         for k in cm:

@@ -103,8 +103,6 @@ class CaduceusConfig(PretrainedConfig):
             bad.append("rcps=False")
         if not self.bidirectional or self.bidirectional_strategy != "add":
             bad.append("bidirectional must be True with strategy 'add'")
-        if not self.bidirectional_weight_tie:
-            bad.append("bidirectional_weight_tie=False")
         if not self.rms_norm:
             bad.append("rms_norm=False")
         if self.d_conv != 4:

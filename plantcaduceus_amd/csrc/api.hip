@@ -59,6 +59,8 @@ struct LayerWeights {
     void* W_out_p;   // [Dp, E]: W_out with zero rows up to Dp = round_up(D, 256) for the folded out_proj (== W_out when D % 256 == 0)
     void* W_in_s;    // [2E, 2D] bf16 = [hi | lo] of W_in: split-bf16 in_proj of the fp32 model ("f32_gemm_split"), else nullptr
     void* W_out_s;   // [D, 2E] bf16 = [hi | lo] of W_out
+    // "untied_directions": mamba_rev's own in_proj / out_proj (W_in / W_out above are then mamba_fwd's), and their [hi | lo] copies; else nullptr
+    void *W_in_r, *W_out_r, *W_in_s_r, *W_out_s_r;
     DirWeights dir[2];
 };
 
@@ -85,6 +87,8 @@ struct pcad_engine {
     int64_t ws_limit = 0;       // pcad_set_option("workspace_limit_mb"): chunks are sized so that the workspace stays below it (0: no limit)
     bool f32_split = false;     // pcad_set_option("f32_gemm_split", 1): the fp32 model's in_proj / out_proj as split-bf16 GEMMs (split_wanted)
     bool split_packed = false;  // ... and their [hi | lo] weight copies exist in the arena (decided like fold_packed)
+    bool untied = false;        // pcad_set_option("untied_directions", 1): mamba_fwd and mamba_rev each run their own in_proj / out_proj
+    bool untied_packed = false; // ... and mamba_rev's weights exist in the arena (decided like fold_packed)
     bool fold_packed = false;   // the norm-folded form's extra weight copies (W_in_f, xz_tab0, padded W_out) exist in the arena: decided
                                 // from the options in force when pcad_weight_arena_bytes / pcad_bind_weights run (fold_wanted)
     int32_t* status = nullptr;   // caller-owned device word for asynchronous input-validation flags (pcad_set_status_buffer)
@@ -121,7 +125,8 @@ struct Carver {
 // whether the options ask for the norm-folded layer form on this model at all (per-forward shape conditions come on top)
 bool fold_wanted(const pcad_engine* e) {
     const bool want = e->norm_fold == 1 || (e->norm_fold < 0 && e->cfg.dtype == PCAD_BF16);
-    return want && e->rdt == F32 && e->xzsplit && e->blocked;
+    // never with "untied_directions": the folded out_proj adds ONE product onto the residual, the untied form has two to round and sum
+    return want && !e->untied && e->rdt == F32 && e->xzsplit && e->blocked;
 }
 
 // "f32_gemm_split": fp32 model only, and never together with the norm-folded form (whose GEMM epilogues are fp32-in / fp32-out)
@@ -157,6 +162,10 @@ void carve_weights(pcad_engine* e, Carver& c) {
         L.W_out_p = pf && (size_t)fold_padded_width((int)D) != D ? c.take((size_t)fold_padded_width((int)D) * E * esz) : L.W_out;
         L.W_in_s = ps ? c.take(2 * E * 2 * D * 2) : nullptr;
         L.W_out_s = ps ? c.take(D * 2 * E * 2) : nullptr;
+        L.W_in_r = e->untied ? c.take(2 * E * D * esz) : nullptr;
+        L.W_out_r = e->untied ? c.take(D * E * esz) : nullptr;
+        L.W_in_s_r = e->untied && ps ? c.take(2 * E * 2 * D * 2) : nullptr;
+        L.W_out_s_r = e->untied && ps ? c.take(D * 2 * E * 2) : nullptr;
         for (int d = 0; d < 2; ++d) {
             DirWeights& w = L.dir[d];
             w.conv_w = (float*)c.take(E * 4 * 4);
@@ -174,6 +183,7 @@ void carve_weights(pcad_engine* e, Carver& c) {
 
 struct Workspace {
     void *res, *u, *h, *xz, *zb, *xc[2], *dtl[2], *y;
+    void *xz2, *zb2;   // "untied_directions": the reverse direction's own in_proj output (laid out as xz / zb); else nullptr
     void* ys;        // "f32_gemm_split": out_proj's operand, bf16 [rows8, 2E] blocked = [hi | lo] of y; else nullptr
     float* bc[2];
     float *rstd, *ssq;   // norm-folded form: rstd [rows]; partial sums of squares [rows, D / 128]
@@ -220,6 +230,10 @@ Workspace carve_workspace(const pcad_engine* e, void* base, int Bc, int L, int B
     // off together with the segmented scan: both trade a different fp32 summation order for parallelism on an otherwise empty chip)
     const size_t cxb = e->segments && e->convx ? convx_split_bytes(2 * Bc, L, (int)E, e->cfg.dtype, e->Rp, 2 * Bpol) : 0;
     w.cxp = cxb ? (float*)c.take(cxb) : nullptr;
+    // carved last, so that every other buffer sits where it does with the option off (and, like everything after h, these are dead
+    // once the last out_proj has run: the heads' partials may cover them)
+    w.xz2 = e->untied ? c.take((e->xzsplit ? rows8z : rows * 2) * E * esz) : nullptr;
+    w.zb2 = e->untied && e->xzsplit ? c.take(rows8z * E * esz) : nullptr;
     w.bytes = c.off;
     return w;
 }
@@ -337,6 +351,8 @@ int pcad_set_option(pcad_handle h, const char* key, int64_t value) {
         h->ws_limit = value << 20;
     } else if (k == "f32_gemm_split") {
         h->f32_split = value != 0;
+    } else if (k == "untied_directions") {
+        h->untied = value != 0;
     } else if (k == "reference_order") {
         // one switch for "every rounding point where the reference has it" (BiMambaWrapper + rms_norm_fn + mamba_inner_fn):
         //   1  = gate_each 1 + norm_fold 0 (which also means no layer-0 in_proj table): only the tied out_proj fold remains
@@ -436,6 +452,19 @@ int pcad_bind_weights(pcad_handle h, const pcad_tensor* tensors, int n, void* ar
         if (L.W_out_p != L.W_out) HIP_TRY(launch_pack2d(t_out->data, t_out->dtype, E, L.W_out_p, dt, E, D, E, fold_padded_width(D), E, s));
         if (L.W_in_s) HIP_TRY(launch_pack_split_w(t_in->data, t_in->dtype, D, L.W_in_s, 2 * E, D, s));
         if (L.W_out_s) HIP_TRY(launch_pack_split_w(t_out->data, t_out->dtype, E, L.W_out_s, D, E, s));
+        if (e->untied) {      // mamba_rev's own in_proj / out_proj: required, not defaulted to mamba_fwd's
+            const std::string mr = lp + "mixer.submodule.mamba_rev.";
+            const pcad_tensor* t_in_r = find(m, mr + "in_proj.weight");
+            if (!t_in_r) return fail(PCAD_ERR_INVALID, "\"untied_directions\" 1 needs tensor %sin_proj.weight", mr.c_str());
+            if (numel(t_in_r) != (int64_t)2 * E * D) return fail(PCAD_ERR_INVALID, "tensor %sin_proj.weight has %lld elements, expected %lld", mr.c_str(), (long long)numel(t_in_r), (long long)2 * E * D);
+            const pcad_tensor* t_out_r = find(m, mr + "out_proj.weight");
+            if (!t_out_r) return fail(PCAD_ERR_INVALID, "\"untied_directions\" 1 needs tensor %sout_proj.weight", mr.c_str());
+            if (numel(t_out_r) != (int64_t)D * E) return fail(PCAD_ERR_INVALID, "tensor %sout_proj.weight has %lld elements, expected %lld", mr.c_str(), (long long)numel(t_out_r), (long long)D * E);
+            HIP_TRY(launch_pack2d(t_in_r->data, t_in_r->dtype, D, L.W_in_r, dt, D, 2 * E, D, 2 * E, D, s));
+            HIP_TRY(launch_pack2d(t_out_r->data, t_out_r->dtype, E, L.W_out_r, dt, E, D, E, D, E, s));
+            if (L.W_in_s_r) HIP_TRY(launch_pack_split_w(t_in_r->data, t_in_r->dtype, D, L.W_in_s_r, 2 * E, D, s));
+            if (L.W_out_s_r) HIP_TRY(launch_pack_split_w(t_out_r->data, t_out_r->dtype, E, L.W_out_s_r, D, E, s));
+        }
         for (int d = 0; d < 2; ++d) {
             DirWeights& w = L.dir[d];
             const std::string mp = lp + "mixer.submodule.mamba_" + (d == 0 ? "fwd." : "rev.");
@@ -468,6 +497,7 @@ int pcad_bind_weights(pcad_handle h, const pcad_tensor* tensors, int n, void* ar
     if (e->xz_tab0) HIP_TRY(launch_embed_inproj_table(e->emb, e->layers[0].W_in_f, e->xz_tab0, V, D, 2 * E, e->cfg.eps, dt, s));
     e->fold_packed = fold_wanted(e);
     e->split_packed = split_wanted(e);
+    e->untied_packed = e->untied;
     e->bound = true;
     return PCAD_OK;
 }
@@ -621,6 +651,16 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
     if (split_wanted(e) && !e->split_packed)
         return fail(PCAD_ERR_INVALID, "pcad_forward: \"f32_gemm_split\" 1 was set after pcad_bind_weights; the split weight copies are packed at "
                                       "bind time - set the option before pcad_weight_arena_bytes / pcad_bind_weights");
+    if (e->untied && !e->untied_packed)
+        return fail(PCAD_ERR_INVALID, "pcad_forward: \"untied_directions\" 1 was set after pcad_bind_weights; mamba_rev's in_proj / out_proj are packed at "
+                                      "bind time - set the option before pcad_weight_arena_bytes / pcad_bind_weights");
+    // Untied directions ("untied_directions": per-direction LoRA deltas, bidirectional_weight_tie = False).  mamba_fwd and mamba_rev
+    // no longer share in_proj / out_proj, so a layer is the strict reference order ("reference_order" 2) with per-direction operands:
+    // one add + norm; in_proj twice (x_f, z_f / x_r, z_r); per direction conv + SiLU on its own x (conv.hip launch_conv_dir), x_proj
+    // as a GEMM, the scan gated with its own z; each direction's own out_proj, each rounded, summed and rounded.  The fused conv +
+    // x_proj kernel, the pair walks and the scan-written out_proj operand all read ONE x / z for both directions and are off; the
+    // segmented scan and the last-layer shortcut take z per launch and stay on.
+    const bool untied = e->untied && e->untied_packed;
     // Split-bf16 GEMMs of the fp32 model ("f32_gemm_split"; pack.hip): in_proj and out_proj - 3/4 of the fp32 model's time on the
     // fp32 MFMA instructions - run as bf16 GEMMs of 3 K / 64 K-tiles on [hi | lo] x [hi | lo] operands (wrap-around K cursor: hi.hi,
     // lo.hi, hi.lo; gemm.hip) with an fp32 result: operand error 2^-17, measured 4e-7 of the logits' range after 32 layers (fp32 MFMA:
@@ -694,6 +734,19 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
         const LayerWeights& W = e->layers[li];
         const int S = 2 * c.Bc;
         const int64_t rows = (int64_t)S * L;
+        if (untied) {
+            for (int d = 0; d < 2; ++d) {       // each direction's own in_proj, then conv + SiLU on its own x
+                void *xd = d ? c.w.xz2 : c.w.xz, *zd = d ? c.w.zb2 : c.w.zb;
+                { ProfScope ps(e, PCAD_K_GEMM_IN, s);
+                if (sp) HIP_TRY(launch_gemm_nt_two(c.w.u, 2 * D, d ? W.W_in_s_r : W.W_in_s, 2 * D, xd, zd, E, true, rows, 2 * E, 3 * D, BF16, s, nullptr, F32, D / 64));
+                else if (e->xzsplit) HIP_TRY(launch_gemm_nt_two(c.w.u, D, d ? W.W_in_r : W.W_in, D, xd, zd, E, true, rows, 2 * E, D, dt, s));
+                else HIP_TRY(launch_gemm_nt(c.w.u, D, d ? W.W_in_r : W.W_in, D, xd, 2 * E, rows, 2 * E, D, dt, dt, false, s)); }
+                ProfScope ps(e, PCAD_K_CONV, s);
+                HIP_TRY(launch_conv_dir(xd, e->xzsplit ? E : 2 * E, W.dir[d].conv_w, W.dir[d].conv_b, c.w.xc[d], E, S, L, E, dt, d == 1, e->blocked,
+                                        e->xzsplit, s));
+            }
+            return PCAD_OK;
+        }
         // in_proj (tied between directions: once per strand)
         // Layer 0 of the norm-folded form: the operand rows are the V = 8 embedding rows themselves, so in_proj's output is a look-up
         // (table built at bind time): one copy kernel instead of 1 / n_layer of the in_proj GEMMs.  PCAD_DEV=1 PCAD_NO_TAB0=1: the GEMM.
@@ -740,10 +793,11 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
         const int64_t rows = (int64_t)S * L;
         const bool last_short = walk_len > 0 && li + 1 == e->nl;
         // split-bf16 dt_proj inside the scan ("f32_gemm_split"): the fused conv + x_proj kernel wrote dt_low as bf16 [rows, 3 Rp]
-        const bool dts = sp && e->convx && ((int64_t)rows + 16) * E * esz < ((int64_t)1 << 32);
+        const bool convx_ran = !untied && e->convx && ((int64_t)rows + 16) * E * esz < ((int64_t)1 << 32);     // phase_P's choice
+        const bool dts = sp && convx_ran;
         // strict reference order ("reference_order" 2; never with norm_fold): the reverse direction's gated output goes to its own
         // tensor (xc[0]: the forward scan, its only reader, has run) and each direction gets its own tied out_proj below
-        const bool strict = e->ref_order == 2 && !c.fold;
+        const bool strict = (e->ref_order == 2 || untied) && !c.fold;
         void* y_rev = strict ? c.w.xc[0] : c.w.y;
         // "f32_gemm_split": out_proj's [hi | lo] operand is written by the gating (reverse) scan itself where it can (whole walk,
         // unsegmented, L % 8 == 0, one out_proj for both directions), instead of fp32 y + a conversion pass
@@ -751,14 +805,15 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                                   !(c.w.seg && scan_segments(2 * B, L, E, nullptr) > 1);
         // the full-size tied out_proj of one [rows, E] tensor (y, or in the strict order each direction's own): fp32 / bf16 GEMM, or the
         // split-bf16 form (operand conversion unless the scan wrote it + bf16 GEMM with K' = 3E, fp32 result)
-        auto out_proj_full = [&](const void* ysrc, void* dst) -> hipError_t {
+        auto out_proj_full = [&](const void* ysrc, void* dst, int d = 0) -> hipError_t {       // d: whose weight (untied form only)
+            const void *Wo = untied && d ? W.W_out_r : W.W_out, *Wo_s = untied && d ? W.W_out_s_r : W.W_out_s;
             if (sp) {
                 if (!(ys_from_scan && ysrc == c.w.y)) {
                     if (hipError_t er = launch_split_rows((const float*)ysrc, E, c.w.ys, rows, E, e->blocked, e->blocked, s)) return er;
                 }
-                return launch_gemm_nt(c.w.ys, 2 * E, W.W_out_s, 2 * E, dst, D, rows, D, 3 * E, BF16, F32, false, s, e->blocked, E / 64);
+                return launch_gemm_nt(c.w.ys, 2 * E, Wo_s, 2 * E, dst, D, rows, D, 3 * E, BF16, F32, false, s, e->blocked, E / 64);
             }
-            return launch_gemm_nt(ysrc, E, W.W_out, E, dst, D, rows, D, E, dt, dt, false, s, e->blocked);
+            return launch_gemm_nt(ysrc, E, Wo, E, dst, D, rows, D, E, dt, dt, false, s, e->blocked);
         };
         // Pair walks (kernels.hpp scan_pair_wanted: few waves per launch - long windows in small batches): both directions in one
         // launch, half a strand each, twice; chosen from the strands of the whole call like the segmented form
@@ -779,7 +834,7 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
         for (int d = 0; d < 2 && !pair; ++d) {
             const DirWeights& dw = W.dir[d];
             // x_proj -> dt_low [rows, Rp] (model dtype, zero padded) and B_t | C_t [rows, 32] (fp32 side output)
-            if (!(e->convx && ((int64_t)rows + 16) * E * esz < ((int64_t)1 << 32))) { ProfScope ps(e, PCAD_K_GEMM_X, s);
+            if (!convx_ran) { ProfScope ps(e, PCAD_K_GEMM_X, s);
             HIP_TRY(launch_gemm_nt_split(c.w.xc[d], E, dw.Wx, E, c.w.dtl[d], Rp, c.w.bc[d], 2 * N, Rp, rows, XP, E, dt, s,
                                          e->blocked)); }
             // dt_proj (on MFMA inside the scan) + bias + softplus + recurrence + D skip + SiLU(z) gate
@@ -788,6 +843,7 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                                     dw.Dskip, dw.dt_bias, c.w.y, S, L, E, false, 0, dt, s, e->blocked, e->xzsplit, c.w.seg, 0, nullptr, dts, 2 * B));
             ProfScope ps(e, PCAD_K_SCAN, s);
             const void* zp = e->xzsplit ? c.w.zb : (const void*)((const char*)c.w.xz + (size_t)E * esz);
+            if (untied && d == 1) zp = e->xzsplit ? c.w.zb2 : (const void*)((const char*)c.w.xz2 + (size_t)E * esz);      // its own in_proj's z
             // gate_once: the forward scan stores its ungated output, the reverse scan adds its own and applies SiLU(z)
             // to the sum (one SiLU per element instead of two, z read once; a rounding-order difference from
             // y_f*g + y_r*g, like the out_proj fold below).  PCAD_GATE_EACH=1: each direction gated and rounded.
@@ -805,24 +861,25 @@ static int forward_impl(pcad_handle h, const int32_t* ids, int B, int L, const i
                 ProfScope ps(e, PCAD_K_HEAD, s);
                 // the gathered rows of one direction (in u) through the tied out_proj: the same product as the full-size launch
                 // (split-bf16 with "f32_gemm_split": bit-identical rows)
-                auto out_proj_rows = [&](void* dst) -> hipError_t {
+                auto out_proj_rows = [&](void* dst, int d) -> hipError_t {
+                    const void *Wo = untied && d ? W.W_out_r : W.W_out, *Wo_s = untied && d ? W.W_out_s_r : W.W_out_s;
                     if (sp) {
                         if (hipError_t er = launch_split_rows((const float*)c.w.u, E, c.w.ys, (int64_t)S * P, E, false, false, s)) return er;
-                        return launch_gemm_nt(c.w.ys, 2 * E, W.W_out_s, 2 * E, dst, D, (int64_t)S * P, D, 3 * E, BF16, F32, false, s, false, E / 64);
+                        return launch_gemm_nt(c.w.ys, 2 * E, Wo_s, 2 * E, dst, D, (int64_t)S * P, D, 3 * E, BF16, F32, false, s, false, E / 64);
                     }
-                    return launch_gemm_nt(c.w.u, E, W.W_out, E, dst, D, (int64_t)S * P, D, E, dt, dt, false, s, false);
+                    return launch_gemm_nt(c.w.u, E, Wo, E, dst, D, (int64_t)S * P, D, E, dt, dt, false, s, false);
                 };
                 HIP_TRY(launch_gather_rows(c.w.y, c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
-                HIP_TRY(out_proj_rows(c.w.h));
+                HIP_TRY(out_proj_rows(c.w.h, 0));
                 HIP_TRY(launch_gather_rows(y_rev, c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
-                HIP_TRY(out_proj_rows(c.w.xz));
+                HIP_TRY(out_proj_rows(c.w.xz, 1));
                 HIP_TRY(launch_add_round(c.w.h, c.w.xz, (int64_t)S * P * D, dt, s));
                 return PCAD_OK;
             }
             { ProfScope ps(e, PCAD_K_GEMM_OUT, s);
             HIP_TRY(out_proj_full(c.w.y, c.w.h)); }
             { ProfScope ps(e, PCAD_K_GEMM_OUT, s);
-            HIP_TRY(out_proj_full(y_rev, c.w.u)); }
+            HIP_TRY(out_proj_full(y_rev, c.w.u, 1)); }
             { ProfScope ps(e, PCAD_K_NORM, s);
             HIP_TRY(launch_add_round(c.w.h, c.w.u, rows * D, dt, s)); }
             if (all_hidden && li + 1 < e->nl) {
@@ -1100,6 +1157,21 @@ int pcad_causal_conv1d_silu(const void* x, int64_t ldx, const float* w_fwd, cons
     if (S < 0 || L < 0 || E <= 0 || E % 8 || ldx < E || ldx % 8)
         return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu: bad shape (E and ldx must be multiples of 8)");
     HIP_TRY(launch_conv_bidir(x, ldx, w_fwd, b_fwd, w_rev, b_rev, y_fwd, y_rev, S, L, E, dtype, false, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_causal_conv1d_silu_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int S, int L, int E,
+                                int reverse, int x_blocked, int y_blocked, int dtype, pcad_stream stream) {
+    if (!x || !w || !b || !y) return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: bad dtype");
+    const int esz = dtype == PCAD_BF16 ? 2 : 4, V = 16 / esz;
+    if (S < 0 || L < 0 || E <= 0 || E % V || (!x_blocked && (ldx < E || ldx % V)) || (!y_blocked && (ldy < E || ldy % V)))
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: bad shape (E, ldx and ldy * elem must be multiples of 16 bytes; ldx, ldy >= E)");
+    if ((x_blocked || y_blocked) && ((int64_t)E * esz) % 128)
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: the blocked layout needs E * elem to be a multiple of 128 bytes");
+    if (((uintptr_t)x) % 16 || ((uintptr_t)y) % 16 || ((uintptr_t)w) % 16)
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: x, y and w must be 16-byte aligned");
+    HIP_TRY(launch_conv_dir(x, ldx, w, b, y, ldy, S, L, E, dtype, reverse != 0, y_blocked != 0, x_blocked != 0, (hipStream_t)stream));
     return PCAD_OK;
 }
 

@@ -144,4 +144,117 @@ hipError_t launch_conv_bidir(const void* x, int64_t ldx, const float* wf, const 
     return hipGetLastError();
 }
 
+// ---- one direction ---------------------------------------------------------------------------------------------------
+// The untied-directions form (api.hip "untied_directions") gives each direction its own in_proj, hence its own x: one read of x can no
+// longer feed both convolutions, so this kernel reads ONE x and writes ONE xc, causal (REV = false) or anti-causal (REV = true).
+// HBM-bound at 2 E s bytes per row (one read, one write).  A lane owns 16 bytes of a row (8 bf16 / 4 fp32 channels), so 8 consecutive
+// lanes move one 128-byte piece - one piece of the blocked layout, or 128 contiguous bytes of a plain row - per access, and slides a
+// 4-row window along CONV_SEG consecutive timesteps of its direction: every row is read once (+ the 3-row halo per segment, straight
+// from L2: no LDS), the taps are loaded once per thread, and the rows of the next 4-step group are in flight while the current one is
+// computed.  Per output the products are accumulated in conv_bidir_kernel's order (bias, then taps 0..3), so with the same taps and
+// the same x the values are conv_bidir_kernel's, bit for bit.
+template <typename T> struct Raw16;
+template <> struct Raw16<bf16_t> {
+    typedef u32x4 type; enum { N = 8 };
+    static __device__ __forceinline__ void unpack(const u32x4& r, float (&v)[8]) { raw_unpack(r, v); }
+    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) { store8<bf16_t>(p, v); }
+};
+template <> struct Raw16<float> {
+    typedef f32x4 type; enum { N = 4 };
+    static __device__ __forceinline__ void unpack(const f32x4& r, float (&v)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = r[i];
+    }
+    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
+};
+
+template <typename T, bool REV>
+__global__ __launch_bounds__(256) void conv_dir_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ w,
+                                                       const float* __restrict__ bw, T* __restrict__ y, int64_t ldy, int S, int L, int E,
+                                                       int out_blocked, int in_blocked) {
+    typedef typename Raw16<T>::type raw_t;
+    constexpr int V = Raw16<T>::N;
+    const int nchunk = E / V;
+    const int nseg = (L + CONV_SEG - 1) / CONV_SEG;
+    const int64_t total = (int64_t)S * nseg * nchunk;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % nchunk) * V;
+    const int64_t rb = i / nchunk;
+    const int s = (int)(rb / nseg);
+    const int t0 = (int)(rb - (int64_t)s * nseg) * CONV_SEG;
+    const int t1 = min(L, t0 + CONV_SEG);
+    const int64_t pieces = ((int64_t)E * sizeof(T)) >> 7;
+
+    float wv[V][4], bv[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(w + (int64_t)(c + e) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wv[e][k] = a[k];
+        bv[e] = bw[c + e];
+    }
+
+    auto row = [&](int t) -> raw_t {                  // rows outside the strand are the conv's zero padding: never another strand's
+        if (t < 0 || t >= L) return raw_t{0, 0, 0, 0};
+        if (in_blocked) return *reinterpret_cast<const raw_t*>(x + blocked_off((int64_t)s * L + t, (int64_t)c * sizeof(T), pieces) / (int64_t)sizeof(T));
+        return *reinterpret_cast<const raw_t*>(x + ((int64_t)s * L + t) * ldx + c);
+    };
+
+    // ext[j] = x[t + sh + j], j = 0 .. 3 + CONV_UN - 1, for the group starting at t; sh = -3 (causal: x[t-3 .. t]) or 0 (anti-causal:
+    // x[t .. t+3]); ext[0..2] carried from the previous group, ext[3..] prefetched
+    constexpr int sh = REV ? 0 : -3;
+    float ext[3 + CONV_UN][V];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Raw16<T>::unpack(row(t0 + sh + j), ext[j]);
+    raw_t nxt[CONV_UN];
+#pragma unroll
+    for (int j = 0; j < CONV_UN; ++j) nxt[j] = row(t0 + sh + 3 + j);
+
+    for (int t = t0; t < t1; t += CONV_UN) {
+#pragma unroll
+        for (int j = 0; j < CONV_UN; ++j) Raw16<T>::unpack(nxt[j], ext[3 + j]);
+#pragma unroll
+        for (int j = 0; j < CONV_UN; ++j) nxt[j] = row(t + CONV_UN + sh + 3 + j);     // rows of the NEXT group, in flight
+#pragma unroll
+        for (int k = 0; k < CONV_UN; ++k) {
+            if (t + k < t1) {
+                float o[V];
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    float a = bv[e];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) a += wv[e][q] * ext[REV ? k + 3 - q : k + q][e];      // x[t+k + 3 - q] / x[t+k - 3 + q]
+                    o[e] = silu(a);
+                }
+                const int64_t orow = (int64_t)s * L + t + k;
+                const int64_t off = out_blocked ? blocked_off(orow, (int64_t)c * sizeof(T), pieces) / (int64_t)sizeof(T) : orow * ldy + c;
+                Raw16<T>::store(y + off, o);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int e = 0; e < V; ++e) ext[j][e] = ext[j + CONV_UN][e];
+    }
+}
+
+hipError_t launch_conv_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int S, int L, int E, int dt,
+                           bool reverse, bool out_blocked, bool in_blocked, hipStream_t s) {
+    if (S <= 0 || L <= 0) return hipSuccess;
+    const int esz = dt == BF16 ? 2 : 4, V = 16 / esz;
+    if (E <= 0 || E % V || (!in_blocked && (ldx < E || ldx % V)) || (!out_blocked && (ldy < E || ldy % V))) return hipErrorInvalidValue;
+    if ((out_blocked || in_blocked) && (E * esz) % 128) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)S * ((L + CONV_SEG - 1) / CONV_SEG) * (E / V);
+    const int64_t nb = (total + 255) / 256;
+    if (nb > 0x7fffffff) return hipErrorInvalidValue;
+#define PCAD_CONV_DIR(T, R)                                                                                                         \
+    hipLaunchKernelGGL((conv_dir_kernel<T, R>), dim3((unsigned)nb), dim3(256), 0, s, (const T*)x, ldx, w, b, (T*)y, ldy, S, L, E, \
+                       (int)out_blocked, (int)in_blocked)
+    if (dt == BF16) { if (reverse) PCAD_CONV_DIR(bf16_t, true); else PCAD_CONV_DIR(bf16_t, false); }
+    else            { if (reverse) PCAD_CONV_DIR(float, true); else PCAD_CONV_DIR(float, false); }
+#undef PCAD_CONV_DIR
+    return hipGetLastError();
+}
+
 }  // namespace pcad

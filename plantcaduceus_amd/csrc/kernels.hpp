@@ -135,6 +135,12 @@ inline int fold_padded_width(int D) { return (D + 255) / 256 * 256; }     // wid
 hipError_t launch_conv_bidir(const void* x, int64_t ldx, const float* wf, const float* bf, const float* wr,
                              const float* br, void* yf, void* yr, int S, int L, int E, int dt, bool out_blocked,
                              hipStream_t s, bool in_blocked = false);
+// One direction ("untied_directions": each direction has its own x): y[t] = silu(b + sum_k w[k] x[t-3+k]) (causal) or, reverse,
+// silu(b + sum_k w[k] x[t+3-k]) (anti-causal), the same arithmetic order per output as launch_conv_bidir.  x / y: plain rows of
+// ldx / ldy elements (multiples of 16 bytes) or the blocked layout (in_blocked / out_blocked; the ld is then ignored); 16-byte
+// aligned pointers; E * elem a multiple of 16 bytes (blocked: of 128).
+hipError_t launch_conv_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int S, int L, int E, int dt,
+                           bool reverse, bool out_blocked, bool in_blocked, hipStream_t s);
 
 // convx.hip -------------------------------------------------------------------------------------
 // Fused conv1d+SiLU (both directions) + x_proj (both directions), Rp == 64 or 96: x [S*L, E] blocked -> xc0 / xc1 [S*L, E]

@@ -61,6 +61,8 @@ SIGNATURES = {
                                    C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "pcad_causal_conv1d_silu": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pcad_causal_conv1d_silu_dir": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pcad_conv_xproj_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "pcad_conv_xproj_bidir": (C.c_int, [C.c_void_p] * 14 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pcad_selective_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -225,6 +227,8 @@ class Engine:
         self._h = C.c_void_p()
         _check(self.lib.pcad_create(C.byref(cfg), C.byref(self._h)), "pcad_create")
         self._ws: Optional[torch.Tensor] = None
+        if not getattr(config, "bidirectional_weight_tie", True):
+            self.set_option("untied_directions", 1)      # mamba_rev has its own in_proj / out_proj: bound beside mamba_fwd's
         for key, val in (getattr(config, "engine_options", None) or {}).items():
             self.set_option(key, int(val))
         with torch.cuda.device(self.device):
@@ -539,9 +543,10 @@ class Engine:
     def set_option(self, key: str, value: int):
         """`pcad_set_option` (include/pcad.h): "chunk_seqs" (windows per pass through the stack), "gate_each" (reference-order
         SiLU gate), "norm_fold" (add + RMSNorm folded into out_proj's epilogue / in_proj), "reference_order" (0 / 1 / 2: one switch for
-        the reference's rounding points), "f32_gemm_split" (fp32 model: split-bf16 in_proj / out_proj), "scan_segments" (segmented
-        scan of long strands), "last_layer_shortcut", "poison_workspace" (debug).  "norm_fold" 1 on an fp32 model and
-        "f32_gemm_split" need weight copies packed at bind time: pass them as `config.engine_options` (applied before binding)."""
+        the reference's rounding points), "f32_gemm_split" (fp32 model: split-bf16 in_proj / out_proj), "untied_directions" (mamba_rev's
+        own in_proj / out_proj: merged LoRA deltas, bidirectional_weight_tie=False), "scan_segments" (segmented scan of long strands),
+        "last_layer_shortcut", "poison_workspace" (debug).  "norm_fold" 1 on an fp32 model, "f32_gemm_split" and "untied_directions"
+        need weights packed at bind time: pass them as `config.engine_options` (applied before binding)."""
         _check(self.lib.pcad_set_option(self._h, key.encode(), int(value)), "pcad_set_option")
         self._ws = None
 

@@ -339,7 +339,7 @@ def build_parser():
         flag(q, "device", default="cuda:0")
         flag(q, "dtype", default="float32", choices=("float32", "bfloat16"))
         flag(q, "pooling", default="mean", choices=("mean", "max", "first", "last"))
-        flag(q, "lora_deltas", default="auto", choices=("auto", "ignore"))
+        flag(q, "lora_deltas", default="auto", choices=("auto", "ignore", "apply"))
     return p
 
 

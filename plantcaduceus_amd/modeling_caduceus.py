@@ -57,9 +57,11 @@ class _BiMamba(nn.Module):
         super().__init__()
         self.mamba_fwd = _Mamba(cfg)
         self.mamba_rev = _Mamba(cfg)
-        # bidirectional_weight_tie (BiMambaWrapper): in_proj / out_proj shared
-        self.mamba_rev.in_proj.weight = self.mamba_fwd.in_proj.weight
-        self.mamba_rev.out_proj.weight = self.mamba_fwd.out_proj.weight
+        # bidirectional_weight_tie (BiMambaWrapper): in_proj / out_proj shared; False: each direction its own (the engine's
+        # "untied_directions" form)
+        if getattr(cfg, "bidirectional_weight_tie", True):
+            self.mamba_rev.in_proj.weight = self.mamba_fwd.in_proj.weight
+            self.mamba_rev.out_proj.weight = self.mamba_fwd.out_proj.weight
 
 
 class _RCPSWrapper(nn.Module):

@@ -84,6 +84,28 @@ def from_blocked(xb: torch.Tensor, rows: int) -> torch.Tensor:
     return xb.permute(0, 2, 1, 3).reshape(nb * 8, pieces * per)[:rows].contiguous()
 
 
+def causal_conv1d_dir(x_tm, weight, bias, reverse: bool = False, blocked: bool = False):
+    """One direction of the conv (pcad_causal_conv1d_silu_dir, what "untied_directions" runs per direction): x_tm [S, L, E] ->
+    y [S, L, E]; reverse: anti-causal (the causal conv of the flipped strand, flipped back).  blocked: x is handed over and y is
+    returned through the engine's blocked layout (`to_blocked` / `from_blocked`) instead of plain rows."""
+    _require_gpu(x_tm, "x")
+    lib = load_library()
+    S, L, E = x_tm.shape
+    w = weight.reshape(E, -1).float().contiguous()
+    b = bias.float().contiguous()
+    with torch.cuda.device(x_tm.device):
+        if blocked:
+            xin = to_blocked(x_tm.reshape(S * L, E))
+            # NaN where the kernel must write, so that a row it skipped shows; the padding rows are not its to write
+            yb = torch.full_like(xin, float("nan"))
+        else:
+            xin = x_tm.contiguous()
+            yb = torch.full_like(xin, float("nan"))
+        _check(lib.pcad_causal_conv1d_silu_dir(xin.data_ptr(), E, w.data_ptr(), b.data_ptr(), yb.data_ptr(), E, S, L, E, int(bool(reverse)),
+                                               int(blocked), int(blocked), _dt(x_tm), _stream_ptr()), "pcad_causal_conv1d_silu_dir")
+    return from_blocked(yb, S * L).view(S, L, E) if blocked else yb
+
+
 def _conv_xproj_raw(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev):
     """pcad_conv_xproj_bidir on a token-major x [S, L, E]: -> (xc [2] blocked, dtl [2] [rows, Rp], bc [2] fp32 [rows, 32], R, Rp)."""
     _require_gpu(x_tm, "x")
