@@ -1,0 +1,271 @@
+// The per-operator entry points of libpcad.so (include/pcad.h): argument checks + the launch; nothing here touches a handle.
+#include "pcad_internal.hpp"
+using namespace pcad;
+
+// what the head operators (final / pooled / loss / probs) check alike: residual layout, dtypes, shape; `who`: the entry's name
+static int head_args(const char* who, int B, int L, int D, int dtype, int res_dtype, int res_fragment_layout) {
+    if (res_fragment_layout && (res_dtype != PCAD_F32 || D % 256 || ((int64_t)2 * B * L) % 256))
+        return fail(PCAD_ERR_INVALID, "%s: the fragment layout needs an fp32 residual, D %% 256 == 0 and 2 B L %% 256 == 0", who);
+    if ((dtype != PCAD_F32 && dtype != PCAD_BF16) || (res_dtype != PCAD_F32 && res_dtype != PCAD_BF16) || (dtype == PCAD_F32 && res_dtype != PCAD_F32))
+        return fail(PCAD_ERR_INVALID, "%s: bad dtype / res_dtype", who);
+    if (B < 0 || L <= 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "%s: bad B / L / D", who);
+    return PCAD_OK;
+}
+
+extern "C" {
+
+int pcad_add_rmsnorm(const void* x, const void* residual_in, const float* weight, void* y, void* residual_out,
+                     int64_t rows, int D, float eps, int dtype, int res_dtype, pcad_stream stream) {
+    if (!x || !weight || !y) return fail(PCAD_ERR_INVALID, "pcad_add_rmsnorm: null argument");
+    if (rows < 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "pcad_add_rmsnorm: bad rows/D");
+    HIP_TRY(launch_add_rmsnorm(x, residual_in, weight, y, residual_out, rows, D, eps, dtype, res_dtype,
+                               (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_causal_conv1d_silu(const void* x, int64_t ldx, const float* w_fwd, const float* b_fwd, const float* w_rev,
+                            const float* b_rev, void* y_fwd, void* y_rev, int S, int L, int E, int dtype,
+                            pcad_stream stream) {
+    if (!x || !w_fwd || !b_fwd || !w_rev || !b_rev) return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu: null argument");
+    if (S < 0 || L < 0 || E <= 0 || E % 8 || ldx < E || ldx % 8)
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu: bad shape (E and ldx must be multiples of 8)");
+    HIP_TRY(launch_conv_bidir(x, ldx, w_fwd, b_fwd, w_rev, b_rev, y_fwd, y_rev, S, L, E, dtype, false, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_causal_conv1d_silu_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int S, int L, int E,
+                                int reverse, int x_blocked, int y_blocked, int dtype, pcad_stream stream) {
+    if (!x || !w || !b || !y) return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: bad dtype");
+    const int esz = dtype == PCAD_BF16 ? 2 : 4, V = 16 / esz;
+    if (S < 0 || L < 0 || E <= 0 || E % V || (!x_blocked && (ldx < E || ldx % V)) || (!y_blocked && (ldy < E || ldy % V)))
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: bad shape (E, ldx and ldy * elem must be multiples of 16 bytes; ldx, ldy >= E)");
+    if ((x_blocked || y_blocked) && ((int64_t)E * esz) % 128)
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: the blocked layout needs E * elem to be a multiple of 128 bytes");
+    if (((uintptr_t)x) % 16 || ((uintptr_t)y) % 16 || ((uintptr_t)w) % 16)
+        return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: x, y and w must be 16-byte aligned");
+    HIP_TRY(launch_conv_dir(x, ldx, w, b, y, ldy, S, L, E, dtype, reverse != 0, y_blocked != 0, x_blocked != 0, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+size_t pcad_conv_xproj_scratch_bytes(int E, int dtype) {
+    if (E <= 0 || (dtype != PCAD_F32 && dtype != PCAD_BF16) || (E * (dtype == PCAD_BF16 ? 2 : 4)) % 128) return 0;
+    return convx_packed_bytes(E, dtype);
+}
+
+int pcad_conv_xproj_bidir(const void* x, const float* w_fwd, const float* b_fwd, const float* w_rev, const float* b_rev,
+                          const void* Wx_fwd, const void* Wx_rev, void* scratch, void* xc_fwd, void* dtl_fwd,
+                          float* bc_fwd, void* xc_rev, void* dtl_rev, float* bc_rev, int S, int L, int E, int Rp, int dtype,
+                          pcad_stream stream) {
+    if (!x || !w_fwd || !b_fwd || !w_rev || !b_rev || !Wx_fwd || !Wx_rev || !scratch || !xc_fwd || !dtl_fwd || !bc_fwd ||
+        !xc_rev || !dtl_rev || !bc_rev)
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir: bad dtype");
+    if (Rp != 64 && Rp != 96) return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir: Rp must be 64 (dt_rank <= 64) or 96 (dt_rank 65..96)");
+    const int64_t esz = dtype == PCAD_BF16 ? 2 : 4;
+    if (S < 0 || L < 0 || E <= 0 || (E * esz) % 128)
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir: E * elem must be a multiple of 128 bytes");
+    if (((int64_t)S * L + 16) * E * esz >= ((int64_t)1 << 32))
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir: (S*L + 16) * E * elem must be < 2^32 (32-bit in-tensor offsets)");
+    if (S == 0 || L == 0) return PCAD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_pack_convw(w_fwd, b_fwd, w_rev, b_rev, (float*)scratch, E, dtype, s));
+    HIP_TRY(launch_convx(x, (const float*)scratch, Wx_fwd, xc_fwd, dtl_fwd, bc_fwd, Wx_rev, xc_rev, dtl_rev, bc_rev, S, L, E,
+                         dtype, s, Rp));
+    return PCAD_OK;
+}
+
+static int scan_args_ok(const void* u, const float* bc, const float* A, const float* Dskip, const float* delta_bias,
+                        void* y, int S, int L, int E) {
+    if (!u || !bc || !A || !Dskip || !delta_bias || !y) return fail(PCAD_ERR_INVALID, "pcad_selective_scan: null argument");
+    if (S < 0 || L < 0 || E <= 0 || E % 64) return fail(PCAD_ERR_INVALID, "pcad_selective_scan: E must be a multiple of 64");
+    if (((uintptr_t)bc) % 16) return fail(PCAD_ERR_INVALID, "pcad_selective_scan: bc must be 16-byte aligned");
+    return PCAD_OK;
+}
+
+int pcad_selective_scan(const void* u, const void* delta, const void* z, int64_t ldz, const float* bc, const float* A,
+                        const float* Dskip, const float* delta_bias, void* y, int S, int L, int E, int reverse,
+                        int accumulate, int dtype, pcad_stream stream) {
+    if (!delta) return fail(PCAD_ERR_INVALID, "pcad_selective_scan: null delta");
+    if (int rc = scan_args_ok(u, bc, A, Dskip, delta_bias, y, S, L, E)) return rc;
+    if (S == 0 || L == 0) return PCAD_OK;
+    // raw A is scaled by log2(e) when the kernel loads it into registers (the engine passes pre-scaled A)
+    HIP_TRY(launch_scan(u, z, ldz, delta, nullptr, 0, nullptr, 0, bc, A, 1.4426950408889634f, Dskip, delta_bias, y, S, L,
+                        E, reverse != 0, accumulate, dtype, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_selective_scan_dtproj(const void* u, const void* dt_low, int64_t lddt, const void* Wdt, int Rp, const void* z,
+                               int64_t ldz, const float* bc, const float* A, const float* Dskip,
+                               const float* delta_bias, void* y, int S, int L, int E, int reverse, int accumulate,
+                               int dtype, pcad_stream stream) {
+    if (!dt_low || !Wdt) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_dtproj: null dt_low / Wdt");
+    if (Rp <= 0 || Rp % 32 || lddt < Rp || ((uintptr_t)dt_low) % 16 || ((uintptr_t)Wdt) % 16 ||
+        (lddt * (dtype == PCAD_BF16 ? 2 : 4)) % 16)
+        return fail(PCAD_ERR_INVALID, "pcad_selective_scan_dtproj: Rp must be a multiple of 32 (zero padded), rows 16-byte aligned");
+    if (int rc = scan_args_ok(u, bc, A, Dskip, delta_bias, y, S, L, E)) return rc;
+    if (S == 0 || L == 0) return PCAD_OK;
+    HIP_TRY(launch_scan(u, z, ldz, nullptr, dt_low, lddt, Wdt, Rp, bc, A, 1.4426950408889634f, Dskip, delta_bias, y, S, L,
+                        E, reverse != 0, accumulate, dtype, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_gemm_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int N, int K,
+                 int dtype, int out_dtype, pcad_stream stream) {
+    if (!A || !W || !C) return fail(PCAD_ERR_INVALID, "pcad_gemm_nt: null argument");
+    hipError_t err = launch_gemm_nt(A, lda, W, ldw, C, ldc, M, N, K, dtype, out_dtype, false, (hipStream_t)stream);
+    if (err == hipErrorInvalidValue)
+        return fail(PCAD_ERR_INVALID, "pcad_gemm_nt: K*elem must be a multiple of 128 bytes; A/W 16-byte aligned rows");
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_gemm_nt: %s", hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+size_t pcad_gemm_nt_split_scratch_bytes(int64_t M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return align_up((size_t)M * 2 * K * 2) + align_up((size_t)N * 2 * K * 2);       // bf16 [M, 2K] = [hi | lo] of A, bf16 [N, 2K] of W
+}
+
+int pcad_gemm_nt_split(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, int N, int K,
+                       void* scratch, size_t scratch_bytes, pcad_stream stream) {
+    if (!A || !W || !C || !scratch) return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_split: null argument");
+    if (M < 0 || N <= 0 || K <= 0 || K % 64 || lda < K || ldw < K || ldc < N)
+        return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_split: K must be a multiple of 64; lda, ldw >= K; ldc >= N");
+    if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_gemm_nt_split_scratch_bytes(M, N, K))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_gemm_nt_split: scratch must be 256-byte aligned and pcad_gemm_nt_split_scratch_bytes large");
+    if (M == 0) return PCAD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    void* As = scratch;
+    void* Ws = (char*)scratch + align_up((size_t)M * 2 * K * 2);
+    HIP_TRY(launch_split_rows(A, lda, As, M, K, false, false, s));                // [hi | lo]
+    HIP_TRY(launch_pack_split_w(W, PCAD_F32, ldw, Ws, N, K, s));                  // [hi | lo]
+    // 3 K / 64 K-tiles, the cursor wrapping around both operands: a_hi w_hi + a_lo w_hi + a_hi w_lo
+    hipError_t err = launch_gemm_nt(As, 2 * (int64_t)K, Ws, 2 * (int64_t)K, C, ldc, M, N, 3 * K, BF16, F32, false, s, false, K / 64);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_gemm_nt_split: %s", hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_gemm_nt_residual(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, float* res, float* ssq, int64_t M, int N,
+                          int K, int dtype, pcad_stream stream) {
+    if (!A || !W || !res || !ssq || !C) return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: bad dtype");
+    if (M < 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || M * (int64_t)N * 4 >= ((int64_t)1 << 32))
+        return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: M and N must be multiples of 256 and M * N * 4 < 2^32");
+    hipError_t err = launch_gemm_nt_res(A, lda, W, ldw, C, res, ssq, M, N, K, dtype, (hipStream_t)stream, false);
+    if (err == hipErrorInvalidValue)
+        return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: K*elem must be a multiple of 128 bytes; 16-byte aligned rows; tensors < 4 GiB");
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_gemm_nt_residual: %s", hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_gather_rows(const void* src, void* out, int B, int L, int E, const int32_t* positions, int P, int dtype, pcad_stream stream) {
+    if (!src || !out) return fail(PCAD_ERR_INVALID, "pcad_gather_rows: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_gather_rows: bad dtype");
+    if (B < 0 || L <= 0 || E <= 0 || (E * (dtype == PCAD_BF16 ? 2 : 4)) % 16 || P < 1)
+        return fail(PCAD_ERR_INVALID, "pcad_gather_rows: bad shape (E * elem must be a multiple of 16 bytes, P >= 1)");
+    Positions pos;
+    if (int rc = positions_arg("pcad_gather_rows", positions, P, L, &pos)) return rc;
+    if (B == 0) return PCAD_OK;
+    HIP_TRY(launch_gather_rows(src, out, B, L, E, pos, dtype, false, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_layer_rows(const void* src, void* out, int B, int L, int D, const int32_t* positions, int P, const int32_t* pos_per_window,
+                    int assembled, int average, int32_t* status, int dtype, pcad_stream stream) {
+    if (!src || !out) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad dtype");
+    if (B < 0 || L <= 0 || D <= 0 || D % 8) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad B / L / D (D must be a multiple of 8)");
+    if (((uintptr_t)src) % 16 || ((uintptr_t)out) % 16) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: src and out must be 16-byte aligned");
+    if ((positions != nullptr) == (pos_per_window != nullptr)) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: exactly one of positions and pos_per_window");
+    if (P < 1) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad positions (P=%d)", P);
+    Positions pos;
+    if (int rc = positions_arg("pcad_layer_rows", pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, L, &pos)) return rc;
+    if (P > PCAD_MAX_POSITIONS) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad positions (P=%d)", P);
+    if (B == 0) return PCAD_OK;
+    HIP_TRY(launch_layer_rows(src, out, B, L, D, pos, assembled ? nullptr : pos_per_window, P, assembled != 0, P, 1, average != 0, dtype, status,
+                              (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_final_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                    void* hidden_out, float* logits_out, int B, int L, int D, float eps, const int32_t* positions, int P,
+                    const int32_t* pos_per_seq, int h_compact, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                    int res_fragment_layout, pcad_stream stream) {
+    if (!h || !res || !norm_weight || !emb_f32 || !complement) return fail(PCAD_ERR_INVALID, "pcad_final_head: null argument");
+    if (int rc = head_args("pcad_final_head", B, L, D, dtype, res_dtype, res_fragment_layout)) return rc;
+    if (pos_per_seq && (positions || P)) return fail(PCAD_ERR_INVALID, "pcad_final_head: positions and pos_per_seq are exclusive");
+    if (h_compact && (pos_per_seq || P == 0)) return fail(PCAD_ERR_INVALID, "pcad_final_head: h_compact needs a shared list of positions");
+    Positions pos;
+    if (int rc = positions_arg("pcad_final_head", positions, P, L, &pos)) return rc;
+    if (B == 0) return PCAD_OK;
+    HIP_TRY(launch_final_head(h, res, norm_weight, nullptr, emb_f32, complement, hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq,
+                              dtype, res_dtype, (hipStream_t)stream, h_compact != 0, ids, status, res_fragment_layout ? D : 0));
+    return PCAD_OK;
+}
+
+size_t pcad_pooled_head_scratch_bytes(int B, int L, int D, int pooling) {
+    if (B <= 0 || L <= 0 || D <= 0 || pooling < PCAD_POOL_MEAN || pooling > PCAD_POOL_LAST) return 0;
+    return align_up(pool_partial_bytes(B, L, D, pooling));
+}
+
+int pcad_pooled_head(const void* h, const void* res, const float* norm_weight, const float* score_w, int num_labels,
+                     float* pooled_out, float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids,
+                     int32_t* status, int dtype, int res_dtype, int res_fragment_layout, void* scratch, size_t scratch_bytes,
+                     pcad_stream stream) {
+    if (!h || !res || !norm_weight || !scratch) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: null argument");
+    if (!pooled_out && !logits_out) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: no output requested");
+    if (logits_out && (!score_w || num_labels < 1 || num_labels > PCAD_MAX_LABELS))
+        return fail(PCAD_ERR_INVALID, "pcad_pooled_head: logits need score_w and 1 <= num_labels <= %d", PCAD_MAX_LABELS);
+    if (pooling < PCAD_POOL_MEAN || pooling > PCAD_POOL_LAST) return fail(PCAD_ERR_INVALID, "pcad_pooled_head: bad pooling %d", pooling);
+    if (int rc = head_args("pcad_pooled_head", B, L, D, dtype, res_dtype, res_fragment_layout)) return rc;
+    if (B == 0) return PCAD_OK;
+    if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_pooled_head_scratch_bytes(B, L, D, pooling))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_pooled_head: scratch must be 256-byte aligned and pcad_pooled_head_scratch_bytes large");
+    HIP_TRY(launch_pooled_head(h, res, norm_weight, score_w, num_labels, pooled_out, logits_out, B, L, D, eps, pooling, ids, status,
+                               dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+size_t pcad_loss_head_scratch_bytes(int B, int L) {
+    if (B <= 0 || L <= 0) return 0;
+    return align_up(loss_partial_bytes(B, L));
+}
+
+int pcad_loss_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                   const int32_t* labels, const float* loss_weights, int ignore_index, float* sums_out, float* nll_out,
+                   float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                   int res_fragment_layout, void* scratch, size_t scratch_bytes, pcad_stream stream) {
+    if (!h || !res || !norm_weight || !emb_f32 || !complement || !labels || !sums_out || !scratch)
+        return fail(PCAD_ERR_INVALID, "pcad_loss_head: null argument");
+    if (int rc = head_args("pcad_loss_head", B, L, D, dtype, res_dtype, res_fragment_layout)) return rc;
+    if (B == 0) return PCAD_OK;
+    if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_loss_head_scratch_bytes(B, L))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_loss_head: scratch must be 256-byte aligned and pcad_loss_head_scratch_bytes large");
+    HIP_TRY(launch_loss_head(h, res, norm_weight, emb_f32, complement, labels, loss_weights, ignore_index, sums_out, nll_out, logits_out,
+                             B, L, D, eps, ids, status, dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+int pcad_probs_head(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                    const int32_t* cols, float* probs_out, float* logits_out, int B, int L, int D, float eps, const int32_t* positions,
+                    int P, const int32_t* pos_per_window, int h_compact, const int32_t* ids, int32_t* status, int dtype, int res_dtype,
+                    int res_fragment_layout, pcad_stream stream) {
+    if (!h || !res || !norm_weight || !emb_f32 || !complement) return fail(PCAD_ERR_INVALID, "pcad_probs_head: null argument");
+    if (!probs_out && !logits_out) return fail(PCAD_ERR_INVALID, "pcad_probs_head: no output requested");
+    if (((uintptr_t)probs_out) % 16) return fail(PCAD_ERR_INVALID, "pcad_probs_head: probs_out must be 16-byte aligned");
+    if (int rc = head_args("pcad_probs_head", B, L, D, dtype, res_dtype, res_fragment_layout)) return rc;
+    if (positions && pos_per_window) return fail(PCAD_ERR_INVALID, "pcad_probs_head: positions and pos_per_window are exclusive");
+    if (P < 0 || P > PCAD_MAX_POSITIONS || (P > 0 && !positions && !pos_per_window) || (P == 0 && (positions || pos_per_window)))
+        return fail(PCAD_ERR_INVALID, "pcad_probs_head: bad positions (P=%d)", P);
+    if (h_compact && (pos_per_window || P == 0)) return fail(PCAD_ERR_INVALID, "pcad_probs_head: h_compact needs a shared list of positions");
+    ProbCols pc;
+    if (int rc = probs_cols_arg("pcad_probs_head", cols, PCAD_MAX_VOCAB, &pc)) return rc;
+    Positions pos;
+    if (int rc = positions_arg("pcad_probs_head", pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, L, &pos)) return rc;
+    if (B == 0) return PCAD_OK;
+    HIP_TRY(launch_probs_head(h, res, norm_weight, emb_f32, complement, pc, probs_out, logits_out, B, L, D, eps, pos, pos_per_window,
+                              pos_per_window ? P : 0, dtype, res_dtype, (hipStream_t)stream, h_compact != 0, ids, status,
+                              res_fragment_layout ? D : 0));
+    return PCAD_OK;
+}
+
+}  // extern "C"

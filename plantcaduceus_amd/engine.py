@@ -5,6 +5,7 @@ The product path has NO CPU fallback: if the HIP library is missing, `load_libra
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -277,6 +278,35 @@ class Engine:
         base = self._aligned(self._ws)
         return base, self._ws.numel() - (base - self._ws.data_ptr())
 
+    def _check_ids(self, input_ids: torch.Tensor):
+        """The checks every forward makes on its ids [B, L] -> (B, L).  Nothing is enqueued here."""
+        _require_gpu(input_ids, "input_ids")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        if input_ids.device != self.device:
+            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        return input_ids.shape[0], input_ids.shape[1]
+
+    def _ids(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """What follows a forward's argument checks: an earlier forward's pending IndexError, then the int32 copy of the ids."""
+        self._poll_status()
+        return input_ids.to(torch.int32).contiguous()
+
+    @contextlib.contextmanager
+    def _call(self, B: int, L: int):
+        """Around one pcad_forward* call -> (workspace, bytes); then the status word follows it on the stream into pinned host memory."""
+        ws = self._workspace(B, L)
+        try:
+            yield ws
+        finally:
+            self._status_host.copy_(self._status, non_blocking=True)
+            self._status_event.record()
+
+    @staticmethod
+    def _narrow_positions(ppw: torch.Tensor) -> torch.Tensor:
+        """int64 positions are clamped before they are narrowed to int32, so that a huge value cannot alias a valid one."""
+        return ppw.clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+
     def forward(self, input_ids: torch.Tensor, positions=None,
                 want_hidden: bool = False, want_logits: bool = True, all_hidden: bool = False):
         """ids [B, L] (any int dtype, on this device) -> (logits fp32 [B,Q,8] | None, hidden [B,Q,2D] | None[, all]).
@@ -287,14 +317,8 @@ class Engine:
         window - for which the reference raises an index error - are detected by the forward's last kernel and reported
         asynchronously: `check_status()` (which the host loops of this package call where they read results back) raises
         IndexError, and so does the next `forward` call once the flag of an earlier one has arrived."""
-        _require_gpu(input_ids, "input_ids")
-        if input_ids.dim() != 2:
-            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
-        if input_ids.device != self.device:
-            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
-        self._poll_status()
-        ids = input_ids.to(torch.int32).contiguous()
-        B, L = ids.shape
+        B, L = self._check_ids(input_ids)
+        ids = self._ids(input_ids)
         D = self.config.d_model
         per_seq = None
         if torch.is_tensor(positions):
@@ -309,10 +333,9 @@ class Engine:
             hidden = torch.empty((B, Q, 2 * D), dtype=self.dtype, device=self.device) if want_hidden else None
             if B == 0:
                 return (logits, hidden, None) if all_hidden else (logits, hidden)
-            ws, ws_bytes = self._workspace(B, L)
             lp = logits.data_ptr() if logits is not None else None
             hp = hidden.data_ptr() if hidden is not None else None
-            try:
+            with self._call(B, L) as (ws, ws_bytes):
                 if all_hidden:
                     if positions is not None or per_seq is not None:
                         raise ValueError("all_hidden requires positions=None")
@@ -327,10 +350,6 @@ class Engine:
                 pos_arr = (C.c_int32 * P)(*[int(p) for p in positions]) if P else None
                 _check(self.lib.pcad_forward(self._h, ids.data_ptr(), B, L, pos_arr, P, hp, lp, ws, ws_bytes,
                                              _stream_ptr()), "pcad_forward")
-            finally:
-                # the status word follows the forward on the stream into pinned host memory; nobody waits for it here
-                self._status_host.copy_(self._status, non_blocking=True)
-                self._status_event.record()
         return logits, hidden
 
     def forward_pooled(self, input_ids: torch.Tensor, pooling: str, score_w: torch.Tensor, want_pooled: bool = False):
@@ -339,19 +358,13 @@ class Engine:
         pooling: "mean" / "max" / "first" / "last"; score_w: the `score` Linear's weight [NL, D] (any float dtype, any device),
         rounded to the model dtype here as the reference's `nn.Linear` in that dtype holds it.  Chunking, workspace and
         asynchronous input validation are those of `forward`."""
-        _require_gpu(input_ids, "input_ids")
-        if input_ids.dim() != 2:
-            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
-        if input_ids.device != self.device:
-            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        B, L = self._check_ids(input_ids)
         if pooling not in POOLING:
             raise ValueError(f"pooling must be one of {sorted(POOLING)}, got {pooling!r}")
         D = self.config.d_model
         if score_w.dim() != 2 or score_w.shape[1] != D or not 1 <= score_w.shape[0] <= MAX_LABELS:
             raise ValueError(f"score weight must be [num_labels (1..{MAX_LABELS}), {D}], got {tuple(score_w.shape)}")
-        self._poll_status()
-        ids = input_ids.to(torch.int32).contiguous()
-        B, L = ids.shape
+        ids = self._ids(input_ids)
         NL = int(score_w.shape[0])
         with torch.cuda.device(self.device):
             w = score_w.detach().to(self.device).to(self.dtype).float().contiguous()
@@ -359,14 +372,10 @@ class Engine:
             pooled = torch.empty((B, 2, D), dtype=torch.float32, device=self.device) if want_pooled else None
             if B == 0:
                 return (logits, pooled) if want_pooled else logits
-            ws, ws_bytes = self._workspace(B, L)
-            try:
+            with self._call(B, L) as (ws, ws_bytes):
                 _check(self.lib.pcad_forward_pooled(self._h, ids.data_ptr(), B, L, POOLING[pooling], w.data_ptr(), NL,
                                                     pooled.data_ptr() if pooled is not None else None, logits.data_ptr(),
                                                     ws, ws_bytes, _stream_ptr()), "pcad_forward_pooled")
-            finally:
-                self._status_host.copy_(self._status, non_blocking=True)
-                self._status_event.record()
         return (logits, pooled) if want_pooled else logits
 
     def forward_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, loss_weights: Optional[torch.Tensor] = None,
@@ -376,20 +385,14 @@ class Engine:
         sum w, labelled positions, labelled positions whose arg-max logit is the label) of window b; a label equal to
         ignore_index or negative is ignored, any other label outside the vocabulary is reported like a bad token id
         (`check_status`).  Chunking, workspace and asynchronous input validation are those of `forward`."""
-        _require_gpu(input_ids, "input_ids")
-        if input_ids.dim() != 2:
-            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
-        if input_ids.device != self.device:
-            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        B, L = self._check_ids(input_ids)
         if not torch.is_tensor(labels) or tuple(labels.shape) != tuple(input_ids.shape) or labels.is_floating_point():
             raise ValueError(f"labels must be an integer tensor of input_ids' shape {tuple(input_ids.shape)}")
         if loss_weights is not None and (not torch.is_tensor(loss_weights) or tuple(loss_weights.shape) != tuple(input_ids.shape)):
             raise ValueError(f"loss_weights must be a tensor of input_ids' shape {tuple(input_ids.shape)}")
         if not -2 ** 31 <= int(ignore_index) < 2 ** 31:
             raise ValueError("ignore_index must fit in 32 bits")
-        self._poll_status()
-        ids = input_ids.to(torch.int32).contiguous()
-        B, L = ids.shape
+        ids = self._ids(input_ids)
         with torch.cuda.device(self.device):
             # int64 labels are clamped before they are narrowed, so that a huge value cannot alias a valid one
             lab = labels.to(self.device).clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
@@ -399,16 +402,11 @@ class Engine:
             logits = torch.empty((B, L, 8), dtype=torch.float32, device=self.device) if want_logits else None
             if B == 0:
                 return sums, nll, logits
-            ws, ws_bytes = self._workspace(B, L)
-            try:
+            with self._call(B, L) as (ws, ws_bytes):
                 _check(self.lib.pcad_forward_loss(self._h, ids.data_ptr(), lab.data_ptr(), w.data_ptr() if w is not None else None,
-                                                  int(ignore_index), B, L, sums.data_ptr(),
-                                                  nll.data_ptr() if nll is not None else None,
+                                                  int(ignore_index), B, L, sums.data_ptr(), nll.data_ptr() if nll is not None else None,
                                                   logits.data_ptr() if logits is not None else None, ws, ws_bytes, _stream_ptr()),
                        "pcad_forward_loss")
-            finally:
-                self._status_host.copy_(self._status, non_blocking=True)
-                self._status_event.record()
         return sums, nll, logits
 
     def forward_probs(self, input_ids: torch.Tensor, cols, positions=None, positions_per_window: Optional[torch.Tensor] = None,
@@ -419,27 +417,19 @@ class Engine:
         positions_per_window: an integer tensor [B, P] (1 <= P <= 16) on this device, window b's own positions - a value outside
         [0, L) is clamped and reported like a bad token id (`check_status`).  At most one of the two.  Chunking, workspace and
         asynchronous input validation are those of `forward`."""
-        _require_gpu(input_ids, "input_ids")
-        if input_ids.dim() != 2:
-            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
-        if input_ids.device != self.device:
-            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
+        B, L = self._check_ids(input_ids)
         cols = [int(c) for c in cols]
         if len(cols) != 4:
             raise ValueError(f"cols must name four vocabulary columns, got {cols}")
         if positions is not None and positions_per_window is not None:
             raise ValueError("positions and positions_per_window are exclusive")
-        self._poll_status()
-        ids = input_ids.to(torch.int32).contiguous()
-        B, L = ids.shape
-        ppw = None
-        if positions_per_window is not None:
-            ppw = positions_per_window
+        ids = self._ids(input_ids)
+        ppw = positions_per_window
+        if ppw is not None:
             if (not torch.is_tensor(ppw) or ppw.is_floating_point() or ppw.dim() != 2 or ppw.shape[0] != B
                     or not 1 <= ppw.shape[1] <= MAX_POSITIONS or ppw.device != self.device):
                 raise ValueError(f"positions_per_window must be an integer tensor [B, 1..{MAX_POSITIONS}] on the engine's device")
-            # int64 positions are clamped before they are narrowed, so that a huge value cannot alias a valid one
-            ppw = ppw.clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+            ppw = self._narrow_positions(ppw)
             P = int(ppw.shape[1])
         else:
             P = 0 if positions is None else len(positions)
@@ -449,16 +439,12 @@ class Engine:
             logits = torch.empty((B, Q, 8), dtype=torch.float32, device=self.device) if want_logits else None
             if B == 0:
                 return (probs, logits) if want_logits else probs
-            ws, ws_bytes = self._workspace(B, L)
             pos_arr = (C.c_int32 * P)(*[int(p) for p in positions]) if (P and ppw is None) else None
-            try:
+            with self._call(B, L) as (ws, ws_bytes):
                 _check(self.lib.pcad_forward_probs(self._h, ids.data_ptr(), B, L, pos_arr, P, ppw.data_ptr() if ppw is not None else None,
                                                    (C.c_int32 * 4)(*cols), probs.data_ptr(),
                                                    logits.data_ptr() if logits is not None else None, ws, ws_bytes, _stream_ptr()),
                        "pcad_forward_probs")
-            finally:
-                self._status_host.copy_(self._status, non_blocking=True)
-                self._status_event.record()
         return (probs, logits) if want_logits else probs
 
     def forward_layers(self, input_ids: torch.Tensor, layers=None, positions=None, positions_per_window: Optional[torch.Tensor] = None,
@@ -471,39 +457,27 @@ class Engine:
         token id, `check_status`).  Only the last level asked for: `forward`'s own walk; any level below it: the unfolded walk of
         `forward(all_hidden=True)`, whose levels the rows are bit-equal to.  Chunking, workspace and asynchronous input validation
         are those of `forward`."""
-        _require_gpu(input_ids, "input_ids")
-        if input_ids.dim() != 2:
-            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
-        if input_ids.device != self.device:
-            raise RuntimeError(f"input_ids on {input_ids.device}, engine on {self.device}")
-        lv, P = check_layer_request(layers, self.config.n_layer, positions, positions_per_window, int(input_ids.shape[0]))
-        self._poll_status()
-        ids = input_ids.to(torch.int32).contiguous()
-        B, L = ids.shape
-        ppw = None
-        if positions_per_window is not None:
-            if positions_per_window.device != self.device:
+        B, L = self._check_ids(input_ids)
+        lv, P = check_layer_request(layers, self.config.n_layer, positions, positions_per_window, B)
+        ids = self._ids(input_ids)
+        ppw = positions_per_window
+        if ppw is not None:
+            if ppw.device != self.device:
                 raise ValueError("positions_per_window must be on the engine's device")
-            # int64 positions are clamped before they are narrowed, so that a huge value cannot alias a valid one
-            ppw = positions_per_window.clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
-        else:
-            positions = [int(p) for p in positions]
+            ppw = self._narrow_positions(ppw)
+        positions = None if positions is None else [int(p) for p in positions]
         D = self.config.d_model
         NL = len(lv) if lv is not None else self.config.n_layer + 1
         with torch.cuda.device(self.device):
             out = torch.empty((NL, B, P, D if average else 2 * D), dtype=torch.float32 if average else self.dtype, device=self.device)
             if B == 0:
                 return out
-            ws, ws_bytes = self._workspace(B, L)
             pos_arr = (C.c_int32 * P)(*positions) if ppw is None else None
             lay_arr = (C.c_int32 * NL)(*lv) if lv is not None else None
-            try:
+            with self._call(B, L) as (ws, ws_bytes):
                 _check(self.lib.pcad_forward_layers(self._h, ids.data_ptr(), B, L, pos_arr, P, ppw.data_ptr() if ppw is not None else None,
                                                     lay_arr, NL if lv is not None else 0, int(bool(average)), out.data_ptr(), ws, ws_bytes,
                                                     _stream_ptr()), "pcad_forward_layers")
-            finally:
-                self._status_host.copy_(self._status, non_blocking=True)
-                self._status_event.record()
         return out
 
     # -- asynchronous input validation (include/pcad.h pcad_set_status_buffer) ----------------------------------------
