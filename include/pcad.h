@@ -311,9 +311,14 @@ int    pcad_forward_probs(pcad_handle h, const int32_t* ids, int B, int L, const
  *               extract_embeddings forms from the plain row ((e[:D] + flip(e[D:])) / 2 on fp32), bit for bit.
  * Layer walk.  Only level n_layer requested: pcad_forward's walk for the shared list (norm fold and last-layer shortcut as that call
  * chooses them; the plain output is bit-equal to its hidden_out) and the full last layer for per-window lists (P == 1:
- * pcad_forward_at's walk and hidden_out).  Any level below n_layer requested: pcad_forward_all_hidden's walk (no norm fold, no
- * shortcut), every level gathered right after it is produced: level k is bit-equal to all_hidden[k][b, p, :] (hidden_out[b, p, :] for
- * k == n_layer) of that call on the same batch under the same options.
+ * pcad_forward_at's walk and hidden_out).  Any level below n_layer requested: the unfolded walk of pcad_forward_all_hidden (no norm
+ * fold), every level gathered right after it is produced, and only as deep as the highest requested level K: with K == n_layer all
+ * blocks, the final norm and the head run as in that call; with K < n_layer blocks 0 .. K - 1 run and nothing after them (K == 0: no
+ * block), the token ids being checked by a small kernel of their own.  For a shared list block K - 1 of such a call is shortened
+ * as "last_layer_shortcut" shortens pcad_forward's last layer (scans stopped after the furthest evaluated row, out_proj on the
+ * 2 B P gathered rows; "last_layer_shortcut" 0 turns it off; not taken where that block runs as a pair walk); per-window lists keep
+ * the block whole.  In every case level k is bit-equal to all_hidden[k][b, p, :] (hidden_out[b, p, :] for k == n_layer) of a
+ * pcad_forward_all_hidden call on the same batch under the same options.
  * pcad_workspace_bytes is the forward's own; nothing is allocated and nothing synchronises.  Token ids outside the vocabulary are
  * reported through pcad_set_status_buffer as by pcad_forward.
  * Replaces: model(input_ids=ids, output_hidden_states=True).hidden_states[k][:, p, :] and the strand averaging of

@@ -31,7 +31,8 @@ struct ForwardRequest {
     struct {       // pcad_forward_layers: chosen levels of hidden_states at the evaluated positions (layers.hip) in place of the LM head's outputs
         const int32_t* layers;         // host [NL], strictly increasing levels in [0, n_layer], or nullptr: all n_layer + 1
         int NL;
-        bool inter, average;           // inter: a level below n_layer is requested: the unfolded full walk of pcad_forward_all_hidden
+        bool inter, average;           // inter: a level below n_layer is requested: the unfolded walk of pcad_forward_all_hidden, up to block `top`
+        int top;                       // the highest requested level
         void* out;                     // [NL, B, P, 2D] model dtype, or (average) [NL, B, P, D] fp32
     } lay = {};
 };
@@ -41,7 +42,8 @@ struct ForwardPlan {
     int chunk, nchunks;     // windows per pass through the layer stack (api.hip chunk_for); passes
     bool fold, sp, untied;  // norm-folded layer form (every chunk folds or none does); split-bf16 GEMMs; per-direction in_proj / out_proj
     bool lay_inter, strict; // pcad_forward_layers with a level below n_layer; each direction's own out_proj, rounded, summed and rounded
-    int walk_len;           // last-layer shortcut: steps of the last layer's walks (0: the full layer)
+    int depth;              // blocks to run: n_layer, or - pcad_forward_layers whose highest level lies below it - that level (0: none)
+    int walk_len;           // last-layer shortcut: steps of the walks of the last EXECUTED block, depth - 1 (0: the full block)
     SmallForms forms;       // from the strands of the whole call; the same function sizes their scratch (api.hip carve_workspace)
     bool tab0;              // layer 0's in_proj of the folded form as a table look-up
     int Q;                  // evaluated positions per window
@@ -94,20 +96,28 @@ ForwardPlan plan_forward(const pcad_engine* e, const ForwardRequest& rq, const P
     // strict reference order ("reference_order" 2; never with norm_fold): the reverse direction's gated output goes to its own
     // tensor (xc[0]: the forward scan, its only reader, has run) and each direction gets its own tied out_proj
     pl.strict = (e->ref_order == 2 || pl.untied) && !pl.fold;
+    // Truncated walk (pcad_forward_layers whose highest requested level K lies below n_layer): nothing above block K - 1 is read, so
+    // the walk stops there - no norm_f, no head (the token ids are checked by ids_check_kernel instead).  K == 0 runs no block.
+    pl.forms = small_forms(e, B, L);
+    pl.depth = pl.lay_inter && rq.lay.top < e->nl ? rq.lay.top : e->nl;
+    const bool truncated = pl.depth < e->nl;
     // Last-layer shortcut (reference callers read ONE position: src/zero_shot_score.py:117,
     // src/train_XGBoost.py:105): with a shared list of P evaluated positions only rows p_q of the forward strands and L - 1 - p_q of
     // the reverse-complement strands of the LAST mixer's output are consumed.  The left-to-right scan stops after the furthest of
     // them, the right-to-left scan likewise (walk_len steps each), and the tied out_proj runs on the 2B * P gathered rows.  Same
     // arithmetic on the consumed rows (sequential walks, row-independent GEMM): results are bit-identical to the full layer.
+    // In a truncated walk the shortened block is K - 1, the last one executed, and level K is gathered from its compact rows.  That
+    // block must compute what pcad_forward_all_hidden computes on it, whose rows the level is bit-equal to: where that is a pair walk
+    // (it rounds the gate-once sum elsewhere than plain walks do) the block stays whole.
     pl.walk_len = 0;
-    if (e->shortcut && P > 0 && !rq.pos_per_window && !rq.all_hidden && !pl.lay_inter && (int64_t)P * E <= (int64_t)L * D) {
+    if (e->shortcut && P > 0 && !rq.pos_per_window && !rq.all_hidden && (int64_t)P * E <= (int64_t)L * D &&
+        (truncated ? pl.depth > 0 && !(pl.forms.pair && !pl.strict) : !pl.lay_inter)) {
         int pmin = pos.p[0], pmax = pos.p[0];
         for (int i = 1; i < P; ++i) { pmin = pos.p[i] < pmin ? pos.p[i] : pmin; pmax = pos.p[i] > pmax ? pos.p[i] : pmax; }
         const int need = (pmax + 1 > L - pmin) ? pmax + 1 : L - pmin;      // forward strands need row pmax, rc strands row L - 1 - pmin
         pl.walk_len = (need + 7) / 8 * 8;                                // whole 8-step groups (two prefetch chunks)
         if (pl.walk_len > L) pl.walk_len = L;
     }
-    pl.forms = small_forms(e, B, L);
     static const bool tab0 = dev_env("PCAD_NO_TAB0") == nullptr;     // layer 0's in_proj as a table look-up (in_proj_conv); PCAD_DEV=1 A/B switch
     pl.tab0 = tab0;
     return pl;
@@ -140,15 +150,18 @@ struct Walk {
     bool convx_fused(int64_t rows) const { return !pl.untied && e->convx && (rows + 16) * E * (int64_t)esz < ((int64_t)1 << 32); }
     // split-bf16 dt_proj inside the scan ("f32_gemm_split"): the fused conv + x_proj kernel wrote dt_low as bf16 [rows, 3 Rp]
     bool dts(int64_t rows) const { return pl.sp && convx_fused(rows); }
-    bool last_short(int li) const { return pl.walk_len > 0 && li + 1 == e->nl; }
+    // the last EXECUTED block (n_layer - 1, or depth - 1 of a truncated walk) with its walks shortened and out_proj on the gathered rows
+    bool last_short(int li) const { return pl.walk_len > 0 && li + 1 == pl.depth; }
+    bool truncated() const { return pl.depth < e->nl; }
     // "f32_gemm_split": out_proj's [hi | lo] operand is written by the gating (reverse) scan itself where it can (whole walk,
     // unsegmented, L % 8 == 0, one out_proj for both directions), instead of fp32 y + a conversion pass
     bool ys_from_scan(int li) const { return pl.sp && !pl.strict && !last_short(li) && L % 8 == 0 && e->blocked && e->xzsplit && pl.forms.G == 1; }
     // Pair walks (kernels.hpp scan_pair_wanted: few waves per launch - long windows in small batches): both directions in one
     // launch, half a strand each, twice; chosen from the strands of the whole call like the segmented form
     // (never the LAST layer: with a list of positions its walks are shortened plain walks - "last_layer_shortcut" - and the full
-    // layer must stay bit-identical to them on the evaluated rows)
-    bool pair(int64_t rows, int li) const { return pl.forms.pair && !pl.strict && li + 1 < e->nl && convx_fused(rows) && reps(PCAD_K_SCAN) == 1; }
+    // layer must stay bit-identical to them on the evaluated rows; block depth - 1 of a truncated walk is shortened only where it
+    // would not be a pair walk - plan_forward - and otherwise runs pcad_forward_all_hidden's form of that block, pair walk included)
+    bool pair(int64_t rows, int li) const { return pl.forms.pair && !pl.strict && li + 1 < e->nl && !last_short(li) && convx_fused(rows) && reps(PCAD_K_SCAN) == 1; }
     void* y_rev(const Lane& c) const { return pl.strict ? c.w.xc[0] : c.w.y; }
     const int32_t* ids_of(const Lane& c) const { return rq.ids + (int64_t)c.b0 * L; }
     const int32_t* ppw_of(const Lane& c) const { return rq.pos_per_window ? rq.pos_per_window + (size_t)c.b0 * rq.Pw : nullptr; }      // its rows of the [B, Pw] list
@@ -177,14 +190,15 @@ struct Walk {
     }
     // hidden_states[level] (now in c.w.h as plain rows) -> pcad_forward_all_hidden's tensor / pcad_forward_layers' rows at the
     // evaluated positions, whichever the call asked for
-    int emit_level(Lane& c, int level) const {
+    // compact: c.w.h holds only the [2 Bc, P, D] rows the shortcut's gather + small GEMM left (the shortened block of a truncated walk)
+    int emit_level(Lane& c, int level, bool compact = false) const {
         if (rq.all_hidden) {
             char* dst = (char*)rq.all_hidden + ((size_t)level * B * L * 2 * D + (size_t)c.b0 * L * 2 * D) * esz;
             HIP_TRY(launch_assemble_hidden(c.w.h, dst, c.Bc, L, D, dt, s));
         }
         const int slot = lay_slot(level);
         if (slot >= 0)
-            HIP_TRY(launch_layer_rows(c.w.h, lay_dst(slot, c.b0), c.Bc, L, D, pos, ppw_of(c), layP, false, 0, 0, rq.lay.average, dt, e->status, s));
+            HIP_TRY(launch_layer_rows(c.w.h, lay_dst(slot, c.b0), c.Bc, L, D, pos, ppw_of(c), layP, false, 0, 0, rq.lay.average, dt, e->status, s, compact));
         return PCAD_OK;
     }
     // A head's scratch goes to the buffers that are dead once the last out_proj has run (everything carved after h: xz, zb, xc,
@@ -193,6 +207,11 @@ struct Walk {
         const size_t avail = (size_t)((char*)rq.workspace + c.w.bytes - (char*)c.w.xz);
         if (need > avail) return fail(PCAD_ERR_WORKSPACE, "%s: the %s (%zu bytes) do not fit the dead buffers (%zu)", who, what, shown ? shown : need, avail);
         return PCAD_OK;
+    }
+    int level0(Lane& c) const {        // hidden_states[0] = RCPSEmbedding output, where asked for (never in the folded form): before block 0, if any
+        if (pl.fold || !(rq.all_hidden || lay_slot(0) >= 0)) return PCAD_OK;
+        HIP_TRY(launch_embed_only(ids_of(c), e->emb, e->comp, c.w.h, c.Bc, L, D, dt, s));
+        return emit_level(c, 0);
     }
     int add_norm(Lane& c, int li) const {        // residual add + norm (layer 0: RCPS embedding + norm)
         const LayerWeights& W = e->layers[li];
@@ -205,10 +224,6 @@ struct Walk {
             return PCAD_OK;     // later layers: the previous out_proj's epilogue already produced res, round(res) and rstd
         }
         if (li == 0) {
-            if (rq.all_hidden || lay_slot(0) >= 0) {   // hidden_states[0] = RCPSEmbedding output
-                HIP_TRY(launch_embed_only(ids_of(c), e->emb, e->comp, c.w.h, c.Bc, L, D, dt, s));
-                if (int rc = emit_level(c, 0)) return rc;
-            }
             ProfScope ps(e, PCAD_K_NORM, s);
             HIP_TRY(launch_embed_rmsnorm(ids_of(c), e->emb, e->comp, W.norm_w, c.w.u, c.w.res, c.Bc, L, D, eps, dt, rdt, s, nullptr, 0, pl.sp));
         } else {
@@ -312,7 +327,7 @@ struct Walk {
             HIP_TRY(launch_gather_rows(y_rev(c), c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
             HIP_TRY(out_proj(c, li, c.w.u, (int64_t)S * P, c.w.xz, 1, false));
             HIP_TRY(launch_add_round(c.w.h, c.w.xz, (int64_t)S * P * D, dt, s));
-            return PCAD_OK;
+            return truncated() ? emit_level(c, li + 1, true) : PCAD_OK;
         }
         { ProfScope ps(e, PCAD_K_GEMM_OUT, s);
         HIP_TRY(out_proj(c, li, c.w.y, rows, c.w.h, 0, e->blocked)); }
@@ -327,7 +342,7 @@ struct Walk {
         HIP_TRY(launch_gather_rows(c.w.y, c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
         // split: the same split-bf16 product as the full-size out_proj (same operand values, same K order: bit-identical rows)
         HIP_TRY(out_proj(c, li, c.w.u, (int64_t)2 * c.Bc * P, c.w.h, 0, false));
-        return PCAD_OK;
+        return truncated() ? emit_level(c, li + 1, true) : PCAD_OK;      // a truncated walk: level `depth` from the compact rows
     }
     int out_proj_folded(Lane& c, int li) const {     // out_proj + residual add + the next block's norm statistics in one launch
         const LayerWeights& W = e->layers[li];
@@ -416,7 +431,14 @@ struct Walk {
         }
         return PCAD_OK;
     }
+    // A truncated walk runs neither norm_f nor the head; what the head would have reported about the chunk's token ids is reported here
+    int ids_check(Lane& c) const {
+        ProfScope ps(e, PCAD_K_HEAD, s);
+        HIP_TRY(launch_ids_check(ids_of(c), (int64_t)c.Bc * L, e->status, s));
+        return PCAD_OK;
+    }
     int head(Lane& c) const {
+        if (truncated()) return ids_check(c);
         return rq.head == Head::pooled ? head_pooled(c) : rq.head == Head::loss ? head_loss(c) : rq.head == Head::probs ? head_probs(c)
                : rq.head == Head::layers ? head_layers(c) : head_lm(c);
     }
@@ -427,7 +449,8 @@ struct Walk {
             c.b0 = ck * pl.chunk;
             c.Bc = (B - c.b0) < pl.chunk ? (B - c.b0) : pl.chunk;
             c.w = carve_workspace(e, rq.workspace, c.Bc, L, B);
-            for (int li = 0; li < e->nl; ++li) {
+            if (int rc = level0(c)) return rc;
+            for (int li = 0; li < pl.depth; ++li) {
                 if (int rc = add_norm(c, li)) return rc;
                 if (int rc = in_proj_conv(c, li)) return rc;
                 if (int rc = scans(c, li)) return rc;
@@ -543,9 +566,11 @@ int pcad_forward_layers(pcad_handle h, const int32_t* ids, int B, int L, const i
     ForwardRequest rq;
     rq.head = Head::layers; rq.ids = ids; rq.B = B; rq.L = L; rq.workspace = workspace; rq.ws_bytes = workspace_bytes; rq.stream = stream;
     rq.lay.layers = layers; rq.lay.NL = layers ? NL : nl + 1; rq.lay.inter = !layers || layers[0] < nl;
+    rq.lay.top = layers ? layers[NL - 1] : nl;
     rq.lay.average = average != 0; rq.lay.out = out;
     // the last level alone: pcad_forward's walk for a shared list (norm fold and last-layer shortcut as that call chooses them), the
-    // full last layer for per-window lists (P == 1: pcad_forward_at's walk); any level below it: pcad_forward_all_hidden's walk
+    // full last layer for per-window lists (P == 1: pcad_forward_at's walk); any level below it: pcad_forward_all_hidden's walk, which
+    // stops after block `top` - 1 when `top` < n_layer (plan_forward: depth)
     if (pos_per_window) { rq.pos_per_window = pos_per_window; rq.Pw = P; } else { rq.positions = positions; rq.P = P; }
     return forward_impl(h, rq);
 }

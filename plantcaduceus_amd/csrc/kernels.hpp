@@ -84,7 +84,10 @@ hipError_t launch_probs_head(const void* h, const void* res, const float* w, con
 // launch_assemble_hidden's rows (b, p_q), or - average - fp32 [B, P, D] = (fwd + rc) * 0.5 in straight channel order.  Positions: the
 // shared list `pos` (pos.n == P) or pos_per_window (device [B, P]; values outside [0, L) are clamped and set status bit 2).
 hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* pos_per_window, int P,
-                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s);
+                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s,
+                             bool compact = false);     // compact (shared list, not assembled): src = launch_gather_rows' [2B, P, D] rows of h
+// token ids outside [0, 8) among ids[0, n) (any 4-byte alignment) set status bit 1, as the heads' own check does; status == nullptr: no launch
+hipError_t launch_ids_check(const int32_t* ids, int64_t n, int32_t* status, hipStream_t s);
 // dst [P, B] = the columns of src [B, P] (device int32): slot q's positions of every window as one contiguous list
 hipError_t launch_position_columns(const int32_t* src, int32_t* dst, int B, int P, hipStream_t s);
 // hidden_states[i] (block input = previous mixer output / embedding) assembled in RCPS layout.

@@ -2,7 +2,9 @@
 // tuple that a caller reads, gathered from the 2B-strand activation tensor right after the level is produced.
 //
 //   source        plain rows [2B * L, D]: the mixer output h of a layer, or the RCPS embedding (level 0);
-//                 or (assembled) rows [.., 2D] that final_head_kernel already wrote in the reference's layout (the last level)
+//                 or (assembled) rows [.., 2D] that final_head_kernel already wrote in the reference's layout (the last level);
+//                 or (compact) the [2B, P, D] plain rows that launch_gather_rows + the small out_proj leave of a shortened block:
+//                 strand b slot q = row p_q, strand B + b slot q = row L - 1 - p_q (the last executed block of a truncated walk)
 //   rows read     (window b, slot q, position p): strand b row p ("fwd") and strand B + b row L - 1 - p ("rc")
 //   plain form    model dtype [B, P, 2D]: [0, D) = fwd, [D, 2D) = rc with channels reversed - assemble_hidden_kernel's row (b, p), bit for bit
 //   averaged form fp32 [B, P, D]: (float(fwd[c]) + float(rc[c])) * 0.5f - one fp32 add and one exact multiply: the value
@@ -43,8 +45,9 @@ template <> struct Piece<bf16_t> {
     }
 };
 
-// ASM: src holds assembled rows of 2D elements, row of (b, q) at index b * sb + q * sq; else plain rows [2B * L, D]
-template <typename T, bool AVG, bool ASM>
+// ASM: src holds assembled rows of 2D elements, row of (b, q) at index b * sb + q * sq; CMP (never with ASM): compact plain rows
+// [2B, P, D], the two rows of (b, q) at indices b * P + q and (B + b) * P + q; else plain rows [2B * L, D]
+template <typename T, bool AVG, bool ASM, bool CMP>
 __global__ __launch_bounds__(64 * LAYERS_WAVES) void layer_rows_kernel(const T* __restrict__ src, void* __restrict__ out, int B, int L, int D,
                                                                        Positions pos, const int32_t* __restrict__ pos_per_window, int P,
                                                                        int64_t sb, int64_t sq, int32_t* __restrict__ status) {
@@ -57,6 +60,9 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void layer_rows_kernel(const T* 
     if constexpr (ASM) {
         fwd = src + (b * sb + q * sq) * 2 * D;
         rc = fwd + D;
+    } else if constexpr (CMP) {
+        fwd = src + item * D;                            // launch_gather_rows' order: (strand * P + q), the same slot in both strands
+        rc = src + ((int64_t)B * P + item) * D;
     } else {
         int p = 0;
         if (pos_per_window) {
@@ -102,19 +108,20 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void layer_rows_kernel(const T* 
 
 template <typename T>
 static hipError_t launch_layer_rows_t(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* ppw, int P,
-                                      bool assembled, int64_t sb, int64_t sq, bool average, int32_t* status, hipStream_t s) {
+                                      bool assembled, int64_t sb, int64_t sq, bool average, int32_t* status, hipStream_t s, bool compact) {
     const int64_t items = (int64_t)B * P;
     const dim3 grid((unsigned)((items + LAYERS_WAVES - 1) / LAYERS_WAVES)), blk(64 * LAYERS_WAVES);
-#define PCAD_LAYER_ROWS(AVG, ASM) \
-    hipLaunchKernelGGL((layer_rows_kernel<T, AVG, ASM>), grid, blk, 0, s, (const T*)src, out, B, L, D, pos, ppw, P, sb, sq, status)
-    if (average) { if (assembled) PCAD_LAYER_ROWS(true, true); else PCAD_LAYER_ROWS(true, false); }
-    else { if (assembled) PCAD_LAYER_ROWS(false, true); else PCAD_LAYER_ROWS(false, false); }
+#define PCAD_LAYER_ROWS(AVG, ASM, CMP) \
+    hipLaunchKernelGGL((layer_rows_kernel<T, AVG, ASM, CMP>), grid, blk, 0, s, (const T*)src, out, B, L, D, pos, ppw, P, sb, sq, status)
+    if (average) { if (assembled) PCAD_LAYER_ROWS(true, true, false); else if (compact) PCAD_LAYER_ROWS(true, false, true); else PCAD_LAYER_ROWS(true, false, false); }
+    else { if (assembled) PCAD_LAYER_ROWS(false, true, false); else if (compact) PCAD_LAYER_ROWS(false, false, true); else PCAD_LAYER_ROWS(false, false, false); }
 #undef PCAD_LAYER_ROWS
     return hipGetLastError();
 }
 
 hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* pos_per_window, int P,
-                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s) {
+                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s, bool compact) {
+    if (compact && (assembled || pos_per_window)) return hipErrorInvalidValue;        // the gathered rows exist for a shared list only
     if (D <= 0 || D % 8 || L <= 0 || P < 1 || P > 16) return hipErrorInvalidValue;
     if (!assembled && !pos_per_window && pos.n != P) return hipErrorInvalidValue;
     if (!assembled && !pos_per_window)
@@ -123,8 +130,8 @@ hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Po
     if (((uintptr_t)src) % 16 || ((uintptr_t)out) % 16) return hipErrorInvalidValue;      // 16-byte pieces
     if (B <= 0) return hipSuccess;
     if (((int64_t)B * P + LAYERS_WAVES - 1) / LAYERS_WAVES > 0x7fffffff) return hipErrorInvalidValue;
-    if (dt == BF16) return launch_layer_rows_t<bf16_t>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s);
-    if (dt == F32) return launch_layer_rows_t<float>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s);
+    if (dt == BF16) return launch_layer_rows_t<bf16_t>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s, compact);
+    if (dt == F32) return launch_layer_rows_t<float>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s, compact);
     return hipErrorInvalidValue;
 }
 
@@ -140,6 +147,38 @@ hipError_t launch_position_columns(const int32_t* src, int32_t* dst, int B, int 
     if (B <= 0 || P <= 0) return hipSuccess;
     const int64_t n = (int64_t)B * P;
     hipLaunchKernelGGL(position_columns_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, B, P);
+    return hipGetLastError();
+}
+
+// Token-id validation of a truncated walk (pcad_forward_layers whose highest level lies below n_layer: no head runs, and the head is
+// what reports ids outside [0, 8) otherwise).  n ids from `ids`, which need not be 16-byte aligned (a chunk starts at window b0, i.e.
+// b0 * L ids in): `head` ids up to the first aligned one and the n - head - 4 nv behind the last whole piece are read singly by the
+// first lanes of the grid, the nv pieces between them as 16-byte loads in a grid-stride loop.  A wave that saw a bad id issues ONE
+// atomicOr; nothing else is written.
+constexpr int IDS_STATUS_BAD_TOKEN_BIT = 1;          // = pcad.h PCAD_STATUS_BAD_TOKEN
+__global__ __launch_bounds__(256) void ids_check_kernel(const int32_t* __restrict__ ids, int64_t n, int head, int64_t nv, int32_t* __restrict__ status) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const int tail = (int)(n - head - 4 * nv);       // < 4
+    bool bad = false;
+    if (g < head) bad |= (unsigned)ids[g] > 7u;
+    if (g < tail) bad |= (unsigned)ids[head + 4 * nv + g] > 7u;
+    const u32x4* v = reinterpret_cast<const u32x4*>(ids + head);
+    for (int64_t i = g; i < nv; i += stride) {
+        const u32x4 t = v[i];
+        bad |= (t[0] | t[1] | t[2] | t[3]) > 7u;     // unsigned: a negative id has its top bit set
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(status, IDS_STATUS_BAD_TOKEN_BIT);
+}
+
+hipError_t launch_ids_check(const int32_t* ids, int64_t n, int32_t* status, hipStream_t s) {
+    if (!status || n <= 0) return hipSuccess;        // no status word bound: nothing to report to
+    if (((uintptr_t)ids) % 4) return hipErrorInvalidValue;
+    int64_t head = (int64_t)(((16 - ((uintptr_t)ids & 15)) & 15) / 4);
+    if (head > n) head = n;
+    const int64_t nv = (n - head) / 4;
+    int64_t blocks = (nv + 255) / 256;
+    blocks = blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks;
+    hipLaunchKernelGGL(ids_check_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ids, n, (int)head, nv, status);
     return hipGetLastError();
 }
 

@@ -455,8 +455,8 @@ class Engine:
         embedding output, n_layer: hidden_states[-1]).  Exactly one of positions (1..16 positions shared by every window) and
         positions_per_window (an integer tensor [B, 1..16] on this device; a value outside [0, L) is clamped and reported like a bad
         token id, `check_status`).  Only the last level asked for: `forward`'s own walk; any level below it: the unfolded walk of
-        `forward(all_hidden=True)`, whose levels the rows are bit-equal to.  Chunking, workspace and asynchronous input validation
-        are those of `forward`."""
+        `forward(all_hidden=True)`, whose levels the rows are bit-equal to, run only as deep as the highest level asked for.
+        Chunking, workspace and asynchronous input validation are those of `forward`."""
         B, L = self._check_ids(input_ids)
         lv, P = check_layer_request(layers, self.config.n_layer, positions, positions_per_window, B)
         ids = self._ids(input_ids)

@@ -5,6 +5,11 @@
                       (b)  pcad_forward_layers, all 33 levels at position 255, out [33, B, 1, 2D]       - the same layer walk
   pair "last_level"   (a)  pcad_forward(positions=[255]), hidden_out [B, 1, 2D]
                       (b)  pcad_forward_layers(layers=[n_layer], positions=[255]), out [1, B, 1, 2D]    - the same walk + one small launch
+  pairs "level_1", "level_mid", "level_below_top", "levels_4_mid": layers = [1], [n_layer / 2], [n_layer - 1], [4, n_layer / 2]
+                      (a)  pcad_forward_layers(layers, positions=[255]) on the baseline library: all n_layer blocks
+                      (b)  the same call on this build: K blocks for the highest level K, block K - 1 shortened to walk_len steps.
+                           Recorded beside the ratio: what construction predicts, (K - 1 + walk_len / L) / n_layer of the parent's
+                           block time (embedding, row gathers and the head / id check are outside that figure)
 
 (a) runs on --baseline-lib (a libpcad.so built from the parent commit) when given, else on this build.  One round = (a), (b), (a')
 once each in that order, (a') being the same call as (a) again: the A/A spread the result is read against; the figure of a series
@@ -26,7 +31,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PAIRS = ("all_levels", "last_level")
+PAIRS = ("all_levels", "last_level", "level_1", "level_mid", "level_below_top", "levels_4_mid")
 PAIR_LIMIT_S = 240            # per pair: engine build + (warmup + steps) x 3 forwards of ~0.1 s
 B, L, POS = 64, 512, 255
 
@@ -47,9 +52,16 @@ def run_pair(a):
     if a.pair == "all_levels":
         fa = lambda: base.forward(ids, want_hidden=True, want_logits=False, all_hidden=True)          # noqa: E731
         fb = lambda: eng.forward_layers(ids, None, positions=[POS])                                   # noqa: E731
-    else:
+    elif a.pair == "last_level":
         fa = lambda: base.forward(ids, positions=[POS], want_hidden=True, want_logits=False)          # noqa: E731
         fb = lambda: eng.forward_layers(ids, [cfg.n_layer], positions=[POS])                          # noqa: E731
+    else:
+        nl = cfg.n_layer
+        layers = {"level_1": [1], "level_mid": [nl // 2], "level_below_top": [nl - 1], "levels_4_mid": [4, nl // 2]}[a.pair]
+        fa = lambda: base.forward_layers(ids, layers, positions=[POS])                                # noqa: E731
+        fb = lambda: eng.forward_layers(ids, layers, positions=[POS])                                 # noqa: E731
+        walk_len = min(L, (max(POS + 1, L - POS) + 7) // 8 * 8)           # csrc/forward.hip plan_forward
+        predicted = (layers[-1] - 1 + walk_len / L) / nl
     series = {"a_parent_call": fa, "b_forward_layers": fb, "a2_parent_call_again": fa}
     for _ in range(a.warmup):
         for fn in series.values():
@@ -67,6 +79,8 @@ def run_pair(a):
              build_hash=eng.lib.pcad_build_hash().decode(), baseline_build_hash=base_hash,
              median_ms={k: round(v, 3) for k, v in med.items()}, min_ms={k: round(min(v), 3) for k, v in ms.items()},
              b_over_a=round(ratio, 5), a_over_a_spread=round(aa, 5), b_not_slower_beyond_3pct=bool(ratio <= 1.03))
+    if a.pair not in ("all_levels", "last_level"):
+        r.update(layers=layers, walk_len=walk_len, predicted_b_over_a=round(predicted, 5), b_below_a_beyond_spread=bool(ratio < 1 - aa))
     print(json.dumps(r), flush=True)
     with open(a.part, "w") as f:
         json.dump(dict(device=torch.cuda.get_device_name(0), row=r), f)
