@@ -167,7 +167,7 @@ void   pcad_destroy(pcad_handle h);
  *                 gating: twice the waves per launch, the same arithmetic, no extra pass (L % 64 == 0; never the last layer, whose
  *                 walks "last_layer_shortcut" shortens).  Against the plain two-launch form the bf16 model's gate-once sum is rounded
  *                 at the other direction's partial on half of the rows: equal to bf16 rounding of one addend (fp32: summation order;
- *                 bf16 with "gate_each" / "reference_order" >= 1: bit-identical).  +13 % at 32 x 8 192 bp (Medium), +12 % at 16 x 512 bp.
+ *                 with "gate_each" / "reference_order" >= 1: bit-identical in both dtypes).  +13 % at 32 x 8 192 bp (Medium), +12 % at 16 x 512 bp.
  *                 The same switch governs the K-split of the fused conv + x_proj kernel for launches of at most 64 row tiles (up to 8
  *                 windows of 512 bp): several blocks per row tile each walk a share of the channels and a second tiny kernel adds
  *                 their partial x_proj sums in a fixed order (deterministic; another fp32 summation order than the unsplit walk).
@@ -391,6 +391,27 @@ int pcad_conv_xproj_bidir(const void* x, const float* w_fwd, const float* b_fwd,
                           void* xc_fwd, void* dtl_fwd, float* bc_fwd, void* xc_rev, void* dtl_rev, float* bc_rev,
                           int S, int L, int E, int Rp, int dtype, pcad_stream stream);
 
+/* pcad_conv_xproj_bidir with the arguments only the engine passes (csrc/convx.hip launch_convx), for operator-level tests of the forms
+ * a small pcad_forward call runs.  x, w_*, b_*, xc_*, bc_*, Rp as above; every tensor 16-byte aligned.
+ *   part_ws    NULL, or a device buffer of pcad_conv_xproj_split_scratch_bytes(S, L, E, dtype, Rp, policy_S) bytes (16-byte aligned):
+ *              when the launch shape asks for it ("scan_segments" above: at most 64 row tiles of 128 rows) ks blocks per row tile each walk
+ *              1 / ks of the channels, write their partial x_dbl there, and a second kernel adds the partials in index order.  xc is
+ *              not affected (the conv is not split).  0 bytes: this shape is not split, and part_ws is ignored.
+ *   policy_S   the strand count the K-split factor is chosen for (0: S) - the engine passes the strands of the whole pcad_forward call,
+ *              so that a chunk of it runs the form the call runs; the scratch is sized for the S strands of the launch
+ *   dtl_split  (fp32 only) dtl_* is written as bf16 [S*L, 2 Rp] = [hi | lo], hi = bf16(v), lo = bf16(v - hi): the operand of the scan's
+ *              split dt_proj (pcad_selective_scan_engine dt_split)
+ *   w_split    (fp32 only) x_proj runs as three bf16 MFMA products per fp32 product (hi.hi, lo.hi, hi.lo of "f32_gemm_split").  Wx_* is
+ *              still given as fp32 [Rp + 32, E]; the entry packs each into its bf16 [Rp + 32, 2E] form (per 32 channels [hi (32) | lo (32)])
+ *              inside `scratch`, as pcad_gemm_nt_split packs its operands
+ *   scratch    256-byte aligned, scratch_bytes >= pcad_conv_xproj_scratch_bytes(E, dtype) rounded up to 256, plus - w_split -
+ *              2 * (Rp + 32) * 2 E * 2 bytes; else PCAD_ERR_WORKSPACE (also for a part_ws that is too small) */
+size_t pcad_conv_xproj_split_scratch_bytes(int S, int L, int E, int dtype, int Rp, int policy_S);
+int pcad_conv_xproj_bidir_engine(const void* x, const float* w_fwd, const float* b_fwd, const float* w_rev, const float* b_rev,
+                                 const void* Wx_fwd, const void* Wx_rev, void* scratch, size_t scratch_bytes, void* xc_fwd, void* dtl_fwd,
+                                 float* bc_fwd, void* xc_rev, void* dtl_rev, float* bc_rev, void* part_ws, size_t part_ws_bytes,
+                                 int policy_S, int dtl_split, int w_split, int S, int L, int E, int Rp, int dtype, pcad_stream stream);
+
 /* selective_scan_fn(u, delta, A, B, C, D, z, delta_bias, delta_softplus=True), token-major:
  *   u, delta [S, L, E] dtype; z [S, L, ldz>=E] dtype or NULL; bc fp32 [S*L, 32] = B_t (16) | C_t (16) per token;
  *   A fp32 [E, 16] (negative real, NOT pre-scaled); Dskip, delta_bias fp32 [E];
@@ -410,6 +431,52 @@ int pcad_selective_scan_dtproj(const void* u, const void* dt_low, int64_t lddt, 
                                const float* A, const float* Dskip, const float* delta_bias,
                                void* y, int S, int L, int E, int reverse, int accumulate,
                                int dtype, pcad_stream stream);
+
+/* pcad_selective_scan_dtproj in the layouts and with the arguments the engine passes (csrc/scan.hip launch_scan), for operator-level
+ * tests of the instantiations and launch forms a pcad_forward call runs.  Fused dt_proj only.
+ *   u, y       [rows8, E] dtype in the BLOCKED layout of pcad_conv_xproj_bidir over the S * L rows (rows8 = S * L rounded up to 8;
+ *              E * elem a multiple of 128 bytes); z the same, or NULL (ungated).  With L % 8 == 0 (and, bf16, Rp 64 or 96) the
+ *              instantiations with compile-time layouts run, otherwise the run-time-layout ones.  Padding rows are never written.
+ *   dt_low     [S*L, lddt >= Rp] dtype, Wdt [E, Rp] dtype as in pcad_selective_scan_dtproj;  dt_split (fp32 only, Rp <= 96): both are
+ *              bf16 [hi | lo] tensors, dt_low [S*L, lddt >= 2 Rp] and Wdt [E, 2 Rp], and dt_proj runs as three bf16 MFMA products
+ *   A2, a_scale  the base-2 decay rate is A2 * a_scale: (A * log2(e), 1) as the engine stores it, or (A, log2(e))
+ *   accumulate as in pcad_selective_scan; the prior content of y is the other direction's output
+ *   seg_ws     NULL, or a device buffer of pcad_scan_segment_scratch_bytes(S, L, E, policy_S) bytes (16-byte aligned; too small:
+ *              PCAD_ERR_WORKSPACE): when the launch shape asks for it ("scan_segments" above) every strand is cut into segments that run
+ *              as separate workgroups - a pass from zero states, the carry h0[g] = exp2(A2 a_scale sum delta) (.) h0[g-1] + h_end[g-1],
+ *              then the real pass.  Taken by the four launches the engine issues (forward accumulate 0; reverse with z, any accumulate);
+ *              other launches, and shapes whose size query returns 0, run the plain walk.
+ *   policy_S   the strand count the segment policy is evaluated for (0: S), as in pcad_conv_xproj_bidir_engine
+ *   walk_len   0 or >= L: the whole strand; else only the first walk_len steps of the walk run (forward rows [0, walk_len), reverse rows
+ *              [L - walk_len, L)) and the other rows of y are not written ("last_layer_shortcut").  Must be a multiple of 8.  Ignored
+ *              when the walk is cut into segments.
+ *   ysplit     NULL, or bf16 [rows8, 2E] blocked = [hi | lo] of the output, hi = bf16(y), lo = bf16(y - hi), written INSTEAD of y
+ *              (out_proj's operand under "f32_gemm_split"): fp32, L % 8 == 0, z given, reverse with accumulate 1 or 2, whole walk, not
+ *              segmented; anything else is PCAD_ERR_INVALID
+ * PCAD_ERR_INVALID: whatever launch_scan rejects (shape / layout / form), walk_len % 8 != 0, misaligned tensors. */
+size_t pcad_scan_segment_scratch_bytes(int S, int L, int E, int policy_S);
+int pcad_selective_scan_engine(const void* u, const void* dt_low, int64_t lddt, const void* Wdt, int Rp, const void* z, const float* bc,
+                               const float* A2, float a_scale, const float* Dskip, const float* delta_bias, void* y, void* ysplit,
+                               void* seg_ws, size_t seg_ws_bytes, int policy_S, int walk_len, int dt_split, int S, int L, int E,
+                               int reverse, int accumulate, int dtype, pcad_stream stream);
+
+/* The PAIR walk ("scan_segments" above; csrc/scan.hip launch_scan_pair): both directions of a layer in one launch, half a strand each.
+ * Per direction (*_fwd walks left to right, *_rev right to left on the same rows): u blocked, dt_low [S*L, lddt], Wdt [E, Rp], bc, A2
+ * (already scaled by log2(e)), Dskip, delta_bias as in pcad_selective_scan_engine; z (required) and y blocked; L % 64 == 0; bf16: Rp 64
+ * or 96.
+ *   phases     bit 0: the first halves - forward rows [0, L/2) and reverse rows [L/2, L) from zero states, written ungated (gate_each:
+ *              each gated and rounded), end states kept in ws;  bit 1: the second halves from those states, each adding what the OTHER
+ *              direction's first half left in y: gate_each 0: y = (y + out) * silu(z);  1: y = round(out * silu(z)) + y - the same two
+ *              rounded addends as two plain accumulate 1 launches.  3: both, in that order (the engine issues 1, then 2).
+ *   ws         pcad_scan_pair_scratch_bytes(S, E) bytes, 16-byte aligned (too small: PCAD_ERR_WORKSPACE); carries the states from
+ *              phase 1 to phase 2
+ *   ysplit / dt_split  (fp32 only) as in pcad_selective_scan_engine; ysplit is written by phase 2 instead of y */
+size_t pcad_scan_pair_scratch_bytes(int S, int E);
+int pcad_selective_scan_pair(const void* u_fwd, const void* dt_low_fwd, const void* Wdt_fwd, const float* bc_fwd, const float* A2_fwd,
+                             const float* Dskip_fwd, const float* delta_bias_fwd, const void* u_rev, const void* dt_low_rev,
+                             const void* Wdt_rev, const float* bc_rev, const float* A2_rev, const float* Dskip_rev,
+                             const float* delta_bias_rev, const void* z, int64_t lddt, int Rp, void* y, void* ysplit, void* ws,
+                             size_t ws_bytes, int S, int L, int E, int gate_each, int phases, int dt_split, int dtype, pcad_stream stream);
 
 /* F.linear(a, w): C[M,N] = A[M,K] . W[N,K]^T on MFMA.  lda/ldw/ldc in elements; K % (128/sizeof(elem)) == 0,
  * lda, ldw multiples of 16 bytes.  out_dtype: PCAD_F32 or `dtype`. */

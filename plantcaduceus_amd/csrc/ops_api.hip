@@ -75,6 +75,57 @@ int pcad_conv_xproj_bidir(const void* x, const float* w_fwd, const float* b_fwd,
     return PCAD_OK;
 }
 
+size_t pcad_conv_xproj_split_scratch_bytes(int S, int L, int E, int dtype, int Rp, int policy_S) {
+    if (S <= 0 || L <= 0 || E <= 0 || policy_S < 0 || (dtype != PCAD_F32 && dtype != PCAD_BF16) || (Rp != 64 && Rp != 96) ||
+        (E * (dtype == PCAD_BF16 ? 2 : 4)) % 128)
+        return 0;
+    return convx_split_bytes(S, L, E, dtype, Rp, policy_S);
+}
+
+int pcad_conv_xproj_bidir_engine(const void* x, const float* w_fwd, const float* b_fwd, const float* w_rev, const float* b_rev,
+                                 const void* Wx_fwd, const void* Wx_rev, void* scratch, size_t scratch_bytes, void* xc_fwd, void* dtl_fwd,
+                                 float* bc_fwd, void* xc_rev, void* dtl_rev, float* bc_rev, void* part_ws, size_t part_ws_bytes,
+                                 int policy_S, int dtl_split, int w_split, int S, int L, int E, int Rp, int dtype, pcad_stream stream) {
+    if (!x || !w_fwd || !b_fwd || !w_rev || !b_rev || !Wx_fwd || !Wx_rev || !scratch || !xc_fwd || !dtl_fwd || !bc_fwd ||
+        !xc_rev || !dtl_rev || !bc_rev)
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: null argument");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: bad dtype");
+    if (Rp != 64 && Rp != 96) return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: Rp must be 64 (dt_rank <= 64) or 96 (dt_rank 65..96)");
+    if ((dtl_split || w_split) && dtype != PCAD_F32)
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: dtl_split / w_split are forms of the fp32 model");
+    const int64_t esz = dtype == PCAD_BF16 ? 2 : 4;
+    if (S < 0 || L < 0 || E <= 0 || policy_S < 0 || (E * esz) % 128)
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: E * elem must be a multiple of 128 bytes; S, L, policy_S >= 0");
+    if (((int64_t)S * L + 16) * E * esz >= ((int64_t)1 << 32))
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: (S*L + 16) * E * elem must be < 2^32 (32-bit in-tensor offsets)");
+    if (((uintptr_t)x) % 16 || ((uintptr_t)xc_fwd) % 16 || ((uintptr_t)xc_rev) % 16 || ((uintptr_t)dtl_fwd) % 16 || ((uintptr_t)dtl_rev) % 16 ||
+        ((uintptr_t)bc_fwd) % 16 || ((uintptr_t)bc_rev) % 16 || ((uintptr_t)Wx_fwd) % 16 || ((uintptr_t)Wx_rev) % 16)
+        return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: tensors must be 16-byte aligned");
+    // scratch: the packed taps, then - w_split - the two [hi | lo] x_proj weights (bf16 [Rp + 32, 2E] each)
+    const size_t taps = align_up(convx_packed_bytes(E, dtype)), wsb = (size_t)(Rp + 32) * 2 * E * 2;
+    if (((uintptr_t)scratch) % 256 || scratch_bytes < taps + (w_split ? 2 * wsb : 0))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_conv_xproj_bidir_engine: scratch must be 256-byte aligned and hold the packed taps%s",
+                    w_split ? " and both split x_proj weights" : "");
+    if (part_ws && (((uintptr_t)part_ws) % 16 || part_ws_bytes < convx_split_bytes(S, L, E, dtype, Rp, policy_S)))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_conv_xproj_bidir_engine: part_ws must be 16-byte aligned and pcad_conv_xproj_split_scratch_bytes large");
+    if (S == 0 || L == 0) return PCAD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_pack_convw(w_fwd, b_fwd, w_rev, b_rev, (float*)scratch, E, dtype, s));
+    const void *W0 = Wx_fwd, *W1 = Wx_rev;
+    if (w_split) {
+        void* p0 = (char*)scratch + taps;
+        void* p1 = (char*)p0 + wsb;
+        HIP_TRY(launch_pack_convx_wsplit((const float*)Wx_fwd, E, p0, Rp + 32, E, s));
+        HIP_TRY(launch_pack_convx_wsplit((const float*)Wx_rev, E, p1, Rp + 32, E, s));
+        W0 = p0; W1 = p1;
+    }
+    hipError_t err = launch_convx(x, (const float*)scratch, W0, xc_fwd, dtl_fwd, bc_fwd, W1, xc_rev, dtl_rev, bc_rev, S, L, E, dtype, s, Rp,
+                                  dtl_split != 0, w_split != 0, (float*)part_ws, policy_S);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: unsupported shape / form");
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_conv_xproj_bidir_engine: %s", hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 static int scan_args_ok(const void* u, const float* bc, const float* A, const float* Dskip, const float* delta_bias,
                         void* y, int S, int L, int E) {
     if (!u || !bc || !A || !Dskip || !delta_bias || !y) return fail(PCAD_ERR_INVALID, "pcad_selective_scan: null argument");
@@ -107,6 +158,72 @@ int pcad_selective_scan_dtproj(const void* u, const void* dt_low, int64_t lddt, 
     if (S == 0 || L == 0) return PCAD_OK;
     HIP_TRY(launch_scan(u, z, ldz, nullptr, dt_low, lddt, Wdt, Rp, bc, A, 1.4426950408889634f, Dskip, delta_bias, y, S, L,
                         E, reverse != 0, accumulate, dtype, (hipStream_t)stream));
+    return PCAD_OK;
+}
+
+size_t pcad_scan_segment_scratch_bytes(int S, int L, int E, int policy_S) {
+    if (S <= 0 || L <= 0 || E <= 0 || E % 64 || policy_S < 0) return 0;
+    return scan_segment_bytes(S, L, E, policy_S);
+}
+
+size_t pcad_scan_pair_scratch_bytes(int S, int E) {
+    if (S <= 0 || E <= 0 || E % 64) return 0;
+    return scan_pair_bytes(S, E);
+}
+
+// what the two engine-form scan entries check alike: dtype, shape, the fused dt_proj operand's rows
+static int scan_engine_args(const char* who, int S, int L, int E, int Rp, int64_t lddt, int dt_split, int dtype) {
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype", who);
+    if (S < 0 || L < 0 || E <= 0 || E % 64) return fail(PCAD_ERR_INVALID, "%s: E must be a multiple of 64; S, L >= 0", who);
+    if (dt_split && dtype != PCAD_F32) return fail(PCAD_ERR_INVALID, "%s: dt_split is a form of the fp32 model", who);
+    const int64_t desz = dtype == PCAD_BF16 || dt_split ? 2 : 4;       // dt_low / Wdt elements
+    if (Rp <= 0 || Rp % 32 || lddt < (dt_split ? 2 : 1) * (int64_t)Rp || (lddt * desz) % 16)
+        return fail(PCAD_ERR_INVALID, "%s: Rp must be a multiple of 32 (zero padded), lddt >= Rp (dt_split: 2 Rp), rows 16-byte aligned", who);
+    return PCAD_OK;
+}
+
+int pcad_selective_scan_engine(const void* u, const void* dt_low, int64_t lddt, const void* Wdt, int Rp, const void* z, const float* bc,
+                               const float* A2, float a_scale, const float* Dskip, const float* delta_bias, void* y, void* ysplit,
+                               void* seg_ws, size_t seg_ws_bytes, int policy_S, int walk_len, int dt_split, int S, int L, int E,
+                               int reverse, int accumulate, int dtype, pcad_stream stream) {
+    if (!u || !dt_low || !Wdt || !bc || !A2 || !Dskip || !delta_bias || !y) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: null argument");
+    if (int rc = scan_engine_args("pcad_selective_scan_engine", S, L, E, Rp, lddt, dt_split, dtype)) return rc;
+    if (accumulate < 0 || accumulate > 2 || (accumulate == 2 && !z)) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: accumulate must be 0, 1 or 2 (2 needs z)");
+    if (policy_S < 0 || walk_len < 0 || walk_len % 8)
+        return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: walk_len must be a whole number of 8-step groups; policy_S >= 0");
+    if (((uintptr_t)u) % 16 || ((uintptr_t)y) % 16 || ((uintptr_t)z) % 16 || ((uintptr_t)ysplit) % 16 || ((uintptr_t)dt_low) % 16 ||
+        ((uintptr_t)Wdt) % 16 || ((uintptr_t)bc) % 16 || ((uintptr_t)A2) % 16)
+        return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: tensors must be 16-byte aligned");
+    if (seg_ws && (((uintptr_t)seg_ws) % 16 || seg_ws_bytes < scan_segment_bytes(S, L, E, policy_S)))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_selective_scan_engine: seg_ws must be 16-byte aligned and pcad_scan_segment_scratch_bytes large");
+    hipError_t err = launch_scan(u, z, E, nullptr, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, delta_bias, y, S, L, E, reverse != 0, accumulate,
+                                 dtype, (hipStream_t)stream, true, true, (float*)seg_ws, walk_len, ysplit, dt_split != 0, policy_S);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: unsupported shape / form (see include/pcad.h)");
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_selective_scan_engine: %s", hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_selective_scan_pair(const void* u_fwd, const void* dt_low_fwd, const void* Wdt_fwd, const float* bc_fwd, const float* A2_fwd,
+                             const float* Dskip_fwd, const float* delta_bias_fwd, const void* u_rev, const void* dt_low_rev,
+                             const void* Wdt_rev, const float* bc_rev, const float* A2_rev, const float* Dskip_rev,
+                             const float* delta_bias_rev, const void* z, int64_t lddt, int Rp, void* y, void* ysplit, void* ws,
+                             size_t ws_bytes, int S, int L, int E, int gate_each, int phases, int dt_split, int dtype, pcad_stream stream) {
+    if (!u_fwd || !dt_low_fwd || !Wdt_fwd || !bc_fwd || !A2_fwd || !Dskip_fwd || !delta_bias_fwd || !u_rev || !dt_low_rev || !Wdt_rev ||
+        !bc_rev || !A2_rev || !Dskip_rev || !delta_bias_rev || !z || !y || !ws)
+        return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: null argument");
+    if (int rc = scan_engine_args("pcad_selective_scan_pair", S, L, E, Rp, lddt, dt_split, dtype)) return rc;
+    if (ysplit && dtype != PCAD_F32) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: ysplit is a form of the fp32 model");
+    if (phases < 1 || phases > 3) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: phases must be 1, 2 or 3");
+    const void* al[] = {u_fwd, dt_low_fwd, Wdt_fwd, bc_fwd, A2_fwd, u_rev, dt_low_rev, Wdt_rev, bc_rev, A2_rev, z, y, ysplit};
+    for (const void* p : al)
+        if (((uintptr_t)p) % 16) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: tensors must be 16-byte aligned");
+    if (((uintptr_t)ws) % 16 || ws_bytes < scan_pair_bytes(S, E))
+        return fail(PCAD_ERR_WORKSPACE, "pcad_selective_scan_pair: ws must be 16-byte aligned and pcad_scan_pair_scratch_bytes large");
+    const ScanDirection f{u_fwd, dt_low_fwd, Wdt_fwd, bc_fwd, A2_fwd, Dskip_fwd, delta_bias_fwd};
+    const ScanDirection r{u_rev, dt_low_rev, Wdt_rev, bc_rev, A2_rev, Dskip_rev, delta_bias_rev};
+    hipError_t err = launch_scan_pair(f, r, z, lddt, Rp, y, S, L, E, gate_each != 0, dtype, (hipStream_t)stream, (float*)ws, ysplit, dt_split != 0, phases);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: unsupported shape (L %% 64 == 0; bf16: Rp 64 or 96; see include/pcad.h)");
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_selective_scan_pair: %s", hipGetErrorString(err));
     return PCAD_OK;
 }
 

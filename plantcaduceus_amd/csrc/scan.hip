@@ -423,7 +423,13 @@ __device__ __forceinline__ void scan_body(float (*dvs)[64], const int block_id, 
         if constexpr (SEG != 1) {
             yv = yacc[0] + yacc[1];
             if constexpr (HASZ) yv *= silu(zv);
-            if constexpr (ACC == 1) yv = Elem<T>::round(yv) + yprev;    // each direction is rounded, then summed
+            if constexpr (ACC == 1) {                                     // each direction is rounded, then summed
+                // fp32: "rounded" is the fp32 value of out * silu(z) itself - without this the compiler contracts the gate's multiply
+                // into the add (one fma), and which of the two addends is the unrounded one then depends on the launch order: a pair
+                // walk and two plain launches differed in the last bit (tests/test_gpu_engine_forms.py test_scan_pair, fp32 gate_each)
+                if constexpr (std::is_same<T, float>::value) asm volatile("" : "+v"(yv));
+                yv = Elem<T>::round(yv) + yprev;
+            }
         }
 #pragma unroll
         for (int p = 0; p < NSTATE; ++p) bcc[p] = bcn[p];

@@ -72,6 +72,15 @@ SIGNATURES = {
     "pcad_selective_scan_dtproj": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pcad_conv_xproj_split_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
+    "pcad_conv_xproj_bidir_engine": (C.c_int, [C.c_void_p] * 8 + [C.c_size_t] + [C.c_void_p] * 7 + [C.c_size_t] + [C.c_int] * 8 + [C.c_void_p]),
+    "pcad_scan_segment_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
+    "pcad_selective_scan_engine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] +
+                                   [C.c_int] * 9 + [C.c_void_p]),
+    "pcad_scan_pair_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "pcad_selective_scan_pair": (C.c_int, [C.c_void_p] * 15 + [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] +
+                                 [C.c_int] * 7 + [C.c_void_p]),
     "pcad_gemm_nt": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pcad_gemm_nt_residual": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -67,14 +67,14 @@ def causal_conv1d_bidir(x_tm, w_fwd, b_fwd, w_rev, b_rev):
     return yf, yr
 
 
-def to_blocked(x_rows: torch.Tensor) -> torch.Tensor:
-    """[rows, E] -> the engine's blocked layout [rows8/8, E*esz/128, 8, 128/esz] (include/pcad.h), rows zero-padded to 8."""
+def to_blocked(x_rows: torch.Tensor, pad_value: float = 0.0) -> torch.Tensor:
+    """[rows, E] -> the engine's blocked layout [rows8/8, E*esz/128, 8, 128/esz] (include/pcad.h), rows padded to 8 with pad_value."""
     rows, E = x_rows.shape
     per = 128 // x_rows.element_size()
     if E % per:
         raise ValueError("E * elem must be a multiple of 128 bytes")
     rows8 = (rows + 7) // 8 * 8
-    buf = torch.zeros((rows8, E), dtype=x_rows.dtype, device=x_rows.device)
+    buf = torch.full((rows8, E), pad_value, dtype=x_rows.dtype, device=x_rows.device)
     buf[:rows] = x_rows
     return buf.view(rows8 // 8, 8, E // per, per).permute(0, 2, 1, 3).contiguous()
 
@@ -153,6 +153,139 @@ def conv_xproj_bidir(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev):
     outs = [from_blocked(c, rows).view(S, L, E) for c in xc]
     dbl = [torch.cat([dtl[d][:, :R], bc[d].to(dt)], dim=1).view(S, L, R + 32) for d in range(2)]
     return outs[0], outs[1], dbl[0], dbl[1]
+
+
+# ---- the engine's launch forms as operators (include/pcad.h pcad_*_engine / pcad_selective_scan_pair) ----------------------------
+# Token-major tensors in and out; the blocked layouts are made and undone here.  Every output buffer starts as NaN where the kernel
+# must write it, so that a row it skipped - or a scratch slot it read without writing - shows.
+def _aligned(t: torch.Tensor) -> int:
+    return (t.data_ptr() + 255) // 256 * 256
+
+
+def _nan_bytes(n: int, dev) -> torch.Tensor:
+    return torch.full((n + 256,), 0xFF, dtype=torch.uint8, device=dev)      # 0xFF bytes: NaN in fp32 and bf16
+
+
+def _y_blocked(y_prior, S, L, E, dt, dev):
+    """the blocked y buffer: the caller's prior content (accumulate modes, walk_len), else NaN; padding rows always NaN"""
+    if y_prior is None:
+        y_prior = torch.full((S, L, E), float("nan"), dtype=dt, device=dev)
+    return to_blocked(y_prior.to(dt).reshape(S * L, E), pad_value=float("nan"))
+
+
+def _decode_ysplit(ysb, rows, S, L, E):
+    """bf16 [rows8, 2E] blocked = [hi | lo] -> (hi, lo) [S, L, E] bf16"""
+    flat = from_blocked(ysb, rows)
+    return flat[:, :E].reshape(S, L, E), flat[:, E:].reshape(S, L, E)
+
+
+def selective_scan_engine(u, dt_low, Wdt, Rp, bc, A2, D, delta_bias, z=None, y_prior=None, reverse=False, accumulate=0, a_scale=1.0,
+                          segmented=False, policy_S=0, walk_len=0, ysplit=False, dt_split=False):
+    """pcad_selective_scan_engine: one direction's fused dt_proj + scan in the engine's layouts.
+    u, z, y_prior [S, L, E] (z / y_prior may be None); dt_low [S, L, lddt] and Wdt [E, Rp] in u's dtype, zero padded to Rp - or, dt_split,
+    the bf16 [hi | lo] forms [S, L, 2 Rp] / [E, 2 Rp]; bc fp32 [S, L, 32]; A2 fp32 [E, 16] with the decay rate A2 * a_scale in base 2.
+    segmented: hand over the segment scratch (whether the walk is then cut is the library's policy for the shape, see
+    pcad_scan_segment_scratch_bytes).  -> namespace(y [S, L, E], pad: the blocked y buffer's padding rows, hi / lo [S, L, E] bf16 or
+    None: the ysplit output, seg_bytes)."""
+    from types import SimpleNamespace
+    _require_gpu(u, "u")
+    lib = load_library()
+    S, L, E = u.shape
+    dt, dev, rows = u.dtype, u.device, S * L
+    ub = to_blocked(u.reshape(rows, E))
+    zb = to_blocked(z.to(dt).reshape(rows, E)) if z is not None else None
+    yb = _y_blocked(y_prior, S, L, E, dt, dev)
+    dl, W = dt_low.contiguous(), Wdt.contiguous()
+    f32 = [t.float().contiguous() for t in (bc, A2, D, delta_bias)]
+    seg_bytes = lib.pcad_scan_segment_scratch_bytes(S, L, E, policy_S)
+    seg = _nan_bytes(seg_bytes, dev) if segmented else None
+    ysb = None
+    if ysplit:
+        ysb = torch.full(((rows + 7) // 8, 2 * E * 2 // 128, 8, 64), float("nan"), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_selective_scan_engine(ub.data_ptr(), dl.data_ptr(), dl.shape[-1], W.data_ptr(), Rp, zb.data_ptr() if zb is not None else None,
+                                              f32[0].data_ptr(), f32[1].data_ptr(), float(a_scale), f32[2].data_ptr(), f32[3].data_ptr(),
+                                              yb.data_ptr(), ysb.data_ptr() if ysb is not None else None,
+                                              _aligned(seg) if seg is not None else None, seg_bytes, policy_S, walk_len, int(bool(dt_split)),
+                                              S, L, E, int(bool(reverse)), accumulate, _dt(u), _stream_ptr()), "pcad_selective_scan_engine")
+    flat = yb.permute(0, 2, 1, 3).reshape(-1, E)
+    hi, lo = _decode_ysplit(ysb, rows, S, L, E) if ysb is not None else (None, None)
+    return SimpleNamespace(y=flat[:rows].reshape(S, L, E).contiguous(), pad=flat[rows:].contiguous(), hi=hi, lo=lo, seg_bytes=seg_bytes)
+
+
+def selective_scan_pair(fwd, rev, z, Rp, gate_each=False, phases=(3,), ysplit=False, dt_split=False):
+    """pcad_selective_scan_pair: both directions in one launch, half a strand each.  fwd / rev: dicts of one direction's operands
+    (u [S, L, E], dt_low, Wdt, bc, A2 - scaled by log2(e) -, D, delta_bias, as selective_scan_engine takes them); z [S, L, E].
+    phases: the calls to issue in order, (1, 2) as the engine does or (3,).  -> namespace(y [S, L, E], pad, hi, lo)."""
+    from types import SimpleNamespace
+    _require_gpu(z, "z")
+    lib = load_library()
+    S, L, E = z.shape
+    dt, dev, rows = z.dtype, z.device, S * L
+    ops = []
+    for d in (fwd, rev):
+        ops += [to_blocked(d["u"].to(dt).reshape(rows, E)), d["dt_low"].contiguous(), d["Wdt"].contiguous()]
+        ops += [d[k].float().contiguous() for k in ("bc", "A2", "D", "delta_bias")]
+    zb = to_blocked(z.reshape(rows, E))
+    yb = _y_blocked(None, S, L, E, dt, dev)
+    ws_bytes = lib.pcad_scan_pair_scratch_bytes(S, E)
+    ws = _nan_bytes(ws_bytes, dev)
+    ysb = None
+    if ysplit:
+        ysb = torch.full(((rows + 7) // 8, 2 * E * 2 // 128, 8, 64), float("nan"), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        for ph in phases:
+            _check(lib.pcad_selective_scan_pair(*[t.data_ptr() for t in ops], zb.data_ptr(), fwd["dt_low"].shape[-1], Rp, yb.data_ptr(),
+                                                ysb.data_ptr() if ysb is not None else None, _aligned(ws), ws_bytes, S, L, E,
+                                                int(bool(gate_each)), int(ph), int(bool(dt_split)), _DT[dt], _stream_ptr()),
+                   "pcad_selective_scan_pair")
+    flat = yb.permute(0, 2, 1, 3).reshape(-1, E)
+    hi, lo = _decode_ysplit(ysb, rows, S, L, E) if ysb is not None else (None, None)
+    return SimpleNamespace(y=flat[:rows].reshape(S, L, E).contiguous(), pad=flat[rows:].contiguous(), hi=hi, lo=lo)
+
+
+def conv_xproj_bidir_engine(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev, ksplit=True, policy_S=0, split=False):
+    """pcad_conv_xproj_bidir_engine on a token-major x [S, L, E] (operands as conv_xproj_bidir's).  ksplit: hand over the K-split
+    scratch (whether the launch is then split is the library's policy for the shape); split (fp32): dtl_split + w_split.
+    -> namespace(xc (fwd, rev) [S, L, E]; dtl (fwd, rev): [S*L, Rp] in x's dtype, or - split - bf16 [S*L, 2 Rp] = [hi | lo];
+                 bc (fwd, rev) fp32 [S*L, 32]; R, Rp; part_bytes: the K-split scratch of this shape, 0 = not split)."""
+    from types import SimpleNamespace
+    _require_gpu(x_tm, "x")
+    lib = load_library()
+    S, L, E = x_tm.shape
+    dt, dev, rows = x_tm.dtype, x_tm.device, S * L
+    R = x_proj_fwd.shape[0] - 32
+    if not 0 < R <= 96:
+        raise ValueError("dt_rank must be in [1, 96] for the fused kernel")
+    Rp = 64 if R <= 64 else 96
+    xb = to_blocked(x_tm.reshape(rows, E))
+
+    def pack_wx(w):
+        p = torch.zeros((Rp + 32, E), dtype=dt, device=dev)
+        p[:R] = w[:R].to(dt)
+        p[Rp:] = w[R:].to(dt)
+        return p
+    wx = [pack_wx(x_proj_fwd), pack_wx(x_proj_rev)]
+    taps = [t.float().contiguous() for t in (w_fwd.reshape(E, -1), b_fwd, w_rev.reshape(E, -1), b_rev)]
+    sb = (lib.pcad_conv_xproj_scratch_bytes(E, _DT[dt]) + 255) // 256 * 256 + (2 * (Rp + 32) * 2 * E * 2 if split else 0)
+    scratch = torch.empty(sb + 256, dtype=torch.uint8, device=dev)
+    part_bytes = lib.pcad_conv_xproj_split_scratch_bytes(S, L, E, _DT[dt], Rp, policy_S)
+    part = _nan_bytes(part_bytes, dev) if ksplit else None
+    xc = [torch.full_like(xb, float("nan")) for _ in range(2)]
+    if split:
+        dtl = [torch.full((rows, 2 * Rp), float("nan"), dtype=torch.bfloat16, device=dev) for _ in range(2)]
+    else:
+        dtl = [torch.full((rows, Rp), float("nan"), dtype=dt, device=dev) for _ in range(2)]
+    bc = [torch.full((rows, 32), float("nan"), dtype=torch.float32, device=dev) for _ in range(2)]
+    with torch.cuda.device(dev):
+        _check(lib.pcad_conv_xproj_bidir_engine(xb.data_ptr(), taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(), taps[3].data_ptr(),
+                                                wx[0].data_ptr(), wx[1].data_ptr(), _aligned(scratch), sb,
+                                                xc[0].data_ptr(), dtl[0].data_ptr(), bc[0].data_ptr(), xc[1].data_ptr(), dtl[1].data_ptr(),
+                                                bc[1].data_ptr(), _aligned(part) if part is not None else None, part_bytes, policy_S,
+                                                int(bool(split)), int(bool(split)), S, L, E, Rp, _DT[dt], _stream_ptr()),
+               "pcad_conv_xproj_bidir_engine")
+    return SimpleNamespace(xc=tuple(from_blocked(c, rows).view(S, L, E) for c in xc), dtl=tuple(dtl), bc=tuple(bc), R=R, Rp=Rp,
+                           part_bytes=part_bytes)
 
 
 def causal_conv1d_fn(x, weight, bias=None, activation=None):

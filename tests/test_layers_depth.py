@@ -12,6 +12,10 @@ pcad_forward_layers pcad_forward_loss pcad_forward_pooled pcad_forward_probs pca
 pcad_gemm_nt_split pcad_gemm_nt_split_scratch_bytes pcad_last_error pcad_layer_rows pcad_loss_head pcad_loss_head_scratch_bytes
 pcad_pooled_head pcad_pooled_head_scratch_bytes pcad_probs_head pcad_profile_enable pcad_profile_read pcad_selective_scan
 pcad_selective_scan_dtproj pcad_set_option pcad_set_status_buffer pcad_version pcad_weight_arena_bytes pcad_workspace_bytes""".split()
+# ... plus the operator entries added since for the engine's scan and conv + x_proj launch forms (tests/test_gpu_engine_forms.py):
+# additions only, nothing above changed
+EXPORTS += """pcad_conv_xproj_bidir_engine pcad_conv_xproj_split_scratch_bytes pcad_scan_pair_scratch_bytes pcad_scan_segment_scratch_bytes
+pcad_selective_scan_engine pcad_selective_scan_pair""".split()
 
 
 def test_exported_c_symbols_are_unchanged():
