@@ -126,21 +126,22 @@ __global__ __launch_bounds__(256) void conv_bidir_kernel(const T* __restrict__ x
     }
 }
 
-hipError_t launch_conv_bidir(const void* x, int64_t ldx, const float* wf, const float* bf, const float* wr,
-                             const float* br, void* yf, void* yr, int S, int L, int E, int dt, bool out_blocked,
-                             hipStream_t s, bool in_blocked) {
+template <typename T>
+static void launch_conv_bidir_t(const ConvLaunch& c, unsigned nb, hipStream_t s) {
+    hipLaunchKernelGGL(conv_bidir_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)c.x, c.ldx, c.fwd.w, c.fwd.b, c.rev.w, c.rev.b, (T*)c.fwd.y, (T*)c.rev.y,
+                       c.S, c.L, c.E, (int)c.out_blocked, (int)c.in_blocked);
+}
+
+hipError_t launch_conv_bidir(const ConvLaunch& c, hipStream_t s) {
+    const int S = c.S, L = c.L, E = c.E;
     if (S <= 0 || L <= 0) return hipSuccess;
     if (E % 8) return hipErrorInvalidValue;
-    if (out_blocked && (E * (dt == BF16 ? 2 : 4)) % 128) return hipErrorInvalidValue;
+    if (c.out_blocked && (E * (c.dt == BF16 ? 2 : 4)) % 128) return hipErrorInvalidValue;
     const int64_t total = (int64_t)S * ((L + CONV_SEG - 1) / CONV_SEG) * (E >> 3);
     const int64_t nb = (total + 255) / 256;
     if (nb > 0x7fffffff) return hipErrorInvalidValue;
-    if (dt == BF16)
-        hipLaunchKernelGGL(conv_bidir_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, s, (const bf16_t*)x, ldx, wf,
-                           bf, wr, br, (bf16_t*)yf, (bf16_t*)yr, S, L, E, (int)out_blocked, (int)in_blocked);
-    else
-        hipLaunchKernelGGL(conv_bidir_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s, (const float*)x, ldx, wf, bf,
-                           wr, br, (float*)yf, (float*)yr, S, L, E, (int)out_blocked, (int)in_blocked);
+    if (c.dt == BF16) launch_conv_bidir_t<bf16_t>(c, (unsigned)nb, s);
+    else launch_conv_bidir_t<float>(c, (unsigned)nb, s);
     return hipGetLastError();
 }
 
@@ -239,21 +240,26 @@ __global__ __launch_bounds__(256) void conv_dir_kernel(const T* __restrict__ x, 
     }
 }
 
-hipError_t launch_conv_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int S, int L, int E, int dt,
-                           bool reverse, bool out_blocked, bool in_blocked, hipStream_t s) {
+template <typename T>
+static void launch_conv_dir_t(const ConvLaunch& c, bool reverse, unsigned nb, hipStream_t s) {
+    const ConvDirection& d = reverse ? c.rev : c.fwd;
+    const auto kernel = reverse ? conv_dir_kernel<T, true> : conv_dir_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, s, (const T*)c.x, c.ldx, d.w, d.b, (T*)d.y, c.ldy, c.S, c.L, c.E, (int)c.out_blocked, (int)c.in_blocked);
+}
+
+hipError_t launch_conv_dir(const ConvLaunch& c, bool reverse, hipStream_t s) {
+    const int S = c.S, L = c.L, E = c.E;
     if (S <= 0 || L <= 0) return hipSuccess;
-    const int esz = dt == BF16 ? 2 : 4, V = 16 / esz;
-    if (E <= 0 || E % V || (!in_blocked && (ldx < E || ldx % V)) || (!out_blocked && (ldy < E || ldy % V))) return hipErrorInvalidValue;
-    if ((out_blocked || in_blocked) && (E * esz) % 128) return hipErrorInvalidValue;
+    const int esz = c.dt == BF16 ? 2 : 4, V = 16 / esz;
+    const ConvDirection& d = reverse ? c.rev : c.fwd;
+    if (!d.w || !d.b || !d.y) return hipErrorInvalidValue;       // the side that `reverse` names was not filled in
+    if (E <= 0 || E % V || (!c.in_blocked && (c.ldx < E || c.ldx % V)) || (!c.out_blocked && (c.ldy < E || c.ldy % V))) return hipErrorInvalidValue;
+    if ((c.out_blocked || c.in_blocked) && (E * esz) % 128) return hipErrorInvalidValue;
     const int64_t total = (int64_t)S * ((L + CONV_SEG - 1) / CONV_SEG) * (E / V);
     const int64_t nb = (total + 255) / 256;
     if (nb > 0x7fffffff) return hipErrorInvalidValue;
-#define PCAD_CONV_DIR(T, R)                                                                                                         \
-    hipLaunchKernelGGL((conv_dir_kernel<T, R>), dim3((unsigned)nb), dim3(256), 0, s, (const T*)x, ldx, w, b, (T*)y, ldy, S, L, E, \
-                       (int)out_blocked, (int)in_blocked)
-    if (dt == BF16) { if (reverse) PCAD_CONV_DIR(bf16_t, true); else PCAD_CONV_DIR(bf16_t, false); }
-    else            { if (reverse) PCAD_CONV_DIR(float, true); else PCAD_CONV_DIR(float, false); }
-#undef PCAD_CONV_DIR
+    if (c.dt == BF16) launch_conv_dir_t<bf16_t>(c, reverse, (unsigned)nb, s);
+    else launch_conv_dir_t<float>(c, reverse, (unsigned)nb, s);
     return hipGetLastError();
 }
 

@@ -591,39 +591,44 @@ hipError_t launch_pack_convw(const float* wf, const float* bf, const float* wr, 
     return hipGetLastError();
 }
 
-hipError_t launch_convx(const void* x, const float* convw, const void* Wx0, void* xc0, void* dtl0, float* bc0,
-                        const void* Wx1, void* xc1, void* dtl1, float* bc1, int S, int L, int E, int dt, hipStream_t s, int Rp, bool dtl_split,
-                        bool w_split, float* part_ws, int policy_S) {
+// the kernel of a launch form: NJ = 6 / 8 (Rp 64 / 96), ZFILL (L % 8 == 0), XS (fp32 only: the split-bf16 x_proj weight)
+template <typename T, int NJ>
+static auto convx_kernel_for(bool zfill, bool w_split) -> decltype(&convx_kernel<T, true, NJ>) {
+    if constexpr (std::is_same<T, float>::value) {
+        if (w_split) return zfill ? convx_kernel<T, true, NJ, true> : convx_kernel<T, false, NJ, true>;
+    }
+    return zfill ? convx_kernel<T, true, NJ> : convx_kernel<T, false, NJ>;
+}
+
+hipError_t launch_convx(const ConvxLaunch& c, hipStream_t s) {
+    const int S = c.S, L = c.L, E = c.E, dt = c.dt, Rp = c.Rp;
     if (S <= 0 || L <= 0) return hipSuccess;
-    if ((dtl_split || w_split) && dt != F32) return hipErrorInvalidValue;
+    if ((c.dtl_split || c.w_split) && dt != F32) return hipErrorInvalidValue;
     const int esz = dt == BF16 ? 2 : 4;
     if ((E * esz) % CX_ROWB || (Rp != 64 && Rp != 96)) return hipErrorInvalidValue;
     if (((int64_t)S * L + 16) * E * esz >= ((int64_t)1 << 32)) return hipErrorInvalidValue;    // unsigned 32-bit in-tensor offsets
-    ConvxDir d0{Wx0, xc0, dtl0, bc0, dtl_split ? 1 : 0}, d1{Wx1, xc1, dtl1, bc1, dtl_split ? 1 : 0};
+    const ConvxDir d0{c.dir[0].Wx, c.dir[0].xc, c.dir[0].dtl, c.dir[0].bc, c.dtl_split ? 1 : 0};
+    const ConvxDir d1{c.dir[1].Wx, c.dir[1].xc, c.dir[1].dtl, c.dir[1].bc, c.dtl_split ? 1 : 0};
     const int tiles = S * ((L + CX_ROWS - 1) / CX_ROWS);
     const bool zfill = L % 8 == 0;
-    const int ks = part_ws ? convx_ksplit(policy_S > 0 ? policy_S : S, L, E, dt) : 1;
-    float* part = ks > 1 ? part_ws : nullptr;
-#define PCAD_CONVX(T, Z, NJ_)                                                                                         \
-    do {                                                                                                                \
-        auto k = convx_kernel<T, Z, NJ_>;                                                                               \
-        if constexpr (std::is_same<T, float>::value) { if (w_split) k = convx_kernel<T, Z, NJ_, true>; }                \
-        if (hipError_t ae = ensure_dynamic_lds((const void*)k, CxGeom<NJ_>::LDS)) return ae;                            \
-        hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)ks), dim3(CX_THREADS), CxGeom<NJ_>::LDS, s, (const T*)x, convw, d0, d1, S, L, E, part); \
-    } while (0)
-#define PCAD_CONVX_NJ(NJ_)                                                                                            \
-    do {                                                                                                                \
-        if (dt == BF16) { if (zfill) PCAD_CONVX(bf16_t, true, NJ_); else PCAD_CONVX(bf16_t, false, NJ_); }              \
-        else { if (zfill) PCAD_CONVX(float, true, NJ_); else PCAD_CONVX(float, false, NJ_); }                           \
-    } while (0)
-    if (Rp == 64) PCAD_CONVX_NJ(6); else PCAD_CONVX_NJ(8);
-#undef PCAD_CONVX_NJ
-#undef PCAD_CONVX
+    const int ks = c.part_ws ? convx_ksplit(c.policy_S > 0 ? c.policy_S : S, L, E, dt) : 1;
+    float* part = ks > 1 ? c.part_ws : nullptr;
+    const int lds = Rp == 64 ? CxGeom<6>::LDS : CxGeom<8>::LDS;
+    const dim3 grid((unsigned)tiles, (unsigned)ks);
+    if (dt == BF16) {
+        const auto k = Rp == 64 ? convx_kernel_for<bf16_t, 6>(zfill, false) : convx_kernel_for<bf16_t, 8>(zfill, false);
+        if (hipError_t ae = ensure_dynamic_lds((const void*)k, lds)) return ae;
+        hipLaunchKernelGGL(k, grid, dim3(CX_THREADS), lds, s, (const bf16_t*)c.x, c.convw, d0, d1, S, L, E, part);
+    } else {
+        const auto k = Rp == 64 ? convx_kernel_for<float, 6>(zfill, c.w_split) : convx_kernel_for<float, 8>(zfill, c.w_split);
+        if (hipError_t ae = ensure_dynamic_lds((const void*)k, lds)) return ae;
+        hipLaunchKernelGGL(k, grid, dim3(CX_THREADS), lds, s, (const float*)c.x, c.convw, d0, d1, S, L, E, part);
+    }
     if (part) {
         const int64_t rows = (int64_t)S * L;
         const unsigned nb = (unsigned)((2 * rows * ((Rp + 32) / 4) + 255) / 256);
-        if (dt == BF16) hipLaunchKernelGGL(convx_reduce_kernel<bf16_t>, dim3(nb > 4096 ? 4096 : nb), dim3(256), 0, s, part, ks, rows, Rp + 32, d0, d1);
-        else hipLaunchKernelGGL(convx_reduce_kernel<float>, dim3(nb > 4096 ? 4096 : nb), dim3(256), 0, s, part, ks, rows, Rp + 32, d0, d1);
+        const auto kr = dt == BF16 ? convx_reduce_kernel<bf16_t> : convx_reduce_kernel<float>;
+        hipLaunchKernelGGL(kr, dim3(nb > 4096 ? 4096 : nb), dim3(256), 0, s, part, ks, rows, Rp + 32, d0, d1);
     }
     return hipGetLastError();
 }

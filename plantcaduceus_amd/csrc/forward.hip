@@ -174,9 +174,33 @@ struct Walk {
         if (pl.sp) {
             if (!(ys_from_scan(li) && src == c.w.y))
                 if (hipError_t er = launch_split_rows((const float*)src, E, c.w.ys, n_rows, E, a_blocked, a_blocked, s)) return er;
-            return launch_gemm_nt(c.w.ys, 2 * E, Wo_s, 2 * E, dst, D, n_rows, D, 3 * E, BF16, F32, false, s, a_blocked, E / 64);
+            return launch_gemm_nt({.A = c.w.ys, .lda = 2 * E, .W = Wo_s, .ldw = 2 * E, .M = n_rows, .N = D, .K = 3 * E, .dt = BF16, .a_blocked = a_blocked, .ksplit = E / 64},
+                                  {.C = dst, .ldc = D, .out_dt = F32}, s);
         }
-        return launch_gemm_nt(src, E, Wo, E, dst, D, n_rows, D, E, dt, dt, false, s, a_blocked);
+        return launch_gemm_nt({.A = src, .lda = E, .W = Wo, .ldw = E, .M = n_rows, .N = D, .K = E, .dt = dt, .a_blocked = a_blocked}, {.C = dst, .ldc = D, .out_dt = dt}, s);
+    }
+    // in_proj of the chunk's normalised rows u -> x | z: the split-bf16 form (bf16 [hi | lo] operands, fp32 outputs), two blocked
+    // tensors, or one plain [rows, 2E] tensor in x.  d: whose weight (untied form only)
+    hipError_t in_proj(const Lane& c, const LayerWeights& W, int64_t rows, int d, void* x, void* z) const {
+        if (pl.sp)
+            return launch_gemm_nt_two({.A = c.w.u, .lda = 2 * D, .W = d ? W.W_in_s_r : W.W_in_s, .ldw = 2 * D, .M = rows, .N = 2 * E, .K = 3 * D, .dt = BF16, .ksplit = D / 64},
+                                      {.C1 = x, .C2 = z, .nsplit = E, .out_blocked = true, .out_dt = F32}, s);
+        const GemmOperands g{.A = c.w.u, .lda = D, .W = d ? W.W_in_r : W.W_in, .ldw = D, .M = rows, .N = 2 * E, .K = D, .dt = dt};
+        if (e->xzsplit) return launch_gemm_nt_two(g, {.C1 = x, .C2 = z, .nsplit = E, .out_blocked = true}, s);
+        return launch_gemm_nt(g, {.C = x, .ldc = 2 * E, .out_dt = dt}, s);
+    }
+    int64_t ldxz() const { return e->xzsplit ? E : 2 * E; }        // elements between the rows of in_proj's x (and of z inside xz)
+    // direction d's scan operands (dts: the [hi | lo] dt_proj weight and dt_low rows)
+    ScanDirection scan_dir(const Lane& c, const LayerWeights& W, int d, bool dts) const {
+        const DirWeights& dw = W.dir[d];
+        return {.u = c.w.xc[d], .dt_low = c.w.dtl[d], .Wdt = dts ? dw.Wdt_s : dw.Wdt, .bc = c.w.bc[d], .A2 = dw.A2, .Dskip = dw.Dskip, .dbias = dw.dt_bias};
+    }
+    int64_t lddt(bool dts) const { return dts ? 2 * Rp : Rp; }
+    // what a layer's scans of direction d share (ungated forward walk of the whole strand into y): operands and the engine's layouts
+    ScanLaunch scan_of(const Lane& c, const LayerWeights& W, int d, bool dts) const {
+        return {.dir = scan_dir(c, W, d, dts), .ldz = ldxz(), .lddt = lddt(dts), .Rp = Rp, .y = c.w.y, .S = 2 * c.Bc, .L = L, .E = E, .dt = dt,
+                .uy_blocked = e->blocked, .z_blocked = e->xzsplit, .seg_ws = c.w.seg, .dt_split = dts,
+                .policy_S = 2 * B};        // the strands of the whole call: every chunk runs the same form
     }
     int lay_slot(int level) const {        // pcad_forward_layers: slot of `level` in the output, or -1
         if (rq.head != Head::layers) return -1;
@@ -241,11 +265,13 @@ struct Walk {
             for (int d = 0; d < 2; ++d) {       // each direction's own in_proj, then conv + SiLU on its own x
                 void *xd = d ? c.w.xz2 : c.w.xz, *zd = d ? c.w.zb2 : c.w.zb;
                 { ProfScope ps(e, PCAD_K_GEMM_IN, s);
-                if (sp) HIP_TRY(launch_gemm_nt_two(c.w.u, 2 * D, d ? W.W_in_s_r : W.W_in_s, 2 * D, xd, zd, E, true, rows, 2 * E, 3 * D, BF16, s, nullptr, F32, D / 64));
-                else if (e->xzsplit) HIP_TRY(launch_gemm_nt_two(c.w.u, D, d ? W.W_in_r : W.W_in, D, xd, zd, E, true, rows, 2 * E, D, dt, s));
-                else HIP_TRY(launch_gemm_nt(c.w.u, D, d ? W.W_in_r : W.W_in, D, xd, 2 * E, rows, 2 * E, D, dt, dt, false, s)); }
+                HIP_TRY(in_proj(c, W, rows, d, xd, zd)); }
                 ProfScope ps(e, PCAD_K_CONV, s);
-                HIP_TRY(launch_conv_dir(xd, e->xzsplit ? E : 2 * E, W.dir[d].conv_w, W.dir[d].conv_b, c.w.xc[d], E, S, L, E, dt, d == 1, e->blocked, e->xzsplit, s));
+                ConvLaunch cv{.x = xd, .ldx = ldxz(), .ldy = E, .S = S, .L = L, .E = E, .dt = dt, .in_blocked = e->xzsplit, .out_blocked = e->blocked};
+                const bool reverse = d == 1;
+                ConvDirection& side = reverse ? cv.rev : cv.fwd;        // launch_conv_dir reads the side that `reverse` names
+                side = {.w = W.dir[d].conv_w, .b = W.dir[d].conv_b, .y = c.w.xc[d]};
+                HIP_TRY(launch_conv_dir(cv, reverse, s));
             }
             return PCAD_OK;
         }
@@ -258,19 +284,23 @@ struct Walk {
         } else
         for (int rep = 0; rep < reps(PCAD_K_GEMM_IN); ++rep)
         { ProfScope ps(e, PCAD_K_GEMM_IN, s);
-        if (pl.fold) HIP_TRY(launch_gemm_nt_two(c.w.u, Dp, W.W_in_f, D, c.w.xz, c.w.zb, E, true, rows, 2 * E, D, dt, s, c.w.rstd));
-        else if (sp) HIP_TRY(launch_gemm_nt_two(c.w.u, 2 * D, W.W_in_s, 2 * D, c.w.xz, c.w.zb, E, true, rows, 2 * E, 3 * D, BF16, s, nullptr, F32, D / 64));
-        else if (e->xzsplit) HIP_TRY(launch_gemm_nt_two(c.w.u, D, W.W_in, D, c.w.xz, c.w.zb, E, true, rows, 2 * E, D, dt, s));
-        else HIP_TRY(launch_gemm_nt(c.w.u, D, W.W_in, D, c.w.xz, 2 * E, rows, 2 * E, D, dt, dt, false, s)); }
+        if (pl.fold)        // on the un-normalised rows (Dp apart), W_in . diag(w_norm) folded at bind time: scaled by the row's rstd
+            HIP_TRY(launch_gemm_nt_two({.A = c.w.u, .lda = Dp, .W = W.W_in_f, .ldw = D, .M = rows, .N = 2 * E, .K = D, .dt = dt},
+                                       {.C1 = c.w.xz, .C2 = c.w.zb, .nsplit = E, .out_blocked = true, .rscale = c.w.rstd}, s));
+        else HIP_TRY(in_proj(c, W, rows, 0, c.w.xz, c.w.zb)); }
         // conv1d + SiLU, causal and anti-causal from one read of x (fused with x_proj of both directions when possible)
         if (convx_fused(rows)) for (int rep = 0; rep < reps(PCAD_K_CONV); ++rep) {
             ProfScope ps(e, PCAD_K_CONV, s);
-            HIP_TRY(launch_convx(c.w.xz, W.convw, sp ? W.dir[0].Wx_s : W.dir[0].Wx, c.w.xc[0], c.w.dtl[0], c.w.bc[0], sp ? W.dir[1].Wx_s : W.dir[1].Wx, c.w.xc[1],
-                                 c.w.dtl[1], c.w.bc[1], S, L, E, dt, s, Rp, sp, sp, c.w.cxp, 2 * B));      // sp: dt_low as bf16 [hi | lo] for the scan's split dt_proj
+            ConvxLaunch cx{.x = c.w.xz, .convw = W.convw, .S = S, .L = L, .E = E, .dt = dt, .Rp = Rp,
+                           .dtl_split = sp,        // dt_low as bf16 [hi | lo] for the scan's split dt_proj
+                           .w_split = sp, .part_ws = c.w.cxp, .policy_S = 2 * B};
+            for (int d = 0; d < 2; ++d) cx.dir[d] = {.Wx = sp ? W.dir[d].Wx_s : W.dir[d].Wx, .xc = c.w.xc[d], .dtl = c.w.dtl[d], .bc = c.w.bc[d]};
+            HIP_TRY(launch_convx(cx, s));
         } else {
             ProfScope ps(e, PCAD_K_CONV, s);
-            HIP_TRY(launch_conv_bidir(c.w.xz, e->xzsplit ? E : 2 * E, W.dir[0].conv_w, W.dir[0].conv_b, W.dir[1].conv_w,
-                                      W.dir[1].conv_b, c.w.xc[0], c.w.xc[1], S, L, E, dt, e->blocked, s, e->xzsplit));
+            HIP_TRY(launch_conv_bidir({.x = c.w.xz, .ldx = ldxz(), .fwd = {.w = W.dir[0].conv_w, .b = W.dir[0].conv_b, .y = c.w.xc[0]},
+                                       .rev = {.w = W.dir[1].conv_w, .b = W.dir[1].conv_b, .y = c.w.xc[1]}, .S = S, .L = L, .E = E, .dt = dt,
+                                       .in_blocked = e->xzsplit, .out_blocked = e->blocked}, s));
         }
         return PCAD_OK;
     }
@@ -280,12 +310,13 @@ struct Walk {
         const int64_t rows = (int64_t)S * L;
         const bool dts = this->dts(rows), strict = pl.strict, ys_from_scan = this->ys_from_scan(li);
         if (pair(rows, li)) {
-            const DirWeights &d0 = W.dir[0], &d1 = W.dir[1];
-            const ScanDirection f{c.w.xc[0], c.w.dtl[0], dts ? d0.Wdt_s : d0.Wdt, c.w.bc[0], d0.A2, d0.Dskip, d0.dt_bias};
-            const ScanDirection r{c.w.xc[1], c.w.dtl[1], dts ? d1.Wdt_s : d1.Wdt, c.w.bc[1], d1.A2, d1.Dskip, d1.dt_bias};
+            ScanPairLaunch pw{.fwd = scan_dir(c, W, 0, dts), .rev = scan_dir(c, W, 1, dts), .z = c.w.zb, .lddt = lddt(dts), .Rp = Rp, .y = c.w.y,
+                              .S = S, .L = L, .E = E, .dt = dt, .gate_each = !e->gate_once, .ws = c.w.pair, .ysplit = ys_from_scan ? c.w.ys : nullptr,
+                              .dt_split = dts};
             for (int ph = 1; ph <= 2; ++ph) {
                 ProfScope ps(e, PCAD_K_SCAN, s);
-                HIP_TRY(launch_scan_pair(f, r, c.w.zb, dts ? 2 * Rp : Rp, Rp, c.w.y, S, L, E, !e->gate_once, dt, s, c.w.pair, ys_from_scan ? c.w.ys : nullptr, dts, ph));
+                pw.phases = ph;
+                HIP_TRY(launch_scan_pair(pw, s));
             }
             return PCAD_OK;
         }
@@ -293,11 +324,12 @@ struct Walk {
             const DirWeights& dw = W.dir[d];
             // x_proj -> dt_low [rows, Rp] (model dtype, zero padded) and B_t | C_t [rows, 32] (fp32 side output)
             if (!convx_fused(rows)) { ProfScope ps(e, PCAD_K_GEMM_X, s);
-            HIP_TRY(launch_gemm_nt_split(c.w.xc[d], E, dw.Wx, E, c.w.dtl[d], Rp, c.w.bc[d], 2 * N, Rp, rows, XP, E, dt, s, e->blocked)); }
+            HIP_TRY(launch_gemm_nt_split({.A = c.w.xc[d], .lda = E, .W = dw.Wx, .ldw = E, .M = rows, .N = XP, .K = E, .dt = dt, .a_blocked = e->blocked},
+                                         {.C = c.w.dtl[d], .ldc = Rp, .C2 = c.w.bc[d], .ldc2 = 2 * N, .nsplit = Rp}, s)); }
+            const ScanLaunch base = scan_of(c, W, d, dts);
             // dt_proj (on MFMA inside the scan) + bias + softplus + recurrence + D skip + SiLU(z) gate
             for (int rep = 1; rep < (d == 0 ? reps(PCAD_K_SCAN) : 1); ++rep)         // measurement aid: the forward-direction launch is idempotent
-                HIP_TRY(launch_scan(c.w.xc[d], nullptr, e->xzsplit ? E : 2 * E, nullptr, c.w.dtl[d], dts ? 2 * Rp : Rp, dts ? dw.Wdt_s : dw.Wdt, Rp, c.w.bc[d], dw.A2, 1.0f,
-                                    dw.Dskip, dw.dt_bias, c.w.y, S, L, E, false, 0, dt, s, e->blocked, e->xzsplit, c.w.seg, 0, nullptr, dts, 2 * B));
+                HIP_TRY(launch_scan(base, s));       // ungated, whole walk, into y
             ProfScope ps(e, PCAD_K_SCAN, s);
             const void* zp = e->xzsplit ? c.w.zb : (const void*)((const char*)c.w.xz + (size_t)E * esz);
             if (pl.untied && d == 1) zp = e->xzsplit ? c.w.zb2 : (const void*)((const char*)c.w.xz2 + (size_t)E * esz);      // its own in_proj's z
@@ -305,10 +337,14 @@ struct Walk {
             // to the sum (one SiLU per element instead of two, z read once; a rounding-order difference from
             // y_f*g + y_r*g, like the out_proj fold below).  PCAD_GATE_EACH=1: each direction gated and rounded.
             const bool gated = strict || !e->gate_once || d == 1;
-            HIP_TRY(launch_scan(c.w.xc[d], gated ? zp : nullptr, e->xzsplit ? E : 2 * E, nullptr, c.w.dtl[d], dts ? 2 * Rp : Rp, dts ? dw.Wdt_s : dw.Wdt, Rp,
-                                c.w.bc[d], dw.A2, 1.0f, dw.Dskip, dw.dt_bias, d == 1 ? y_rev(c) : c.w.y, S, L, E, d == 1,
-                                strict ? 0 : (d == 1 ? (e->gate_once ? 2 : 1) : 0), dt, s, e->blocked, e->xzsplit, c.w.seg, last_short(li) ? pl.walk_len : 0,
-                                d == 1 && ys_from_scan ? c.w.ys : nullptr, dts, 2 * B));
+            ScanLaunch sc = base;
+            sc.z = gated ? zp : nullptr;
+            sc.y = d == 1 ? y_rev(c) : c.w.y;
+            sc.reverse = d == 1;
+            sc.accumulate = strict ? 0 : (d == 1 ? (e->gate_once ? 2 : 1) : 0);
+            sc.walk_len = last_short(li) ? pl.walk_len : 0;
+            sc.ysplit = d == 1 && ys_from_scan ? c.w.ys : nullptr;
+            HIP_TRY(launch_scan(sc, s));
         }
         return PCAD_OK;
     }
@@ -348,7 +384,8 @@ struct Walk {
         const LayerWeights& W = e->layers[li];
         const int64_t rows = (int64_t)2 * c.Bc * L;
         { ProfScope ps(e, PCAD_K_GEMM_OUT_RES, s);
-        HIP_TRY(launch_gemm_nt_res(c.w.y, E, W.W_out_p, E, c.w.u, (float*)c.w.res, c.w.ssq, rows, Dp, E, dt, s, e->blocked)); }
+        HIP_TRY(launch_gemm_nt_res({.A = c.w.y, .lda = E, .W = W.W_out_p, .ldw = E, .M = rows, .N = Dp, .K = E, .dt = dt, .a_blocked = e->blocked},
+                                   {.C = c.w.u, .res = (float*)c.w.res, .ssq = c.w.ssq}, s)); }
         ProfScope ps(e, PCAD_K_RSTD, s);
         HIP_TRY(launch_rstd(c.w.ssq, c.w.rstd, rows, Dp / 128, D, eps, s));
         return PCAD_OK;

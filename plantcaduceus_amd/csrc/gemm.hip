@@ -318,13 +318,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_kernel(const T* __res
     epilogue(pm0, pn0);
 }
 
-// =====================================================================================================================
-// 256x256-tile variant for the square-ish projections (in_proj, out_proj): 8 waves as 2(M) x 4(N), wave tile 128x64 =
-// 8x4 MFMA tiles (128 accumulator registers).  Per flop it moves 33 % fewer L2->LDS bytes and 25 % fewer LDS->register
-// bytes than the 256x128 / 64x64 kernel above, which the ablation showed to be what that kernel is bound by.  Each K-tile
-// is four phases of 16 MFMAs (m-half x k-half); the ds_read_b128 of the next phase's fragments are issued before the
-// current phase's MFMAs (four 16-register fragment sets rotate).  (Its first form, a 2-stage ring with all eight DMAs of
-// K-tile g+2 behind one barrier, is gone: the ring kernels below replaced it — DESIGN.md §3.)
+// 256x256 tiles of the square-ish projections (in_proj, out_proj), for the ring kernels below.  8 waves as 2(M) x 4(N), wave tile
+// 128x64 = 8x4 MFMA tiles (128 accumulator registers): per flop 33 % fewer L2->LDS bytes and 25 % fewer LDS->register bytes than the
+// 256x128 / 64x64 kernel above, which the ablation showed to be what that kernel is bound by.  Each K-tile is four phases of 16
+// MFMAs (m-half x k-half); the ds_read_b128 of the next phase's fragments are issued before the current phase's MFMAs (four
+// 16-register fragment sets rotate).
 constexpr int BM2 = 256, BN2 = 256;
 constexpr int A2_BYTES = BM2 * ROWB, W2_BYTES = BN2 * ROWB;     // 32 KiB each
 
@@ -1088,48 +1086,34 @@ static int persistent_grid(int nblk) {
 }
 
 template <typename T, typename OutT, bool ROUND>
-static hipError_t launch_gemm_t(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                                int64_t M, int N, int K, hipStream_t s, bool a_blocked, int ksplit = 0) {
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (N + BN - 1) / BN;
+static hipError_t launch_gemm_t(const GemmOperands& g, void* C, int64_t ldc, hipStream_t s) {
+    const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (g.N + BN - 1) / BN;
     const bool vec = ((ldc * (int64_t)sizeof(OutT)) % 16 == 0) && (((uintptr_t)C) % 16 == 0);
-    dim3 grid((unsigned)persistent_grid(tiles_m * tiles_n)), block(GEMM_THREADS);
-    if (vec) {
-        auto kfn = gemm_nt_kernel<T, OutT, ROUND, true, false>;
-        if (hipError_t ae = ensure_dynamic_lds((const void*)kfn, GEMM_LDS)) return ae;
-        hipLaunchKernelGGL(kfn, grid, block, GEMM_LDS, s, (const T*)A, lda, (const T*)W, ldw, (OutT*)C, ldc, M, N, K,
-                           tiles_m, tiles_n, (float*)nullptr, (int64_t)0, 0, (int)a_blocked, ksplit);
-    } else {
-        auto kfn = gemm_nt_kernel<T, OutT, ROUND, false, false>;
-        if (hipError_t ae = ensure_dynamic_lds((const void*)kfn, GEMM_LDS)) return ae;
-        hipLaunchKernelGGL(kfn, grid, block, GEMM_LDS, s, (const T*)A, lda, (const T*)W, ldw, (OutT*)C, ldc, M, N, K,
-                           tiles_m, tiles_n, (float*)nullptr, (int64_t)0, 0, (int)a_blocked, ksplit);
-    }
+    const auto kfn = vec ? gemm_nt_kernel<T, OutT, ROUND, true, false> : gemm_nt_kernel<T, OutT, ROUND, false, false>;
+    if (hipError_t ae = ensure_dynamic_lds((const void*)kfn, GEMM_LDS)) return ae;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)persistent_grid(tiles_m * tiles_n)), dim3(GEMM_THREADS), GEMM_LDS, s, (const T*)g.A, g.lda, (const T*)g.W, g.ldw,
+                       (OutT*)C, ldc, g.M, g.N, g.K, tiles_m, tiles_n, (float*)nullptr, (int64_t)0, 0, (int)g.a_blocked, g.ksplit);
     return hipGetLastError();
 }
 
 template <typename T>
-static hipError_t launch_gemm_split_t(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                                      float* C2, int64_t ldc2, int nsplit, int64_t M, int N, int K, hipStream_t s,
-                                      bool a_blocked) {
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (N + BN - 1) / BN;
-    dim3 grid((unsigned)persistent_grid(tiles_m * tiles_n)), block(GEMM_THREADS);
-    auto kfn = gemm_nt_kernel<T, T, false, true, true>;
+static hipError_t launch_gemm_split_t(const GemmOperands& g, const GemmSplitOut& o, hipStream_t s) {
+    const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (g.N + BN - 1) / BN;
+    const auto kfn = gemm_nt_kernel<T, T, false, true, true>;
     if (hipError_t ae = ensure_dynamic_lds((const void*)kfn, GEMM_LDS)) return ae;
-    hipLaunchKernelGGL(kfn, grid, block, GEMM_LDS, s, (const T*)A, lda, (const T*)W, ldw, (T*)C, ldc, M, N, K, tiles_m,
-                       tiles_n, C2, ldc2, nsplit, (int)a_blocked, 0);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)persistent_grid(tiles_m * tiles_n)), dim3(GEMM_THREADS), GEMM_LDS, s, (const T*)g.A, g.lda, (const T*)g.W, g.ldw,
+                       (T*)o.C, o.ldc, g.M, g.N, g.K, tiles_m, tiles_n, o.C2, o.ldc2, o.nsplit, (int)g.a_blocked, 0);
     return hipGetLastError();
 }
 
-hipError_t launch_gemm_nt_split(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* C2,
-                                int64_t ldc2, int nsplit, int64_t M, int N, int K, int dt, hipStream_t s, bool a_blocked) {
-    if (M <= 0 || N <= 0) return hipSuccess;
-    const int esz = dt == BF16 ? 2 : 4;
-    if (K <= 0 || (K * esz) % ROWB || nsplit % 16 || (N - nsplit) % 16) return hipErrorInvalidValue;
-    if ((lda * esz) % 16 || (ldw * esz) % 16 || ((uintptr_t)A) % 16 || ((uintptr_t)W) % 16) return hipErrorInvalidValue;
-    if ((ldc * esz) % 16 || ((uintptr_t)C) % 16 || (ldc2 * 4) % 16 || ((uintptr_t)C2) % 16) return hipErrorInvalidValue;
-    if (a_blocked && (lda * esz) % 128) return hipErrorInvalidValue;
-    if (dt == BF16) return launch_gemm_split_t<bf16_t>(A, lda, W, ldw, C, ldc, C2, ldc2, nsplit, M, N, K, s, a_blocked);
-    return launch_gemm_split_t<float>(A, lda, W, ldw, C, ldc, C2, ldc2, nsplit, M, N, K, s, a_blocked);
+hipError_t launch_gemm_nt_split(const GemmOperands& g, const GemmSplitOut& o, hipStream_t s) {
+    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+    const int esz = g.dt == BF16 ? 2 : 4;
+    if (g.K <= 0 || (g.K * esz) % ROWB || o.nsplit % 16 || (g.N - o.nsplit) % 16 || g.ksplit) return hipErrorInvalidValue;
+    if ((g.lda * esz) % 16 || (g.ldw * esz) % 16 || ((uintptr_t)g.A) % 16 || ((uintptr_t)g.W) % 16) return hipErrorInvalidValue;
+    if ((o.ldc * esz) % 16 || ((uintptr_t)o.C) % 16 || (o.ldc2 * 4) % 16 || ((uintptr_t)o.C2) % 16) return hipErrorInvalidValue;
+    if (g.a_blocked && (g.lda * esz) % 128) return hipErrorInvalidValue;
+    return g.dt == BF16 ? launch_gemm_split_t<bf16_t>(g, o, s) : launch_gemm_split_t<float>(g, o, s);
 }
 
 // shapes the 4-wave kernel takes: whole 256 x 256 tiles, unsigned 32-bit buffer offsets
@@ -1140,65 +1124,76 @@ static bool quad_ok(int64_t lda, int64_t ldw, int64_t M, int N, bool two, int ns
            (int64_t)N * ldw * esz_ < ((int64_t)1 << 32) - 65536;
 }
 
+// Where a 256x256 launch writes: one tensor, or (C2 != nullptr) columns [0, nsplit) -> C and [nsplit, N) -> C2.
+struct Gemm256Out {
+    void* C;  int64_t ldc;
+    void* C2 = nullptr;  int nsplit = 0;
+    bool out_blocked = false;
+    int epi_kind = EPI_NONE;                            // a fused epilogue: the 4-wave kernel only
+    GemmEpi epi = {nullptr, nullptr, nullptr};
+};
+
+// the 4-wave kernel of an epilogue kind; nullptr: no such kernel (the fused epilogues exist for OutT == T only)
+template <typename T, typename OutT>
+static auto gemm256q_for(int epi_kind) -> decltype(&gemm256q_kernel<T, OutT, EPI_NONE>) {
+    if constexpr (std::is_same<T, OutT>::value) {
+        if (epi_kind == EPI_SCALE) return gemm256q_kernel<T, OutT, EPI_SCALE>;
+        if (epi_kind == EPI_RES) return gemm256q_kernel<T, OutT, EPI_RES>;
+    }
+    return epi_kind == EPI_NONE ? gemm256q_kernel<T, OutT, EPI_NONE> : nullptr;
+}
+
 // OutT != T only as <bf16_t, float>: bf16 operands, fp32 result stored as fp32 (the split-bf16 GEMMs of the fp32 model, api.hip
-// "f32_gemm_split"); the fused epilogues exist for OutT == T only.
+// "f32_gemm_split").
 template <typename T, typename OutT = T>
-static hipError_t launch_gemm256_t(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M,
-                                   int N, int K, hipStream_t s, bool a_blocked, void* C2 = nullptr, int nsplit = 0,
-                                   bool out_blocked = false, int epi_kind = EPI_NONE, GemmEpi epi = GemmEpi{nullptr, nullptr, nullptr},
-                                   int ksplit = 0) {
-    const int tiles_m = (int)((M + BM2 - 1) / BM2), tiles_n = (N + BN2 - 1) / BN2;
-    dim3 grid((unsigned)persistent_grid(tiles_m * tiles_n)), block(GEMM_THREADS);
+static hipError_t launch_gemm256_t(const GemmOperands& g, const Gemm256Out& o, hipStream_t s) {
+    const int tiles_m = (int)((g.M + BM2 - 1) / BM2), tiles_n = (g.N + BN2 - 1) / BN2;
+    const dim3 grid((unsigned)persistent_grid(tiles_m * tiles_n));
     static const bool quad = dev_env("PCAD_GEMM_NOQUAD") == nullptr;   // PCAD_DEV=1 only: the 8-wave kernel for A/B runs
     static const bool epi_swap = dev_env("PCAD_GEMM_EPI_PLAIN") == nullptr;  // 64-byte-contiguous epilogue stores (PCAD_DEV=1 PCAD_GEMM_EPI_PLAIN=1: the interleaved form, for A/B)
-    const bool qok = quad_ok<T>(lda, ldw, M, N, C2 != nullptr, nsplit);
-    if (epi_kind != EPI_NONE && !qok) return hipErrorInvalidValue;             // the fused epilogues exist on the 4-wave kernel only
-#define PCAD_LAUNCH_Q(EPIK)                                                                                                     \
-    do {                                                                                                                        \
-        auto kq = gemm256q_kernel<T, OutT, EPIK>;                                                                               \
-        if (hipError_t ae = ensure_dynamic_lds((const void*)kq, GEMM3_LDS)) return ae;                                          \
-        hipLaunchKernelGGL(kq, grid, dim3(GEMMQ_THREADS), GEMM3_LDS, s, (const T*)A, lda, (const T*)W, ldw, (OutT*)C, ldc, M, N, K, \
-                           tiles_m, tiles_n, (int)a_blocked, (OutT*)C2, nsplit, (int)out_blocked, (int)epi_swap, epi, ksplit); \
-                                                                                             \
-        return hipGetLastError();                                                                                               \
-    } while (0)
-    if constexpr (std::is_same<T, OutT>::value) {
-        if (epi_kind == EPI_SCALE) PCAD_LAUNCH_Q(EPI_SCALE);
-        if (epi_kind == EPI_RES) PCAD_LAUNCH_Q(EPI_RES);
-    } else if (epi_kind != EPI_NONE) {
-        return hipErrorInvalidValue;
+    const bool qok = quad_ok<T>(g.lda, g.ldw, g.M, g.N, o.C2 != nullptr, o.nsplit);
+    if (o.epi_kind != EPI_NONE && !qok) return hipErrorInvalidValue;             // the fused epilogues exist on the 4-wave kernel only
+    if (o.epi_kind != EPI_NONE || (quad && qok)) {
+        const auto kq = gemm256q_for<T, OutT>(o.epi_kind);
+        if (!kq) return hipErrorInvalidValue;
+        if (hipError_t ae = ensure_dynamic_lds((const void*)kq, GEMM3_LDS)) return ae;
+        hipLaunchKernelGGL(kq, grid, dim3(GEMMQ_THREADS), GEMM3_LDS, s, (const T*)g.A, g.lda, (const T*)g.W, g.ldw, (OutT*)o.C, o.ldc, g.M, g.N, g.K,
+                           tiles_m, tiles_n, (int)g.a_blocked, (OutT*)o.C2, o.nsplit, (int)o.out_blocked, (int)epi_swap, o.epi, g.ksplit);
+        return hipGetLastError();
     }
-    if (quad && qok) PCAD_LAUNCH_Q(EPI_NONE);
-#undef PCAD_LAUNCH_Q
-    auto kr = gemm256r_kernel<T, OutT>;
+    const auto kr = gemm256r_kernel<T, OutT>;
     if (hipError_t ae = ensure_dynamic_lds((const void*)kr, GEMM3_LDS)) return ae;
-    hipLaunchKernelGGL(kr, grid, block, GEMM3_LDS, s, (const T*)A, lda, (const T*)W, ldw, (OutT*)C, ldc, M, N, K, tiles_m,
-                       tiles_n, (int)a_blocked, (OutT*)C2, nsplit, (int)out_blocked, ksplit);
+    hipLaunchKernelGGL(kr, grid, dim3(GEMM_THREADS), GEMM3_LDS, s, (const T*)g.A, g.lda, (const T*)g.W, g.ldw, (OutT*)o.C, o.ldc, g.M, g.N, g.K, tiles_m,
+                       tiles_n, (int)g.a_blocked, (OutT*)o.C2, o.nsplit, (int)o.out_blocked, g.ksplit);
     return hipGetLastError();
+}
+
+// the 256x256 launch of an (operand, output) dtype pair: bf16 -> fp32, or OutT == T
+static hipError_t launch_gemm256(const GemmOperands& g, int out_dt, const Gemm256Out& o, hipStream_t s) {
+    if (g.dt == BF16 && out_dt == F32) return launch_gemm256_t<bf16_t, float>(g, o, s);
+    return g.dt == BF16 ? launch_gemm256_t<bf16_t>(g, o, s) : launch_gemm256_t<float>(g, o, s);
 }
 
 // in_proj form on the 256x256 kernel: columns [0, nsplit) -> C1, [nsplit, N) -> C2: two separate tensors of nsplit and
 // N - nsplit columns, plain (contiguous rows) or both in the blocked layout.
-hipError_t launch_gemm_nt_two(const void* A, int64_t lda, const void* W, int64_t ldw, void* C1, void* C2, int nsplit,
-                              bool out_blocked, int64_t M, int N, int K, int dt, hipStream_t s, const float* rscale, int out_dt, int ksplit) {
-    if (M <= 0 || N <= 0) return hipSuccess;
+hipError_t launch_gemm_nt_two(const GemmOperands& g, const GemmTwoOut& o, hipStream_t s) {
+    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+    const int dt = g.dt, N = g.N, K = g.K, nsplit = o.nsplit, ksplit = g.ksplit;
     const int esz = dt == BF16 ? 2 : 4;
-    if (out_dt < 0) out_dt = dt;
+    const int out_dt = o.out_dt < 0 ? dt : o.out_dt;
     const int osz = out_dt == BF16 ? 2 : 4;
-    if (K <= 0 || (K * esz) % ROWB || nsplit % 16 || N % 16 || nsplit <= 0 || nsplit >= N) return hipErrorInvalidValue;
-    if ((lda * esz) % 16 || (ldw * esz) % 16 || ((uintptr_t)A) % 16 || ((uintptr_t)W) % 16) return hipErrorInvalidValue;
-    if (((uintptr_t)C1) % 16 || ((uintptr_t)C2) % 16) return hipErrorInvalidValue;
-    if (out_blocked && ((nsplit * osz) % 128 || ((N - nsplit) * osz) % 128)) return hipErrorInvalidValue;
-    const int ek = rscale ? EPI_SCALE : EPI_NONE;
-    const GemmEpi epi{rscale, nullptr, nullptr};
+    if (K <= 0 || (K * esz) % ROWB || nsplit % 16 || N % 16 || nsplit <= 0 || nsplit >= N || g.a_blocked) return hipErrorInvalidValue;
+    if ((g.lda * esz) % 16 || (g.ldw * esz) % 16 || ((uintptr_t)g.A) % 16 || ((uintptr_t)g.W) % 16) return hipErrorInvalidValue;
+    if (((uintptr_t)o.C1) % 16 || ((uintptr_t)o.C2) % 16) return hipErrorInvalidValue;
+    if (o.out_blocked && ((nsplit * osz) % 128 || ((N - nsplit) * osz) % 128)) return hipErrorInvalidValue;
     if (out_dt != dt) {                    // bf16 operands -> fp32 outputs (split-bf16 in_proj of the fp32 model)
-        if (dt != BF16 || out_dt != F32 || rscale) return hipErrorInvalidValue;
+        if (dt != BF16 || out_dt != F32 || o.rscale) return hipErrorInvalidValue;
         if (ksplit && (ksplit < 0 || K != 3 * ksplit * (ROWB / 2))) return hipErrorInvalidValue;     // K = 3 Ko, ksplit = Ko / 64 K-tiles per part
-        return launch_gemm256_t<bf16_t, float>(A, lda, W, ldw, C1, nsplit, M, N, K, s, false, C2, nsplit, out_blocked, EPI_NONE, epi, ksplit);
+    } else if (ksplit) {
+        return hipErrorInvalidValue;
     }
-    if (ksplit) return hipErrorInvalidValue;
-    if (dt == BF16) return launch_gemm256_t<bf16_t>(A, lda, W, ldw, C1, nsplit, M, N, K, s, false, C2, nsplit, out_blocked, ek, epi);
-    return launch_gemm256_t<float>(A, lda, W, ldw, C1, nsplit, M, N, K, s, false, C2, nsplit, out_blocked, ek, epi);
+    return launch_gemm256(g, out_dt, {.C = o.C1, .ldc = nsplit, .C2 = o.C2, .nsplit = nsplit, .out_blocked = o.out_blocked,
+                                      .epi_kind = o.rscale ? EPI_SCALE : EPI_NONE, .epi = {o.rscale, nullptr, nullptr}}, s);
 }
 
 bool gemm_fold_shapes_ok(int64_t M, int D, int E, int dt) {
@@ -1211,51 +1206,40 @@ bool gemm_fold_shapes_ok(int64_t M, int D, int E, int dt) {
     return in_ok && out_ok && (D * esz) % ROWB == 0 && (E * esz) % ROWB == 0 && M * (int64_t)Dp * 4 < ((int64_t)1 << 32);
 }
 
-hipError_t launch_gemm_nt_res(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, float* res, float* ssq, int64_t M,
-                              int N, int K, int dt, hipStream_t s, bool a_blocked) {
-    if (M <= 0 || N <= 0) return hipSuccess;
-    const int esz = dt == BF16 ? 2 : 4;
-    if (K <= 0 || (K * esz) % ROWB || !res || !ssq || !C) return hipErrorInvalidValue;
-    if ((lda * esz) % 16 || (ldw * esz) % 16 || ((uintptr_t)A) % 16 || ((uintptr_t)W) % 16 || ((uintptr_t)res) % 16) return hipErrorInvalidValue;
-    if (a_blocked && (lda * esz) % 128) return hipErrorInvalidValue;
+hipError_t launch_gemm_nt_res(const GemmOperands& g, const GemmResOut& o, hipStream_t s) {
+    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+    const int esz = g.dt == BF16 ? 2 : 4;
+    if (g.K <= 0 || (g.K * esz) % ROWB || !o.res || !o.ssq || !o.C || g.ksplit) return hipErrorInvalidValue;
+    if ((g.lda * esz) % 16 || (g.ldw * esz) % 16 || ((uintptr_t)g.A) % 16 || ((uintptr_t)g.W) % 16 || ((uintptr_t)o.res) % 16) return hipErrorInvalidValue;
+    if (g.a_blocked && (g.lda * esz) % 128) return hipErrorInvalidValue;
     // (Tried and removed, profiles/r04_ab_runs.txt r04d / r04e / r04g: delaying block b by ((b / 8) % 8) eighths of a tile so that an
     // eighth of the CUs is in its epilogue at a time - no effect with the fragment layout, 2.096 vs 2.097 ms.  Ablations: residual
     // loads from cache 1.94 ms, no write-back 1.90, neither 1.71 = the plain out_proj; i.e. the 4.3 GB of extra traffic costs
     // 0.37 ms, about half of its HBM time, the rest is hidden behind the mainloops.  Also removed: pulling the NEXT tile's residual
     // towards L2 with 8 throw-away loads per wave during a tile's last K-tile (so that the tile-start loads hit) - out_proj + residual
     // 2.05 -> 2.29 ms: the extra requests in the mainloop cost more than the tile-start latency they hide, r04l.)
-    const GemmEpi epi{nullptr, res, ssq};
-    if (dt == BF16) return launch_gemm256_t<bf16_t>(A, lda, W, ldw, C, N, M, N, K, s, a_blocked, nullptr, 0, false, EPI_RES, epi);
-    return launch_gemm256_t<float>(A, lda, W, ldw, C, N, M, N, K, s, a_blocked, nullptr, 0, false, EPI_RES, epi);
+    return launch_gemm256(g, g.dt, {.C = o.C, .ldc = g.N, .epi_kind = EPI_RES, .epi = {nullptr, o.res, o.ssq}}, s);
 }
 
-hipError_t launch_gemm_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M,
-                          int N, int K, int dt, int out_dt, bool round_bf16, hipStream_t s, bool a_blocked, int ksplit) {
-    if (M <= 0 || N <= 0) return hipSuccess;
+hipError_t launch_gemm_nt(const GemmOperands& g, const GemmPlainOut& o, hipStream_t s) {
+    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+    const int dt = g.dt, out_dt = o.out_dt, ksplit = g.ksplit;
     const int esz = dt == BF16 ? 2 : 4;
-    if (K <= 0 || (K * esz) % ROWB) return hipErrorInvalidValue;
+    if (g.K <= 0 || (g.K * esz) % ROWB) return hipErrorInvalidValue;
     // wrap-around K cursor: bf16 [hi | lo] operands (2 Ko columns), fp32 result, K = 3 Ko, ksplit = Ko / 64
-    if (ksplit && (ksplit < 0 || dt != BF16 || out_dt != F32 || round_bf16 || K != 3 * ksplit * (ROWB / 2))) return hipErrorInvalidValue;
-    if ((lda * esz) % 16 || (ldw * esz) % 16 || ((uintptr_t)A) % 16 || ((uintptr_t)W) % 16)
+    if (ksplit && (ksplit < 0 || dt != BF16 || out_dt != F32 || o.round_bf16 || g.K != 3 * ksplit * (ROWB / 2))) return hipErrorInvalidValue;
+    if ((g.lda * esz) % 16 || (g.ldw * esz) % 16 || ((uintptr_t)g.A) % 16 || ((uintptr_t)g.W) % 16)
         return hipErrorInvalidValue;
-    if (a_blocked && (lda * esz) % 128) return hipErrorInvalidValue;
+    if (g.a_blocked && (g.lda * esz) % 128) return hipErrorInvalidValue;
     static const bool no256 = dev_env("PCAD_GEMM_NO256") != nullptr;      // PCAD_DEV=1 only: force the 256x128 kernel
     const int osz = out_dt == BF16 ? 2 : 4;
-    const bool big = !no256 && M >= 2048 && N >= 512 && N % 16 == 0 && (out_dt == dt || (dt == BF16 && out_dt == F32 && !round_bf16)) &&
-                     (ldc * osz) % 16 == 0 && ((uintptr_t)C) % 16 == 0;
-    if (big) {
-        if (dt == BF16 && out_dt == F32)
-            return launch_gemm256_t<bf16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked, nullptr, 0, false, EPI_NONE, GemmEpi{nullptr, nullptr, nullptr}, ksplit);
-        if (dt == BF16) return launch_gemm256_t<bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked);
-        return launch_gemm256_t<float>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked);
-    }
-    if (dt == BF16 && out_dt == BF16)
-        return launch_gemm_t<bf16_t, bf16_t, false>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked);
+    const bool big = !no256 && g.M >= 2048 && g.N >= 512 && g.N % 16 == 0 && (out_dt == dt || (dt == BF16 && out_dt == F32 && !o.round_bf16)) &&
+                     (o.ldc * osz) % 16 == 0 && ((uintptr_t)o.C) % 16 == 0;
+    if (big) return launch_gemm256(g, out_dt, {.C = o.C, .ldc = o.ldc}, s);
+    if (dt == BF16 && out_dt == BF16) return launch_gemm_t<bf16_t, bf16_t, false>(g, o.C, o.ldc, s);
     if (dt == BF16 && out_dt == F32)
-        return round_bf16 ? launch_gemm_t<bf16_t, float, true>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked)
-                          : launch_gemm_t<bf16_t, float, false>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked, ksplit);
-    if (dt == F32 && out_dt == F32)
-        return launch_gemm_t<float, float, false>(A, lda, W, ldw, C, ldc, M, N, K, s, a_blocked);
+        return o.round_bf16 ? launch_gemm_t<bf16_t, float, true>(g, o.C, o.ldc, s) : launch_gemm_t<bf16_t, float, false>(g, o.C, o.ldc, s);
+    if (dt == F32 && out_dt == F32) return launch_gemm_t<float, float, false>(g, o.C, o.ldc, s);
     return hipErrorInvalidValue;
 }
 

@@ -98,52 +98,65 @@ hipError_t launch_embed_only(const int32_t* ids, const void* emb, const int32_t*
 hipError_t launch_add_round(void* a, const void* b, int64_t n, int dt, hipStream_t s);
 
 // gemm.hip --------------------------------------------------------------------------------------
-// C[M,N] = A[M,K] W[N,K]^T.  K multiple of 128 bytes; lda/ldw multiples of 16 bytes.
-// out_dt: F32 or == dt.  round_bf16: round the fp32 result to bf16 precision before an F32 store.
-// a_blocked: A is in the blocked layout with rows of lda elements.
-// ksplit != 0 (dt == BF16, out_dt == F32 only): the wrap-around K cursor of the split-bf16 GEMMs (api.hip "f32_gemm_split") - both
-// operands are bf16 [hi | lo] tensors of 2 Ko columns, K = 3 Ko, ksplit = Ko / 64 (K-tiles per part): the cursor reads A as hi, lo, hi
-// and W as hi, hi, lo, i.e. C = a_hi w_hi + a_lo w_hi + a_hi w_lo accumulated in fp32 in that order.
-hipError_t launch_gemm_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                          int64_t M, int N, int K, int dt, int out_dt, bool round_bf16, hipStream_t s,
-                          bool a_blocked = false, int ksplit = 0);
+// C[M,N] = A[M,K] W[N,K]^T in four forms that share their operands (GemmOperands) and differ in where the result goes (Gemm*Out).
+// Every option is a named field whose default is its initialiser; the stream is the launchers' last parameter.
+struct GemmOperands {
+    const void* A;  int64_t lda;      // [M, K]; lda / ldw multiples of 16 bytes
+    const void* W;  int64_t ldw;      // [N, K]
+    int64_t M;  int N, K;             // K a multiple of 128 bytes
+    int dt;
+    bool a_blocked = false;           // A is in the blocked layout with rows of lda elements (not the `two` form)
+    // ksplit != 0 (dt == BF16, fp32 result only; plain and `two` forms): the wrap-around K cursor of the split-bf16 GEMMs (api.hip
+    // "f32_gemm_split") - both operands are bf16 [hi | lo] tensors of 2 Ko columns, K = 3 Ko, ksplit = Ko / 64 (K-tiles per part): the
+    // cursor reads A as hi, lo, hi and W as hi, hi, lo, i.e. C = a_hi w_hi + a_lo w_hi + a_hi w_lo accumulated in fp32 in that order.
+    int ksplit = 0;
+};
+struct GemmPlainOut {
+    void* C;  int64_t ldc;
+    int out_dt;                       // F32 or == dt
+    bool round_bf16 = false;          // round the fp32 result to bf16 precision before an F32 store
+};
 // x_proj form: columns [0, nsplit) -> C (dtype dt, ld ldc); columns [nsplit, N) -> C2 (fp32, rounded to dt's
 // precision, ld ldc2).  nsplit % 16 == 0.
-hipError_t launch_gemm_nt_split(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                                float* C2, int64_t ldc2, int nsplit, int64_t M, int N, int K, int dt, hipStream_t s,
-                                bool a_blocked = false);
-
+struct GemmSplitOut { void* C;  int64_t ldc;  float* C2;  int64_t ldc2;  int nsplit; };
 // in_proj form on the 256x256 kernel: columns [0, nsplit) -> C1, [nsplit, N) -> C2 (separate tensors of nsplit and
 // N - nsplit columns; both plain or both blocked).
-// rscale (or nullptr): per-row factor [M] applied to the result before it is rounded (the norm-folded in_proj: rstd of the row).
-// out_dt: -1 = dt; F32 with dt == BF16: bf16 operands, fp32 outputs (no rscale) - the split-bf16 in_proj of the fp32 model, with
-// ksplit = Ko / 64 and [hi | lo] operands as in launch_gemm_nt.
-hipError_t launch_gemm_nt_two(const void* A, int64_t lda, const void* W, int64_t ldw, void* C1, void* C2, int nsplit,
-                              bool out_blocked, int64_t M, int N, int K, int dt, hipStream_t s, const float* rscale = nullptr,
-                              int out_dt = -1, int ksplit = 0);
-
+struct GemmTwoOut {
+    void *C1, *C2;  int nsplit;
+    bool out_blocked = false;
+    const float* rscale = nullptr;    // per-row factor [M] applied to the result before it is rounded (the norm-folded in_proj: rstd of the row)
+    // -1 = dt; F32 with dt == BF16: bf16 operands, fp32 outputs (no rscale) - the split-bf16 in_proj of the fp32 model, with
+    // ksplit = Ko / 64 and [hi | lo] operands
+    int out_dt = -1;
+};
 // out_proj of the norm-folded layer form, on the 4-wave kernel only (gemm_fold_shapes_ok):
 //   res [M, N] fp32 (FRAGMENT layout, common.hpp res_frag_off) += A . W^T (in place);  C [M, N] (plain rows, dtype dt; unused for
 //   fp32: see api.hip) = round(res);  ssq [M, N / 128] = per-row partial
 //   sums of squares of the updated residual, one per 128-column wave tile (deterministic; reduced by launch_rstd).
-hipError_t launch_gemm_nt_res(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, float* res, float* ssq, int64_t M,
-                              int N, int K, int dt, hipStream_t s, bool a_blocked);
+struct GemmResOut { void* C;  float* res;  float* ssq; };
+hipError_t launch_gemm_nt(const GemmOperands& g, const GemmPlainOut& o, hipStream_t s);
+hipError_t launch_gemm_nt_split(const GemmOperands& g, const GemmSplitOut& o, hipStream_t s);
+hipError_t launch_gemm_nt_two(const GemmOperands& g, const GemmTwoOut& o, hipStream_t s);
+hipError_t launch_gemm_nt_res(const GemmOperands& g, const GemmResOut& o, hipStream_t s);
 // whether a chunk of M token-rows of a (D, E) model can run the folded form (whole 256 x 256 tiles for both projections)
 bool gemm_fold_shapes_ok(int64_t M, int D, int E, int dt);
 inline int fold_padded_width(int D) { return (D + 255) / 256 * 256; }     // width of res / u in the folded form (l20: 384 -> 512)
 
 // conv.hip --------------------------------------------------------------------------------------
-// out_blocked: yf / yr in the blocked layout (common.hpp::blocked_off), buffers padded to a multiple of 8 rows.
-// in_blocked: x is a [S*L, E] tensor in the blocked layout (ldx ignored).
-hipError_t launch_conv_bidir(const void* x, int64_t ldx, const float* wf, const float* bf, const float* wr,
-                             const float* br, void* yf, void* yr, int S, int L, int E, int dt, bool out_blocked,
-                             hipStream_t s, bool in_blocked = false);
-// One direction ("untied_directions": each direction has its own x): y[t] = silu(b + sum_k w[k] x[t-3+k]) (causal) or, reverse,
-// silu(b + sum_k w[k] x[t+3-k]) (anti-causal), the same arithmetic order per output as launch_conv_bidir.  x / y: plain rows of
-// ldx / ldy elements (multiples of 16 bytes) or the blocked layout (in_blocked / out_blocked; the ld is then ignored); 16-byte
-// aligned pointers; E * elem a multiple of 16 bytes (blocked: of 128).
-hipError_t launch_conv_dir(const void* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int S, int L, int E, int dt,
-                           bool reverse, bool out_blocked, bool in_blocked, hipStream_t s);
+// y[t] = silu(b + sum_k w[k] x[t-3+k]) (fwd: causal) or silu(b + sum_k w[k] x[t+3-k]) (rev: anti-causal).
+struct ConvDirection { const float* w;  const float* b;  void* y; };        // taps [E, 4], bias [E], output (nullptr in launch_conv_bidir: not written)
+struct ConvLaunch {
+    const void* x;  int64_t ldx;      // plain rows of ldx elements (a multiple of 16 bytes), 16-byte aligned
+    ConvDirection fwd, rev;
+    int64_t ldy = 0;                  // launch_conv_dir: elements between plain output rows (launch_conv_bidir writes rows of E)
+    int S, L, E, dt;                  // E * elem a multiple of 16 bytes (blocked: of 128)
+    bool in_blocked = false;          // x is a [S*L, E] tensor in the blocked layout (ldx ignored)
+    bool out_blocked = false;         // y in the blocked layout (common.hpp::blocked_off; ldy ignored), buffers padded to a multiple of 8 rows
+};
+hipError_t launch_conv_bidir(const ConvLaunch& c, hipStream_t s);       // both directions from one read of x
+// One direction ("untied_directions": each direction has its own x): c.rev if `reverse`, else c.fwd (refused if that side's w, b or
+// y is null; the other side is not read) - the same arithmetic order per output as launch_conv_bidir.
+hipError_t launch_conv_dir(const ConvLaunch& c, bool reverse, hipStream_t s);
 
 // convx.hip -------------------------------------------------------------------------------------
 // Fused conv1d+SiLU (both directions) + x_proj (both directions), Rp == 64 or 96: x [S*L, E] blocked -> xc0 / xc1 [S*L, E]
@@ -151,14 +164,20 @@ hipError_t launch_conv_dir(const void* x, int64_t ldx, const float* w, const flo
 size_t convx_packed_bytes(int E, int dt);
 hipError_t launch_pack_convw(const float* wf, const float* bf, const float* wr, const float* br, float* out, int E, int dt,
                              hipStream_t s);
-hipError_t launch_convx(const void* x, const float* convw, const void* Wx0, void* xc0, void* dtl0, float* bc0,
-                        const void* Wx1, void* xc1, void* dtl1, float* bc1, int S, int L, int E, int dt, hipStream_t s, int Rp = 64,
-                        bool dtl_split = false,       // dtl_split (dt == F32): dtl_d is written as bf16 [S*L, 2 Rp] = [hi | lo]
-                        bool w_split = false,         // w_split (dt == F32): Wx_d is the bf16 [Rp + 32, 2E] copy of launch_pack_convx_wsplit and
-                                                      // x_proj runs as three bf16 MFMA products per fp32 product
-                        float* part_ws = nullptr,     // scratch of convx_split_bytes(): small launches split the channel walk over several
-                                                      // blocks per row tile (convx_ksplit) and a second tiny kernel adds their partial x_dbl
-                        int policy_S = 0);            // strands the K-split policy is evaluated for (0: S; see scan_segment_bytes)
+struct ConvxDirection { const void* Wx;  void* xc;  void* dtl;  float* bc; };
+struct ConvxLaunch {
+    const void* x;  const float* convw;
+    ConvxDirection dir[2];            // 0: forward (causal), 1: reverse
+    int S, L, E, dt;
+    int Rp = 64;
+    bool dtl_split = false;           // (dt == F32): dtl_d is written as bf16 [S*L, 2 Rp] = [hi | lo]
+    bool w_split = false;             // (dt == F32): Wx_d is the bf16 [Rp + 32, 2E] copy of launch_pack_convx_wsplit and
+                                      // x_proj runs as three bf16 MFMA products per fp32 product
+    float* part_ws = nullptr;         // scratch of convx_split_bytes(): small launches split the channel walk over several
+                                      // blocks per row tile (convx_ksplit) and a second tiny kernel adds their partial x_dbl
+    int policy_S = 0;                 // strands the K-split policy is evaluated for (0: S; see scan_segment_bytes)
+};
+hipError_t launch_convx(const ConvxLaunch& c, hipStream_t s);
 int convx_ksplit(int S, int L, int E, int dt);        // K-split factor for this launch shape (1: none)
 size_t convx_split_bytes(int S, int L, int E, int dt, int Rp, int policy_S = 0);
 hipError_t launch_pack_convx_wsplit(const float* src, int64_t ld, void* dst, int rows, int E, hipStream_t s);
@@ -167,25 +186,39 @@ hipError_t launch_pack_convx_wsplit(const float* src, int64_t ld, void* dst, int
 inline int padded_dt_rank(int R) { return R <= 64 ? 64 : (R + 31) / 32 * 32; }
 
 // scan.hip --------------------------------------------------------------------------------------
-// Selective scan of one direction.  delta == nullptr: fused dt_proj (delta tile = dt_low[rows, Rp] . Wdt[E, Rp]^T on
-// MFMA inside the kernel, Rp % 32 == 0, zero-padded K);  delta != nullptr: delta [rows, E] read from memory.
-// bc: fp32 [rows, 32] = B_t | C_t.  The recurrence uses A2 * a_scale as the base-2 decay rate: pass
-// (A * log2(e), 1) or (A, log2(e)).
-// uy_blocked: u and y are in the blocked layout (whole-tensor row index s*L + t, buffers padded to 8 rows).
-// z_blocked (needs uy_blocked): z is a separate [S*L, E] tensor in the same blocked layout (ldz ignored).
-// seg_ws (fused dt_proj form only): scratch of scan_segment_bytes(S, L, E) bytes; when given and scan_segments() > 1 the walk of
-// every strand is cut into segments that run as separate workgroups (long sequences with few strands: PlantCAD2's 8 192-bp windows).
-// walk_len (0 or >= L: the whole strand): only the first walk_len steps of the walk are run (forward: rows [0, walk_len); reverse:
-// rows [L - walk_len, L)); the other rows of y are not written.  Ignored when the walk is cut into segments.
-hipError_t launch_scan(const void* u, const void* z, int64_t ldz, const void* delta, const void* dt_low, int64_t lddt,
-                       const void* Wdt, int Rp, const float* bc, const float* A2, float a_scale, const float* Dskip,
-                       const float* dbias, void* y, int S, int L, int E, bool reverse, int accumulate, int dt,
-                       hipStream_t s, bool uy_blocked = false, bool z_blocked = false, float* seg_ws = nullptr, int walk_len = 0,
-                       void* ysplit = nullptr, bool dt_split = false, int policy_S = 0);
-// dt_split (dt == F32, fused dt_proj): dt_low is bf16 [rows, lddt >= 2 Rp] = [hi | lo] and Wdt bf16 [E, 2 Rp] = [hi | lo] (Rp = the padded
-// dt_rank, <= 96): the fp32 model's dt_proj as three bf16 MFMA products per fp32 product ("f32_gemm_split"; K walk hi.hi, lo.hi, hi.lo).
-// ysplit (fp32 engine layouts only: dt == F32, fused dt_proj, blocked u / y / z, L % 8 == 0; reverse gating launch, unsegmented, whole
-// walk): the output is written NOT to y but as out_proj's split-bf16 operand, bf16 [rows8, 2E] blocked = [hi | lo] (pack.hip).
+// One direction's operands.  bc: fp32 [rows, 32] = B_t | C_t.  dt_low [rows, lddt] / Wdt [E, Rp]: the fused dt_proj's operands (null in
+// launch_scan's unfused form, which reads delta from memory).
+struct ScanDirection { const void *u, *dt_low, *Wdt; const float *bc, *A2, *Dskip, *dbias; };
+// Selective scan of one direction.
+struct ScanLaunch {
+    ScanDirection dir;
+    // delta == nullptr: fused dt_proj (delta tile = dt_low[rows, Rp] . Wdt[E, Rp]^T on MFMA inside the kernel, Rp % 32 == 0,
+    // zero-padded K);  delta != nullptr: delta [rows, E] read from memory (lddt / Rp unused).
+    const void* delta = nullptr;
+    const void* z = nullptr;  int64_t ldz = 0;      // the gate (nullptr: ungated output); rows of ldz elements
+    int64_t lddt = 0;  int Rp = 0;
+    float a_scale = 1.0f;             // the recurrence uses A2 * a_scale as the base-2 decay rate: pass (A * log2(e), 1) or (A, log2(e))
+    void* y;
+    int S, L, E, dt;
+    bool reverse = false;
+    int accumulate = 0;               // 1: y += after the gate, each direction rounded; 2 (needs z): (y_prev + y) * silu(z), gated once
+    bool uy_blocked = false;          // u and y are in the blocked layout (whole-tensor row index s*L + t, buffers padded to 8 rows)
+    bool z_blocked = false;           // (needs uy_blocked): z is a separate [S*L, E] tensor in the same blocked layout (ldz ignored)
+    // seg_ws (fused dt_proj form only): scratch of scan_segment_bytes(S, L, E) bytes; when given and scan_segments() > 1 the walk of
+    // every strand is cut into segments that run as separate workgroups (long sequences with few strands: PlantCAD2's 8 192-bp windows).
+    float* seg_ws = nullptr;
+    // walk_len (0 or >= L: the whole strand): only the first walk_len steps of the walk are run (forward: rows [0, walk_len); reverse:
+    // rows [L - walk_len, L)); the other rows of y are not written.  Ignored when the walk is cut into segments.
+    int walk_len = 0;
+    // ysplit (fp32 engine layouts only: dt == F32, fused dt_proj, blocked u / y / z, L % 8 == 0; reverse gating launch, unsegmented, whole
+    // walk): the output is written NOT to y but as out_proj's split-bf16 operand, bf16 [rows8, 2E] blocked = [hi | lo] (pack.hip).
+    void* ysplit = nullptr;
+    // dt_split (dt == F32, fused dt_proj): dt_low is bf16 [rows, lddt >= 2 Rp] = [hi | lo] and Wdt bf16 [E, 2 Rp] = [hi | lo] (Rp = the padded
+    // dt_rank, <= 96): the fp32 model's dt_proj as three bf16 MFMA products per fp32 product ("f32_gemm_split"; K walk hi.hi, lo.hi, hi.lo).
+    bool dt_split = false;
+    int policy_S = 0;                 // strands the segment policy is evaluated for (0: S; see scan_segment_bytes)
+};
+hipError_t launch_scan(const ScanLaunch& a, hipStream_t s);
 
 // Segments per strand for the scan of S strands of L steps over E channels.  Pass A + pass B cost ~1.8x the arithmetic of one
 // walk, and a single wave per SIMD already keeps the VALU ~65 % busy, so cutting only pays when most SIMDs would otherwise idle
@@ -213,7 +246,7 @@ inline int scan_segments(int S, int L, int E, int* seg_blocks) {
     if (seg_blocks) *seg_blocks = sb;
     return G;
 }
-// policy_S (here and in launch_scan / launch_convx; 0: S): the strand count the small-launch policy is evaluated for.  The engine
+// policy_S (here and in ScanLaunch / ConvxLaunch; 0: S): the strand count the small-launch policy is evaluated for.  The engine
 // passes the strands of the WHOLE pcad_forward batch, so that every chunk of a call runs the same form and results do not depend on
 // how the batch was cut into chunks, bit for bit; the scratch is sized for the S strands of the launch.
 inline size_t scan_segment_bytes(int S, int L, int E, int policy_S = 0) {
@@ -230,18 +263,27 @@ inline size_t scan_segment_bytes(int S, int L, int E, int policy_S = 0) {
 // fp32, instead of the reverse): results of a pair walk and of a plain walk agree to bf16 rounding of one addend (fp32 model: to fp32
 // summation order), exactly as the segmented form does - and the form is chosen like it: from the strands of the whole pcad_forward
 // call, governed by "scan_segments".
-struct ScanDirection { const void *u, *dt_low, *Wdt; const float *bc, *A2, *Dskip, *dbias; };
 inline bool scan_pair_wanted(int S, int L, int E) {
     const int64_t waves = (int64_t)S * (E / 64);
     static const int64_t max_waves = [] { const char* v = dev_env("PCAD_PAIR_MAX_WAVES"); return v ? (int64_t)atoll(v) : (int64_t)3584; }();   // PCAD_DEV=1 A/B knob
     return L % 64 == 0 && L >= 128 && waves > 0 && waves <= max_waves && scan_segments(S, L, E, nullptr) == 1;
 }
 inline size_t scan_pair_bytes(int S, int E) { return (size_t)2 * S * 2 * E * 16 * sizeof(float); }     // [dir][S][2][E][16] states
-// u / y / z blocked [S*L (8-row padded), E]; dt_low [S*L, lddt]; Wdt [E, Rp] (dt_split: bf16 [hi | lo] operands as in launch_scan);
-// A2 pre-scaled by log2(e); ws: scan_pair_bytes(S, E); ysplit (fp32 + f32_gemm_split): the gated output as out_proj's [hi | lo] operand.
-hipError_t launch_scan_pair(const ScanDirection& fwd, const ScanDirection& rev, const void* z, int64_t lddt, int Rp, void* y, int S, int L, int E,
-                            bool gate_each, int dt, hipStream_t s, float* ws, void* ysplit = nullptr, bool dt_split = false,
-                            int phases = 3);       // bit 0: the first-half launch, bit 1: the second-half launch
+// u / y / z blocked [S*L (8-row padded), E]; dt_low [S*L, lddt]; Wdt [E, Rp] (dt_split: bf16 [hi | lo] operands as in ScanLaunch);
+// A2 pre-scaled by log2(e).
+struct ScanPairLaunch {
+    ScanDirection fwd, rev;
+    const void* z;
+    int64_t lddt;  int Rp;
+    void* y;
+    int S, L, E, dt;
+    bool gate_each = false;           // each direction gated and rounded (default: the sum of both gated once)
+    float* ws;                        // scan_pair_bytes(S, E)
+    void* ysplit = nullptr;           // (fp32 + f32_gemm_split): the gated output as out_proj's [hi | lo] operand
+    bool dt_split = false;
+    int phases = 3;                   // bit 0: the first-half launch, bit 1: the second-half launch
+};
+hipError_t launch_scan_pair(const ScanPairLaunch& a, hipStream_t s);
 
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor (plain or blocked) -> out[(strand * P + q), E]
@@ -263,7 +305,7 @@ hipError_t launch_embed_xz_gather(const int32_t* ids, const int32_t* comp8, cons
 //   weights     [rows, cols] (fp32 / bf16 source) -> bf16 [rows, 2 cols] = [hi | lo]                    (bind time)
 //   activations fp32 [rows, K] (plain or blocked) -> bf16 [rows, 2 K]    = [hi | lo] (plain or blocked), K % 64 == 0
 // so that a_hi w_hi + a_lo w_hi + a_hi w_lo is ONE bf16 GEMM of 3 K / 64 K-tiles whose cursor wraps around both operands
-// (gemm.hip "wrap-around K cursor": launch_gemm_nt(..., K = 3 K, ksplit = K / 64)) with an fp32 result.
+// (gemm.hip "wrap-around K cursor": launch_gemm_nt with GemmOperands K = 3 K, ksplit = K / 64) with an fp32 result.
 hipError_t launch_pack_split_w(const void* src, int src_dt, int64_t src_ld, void* dst, int rows, int cols, hipStream_t s);
 hipError_t launch_split_rows(const float* src, int64_t src_ld, void* dst, int64_t rows, int K, bool src_blocked, bool dst_blocked,
                              hipStream_t s);       // src_ld: elements between plain source rows (ignored for a blocked source)

@@ -29,7 +29,8 @@ int pcad_causal_conv1d_silu(const void* x, int64_t ldx, const float* w_fwd, cons
     if (!x || !w_fwd || !b_fwd || !w_rev || !b_rev) return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu: null argument");
     if (S < 0 || L < 0 || E <= 0 || E % 8 || ldx < E || ldx % 8)
         return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu: bad shape (E and ldx must be multiples of 8)");
-    HIP_TRY(launch_conv_bidir(x, ldx, w_fwd, b_fwd, w_rev, b_rev, y_fwd, y_rev, S, L, E, dtype, false, (hipStream_t)stream));
+    HIP_TRY(launch_conv_bidir({.x = x, .ldx = ldx, .fwd = {.w = w_fwd, .b = b_fwd, .y = y_fwd}, .rev = {.w = w_rev, .b = b_rev, .y = y_rev},
+                               .S = S, .L = L, .E = E, .dt = dtype}, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -44,7 +45,10 @@ int pcad_causal_conv1d_silu_dir(const void* x, int64_t ldx, const float* w, cons
         return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: the blocked layout needs E * elem to be a multiple of 128 bytes");
     if (((uintptr_t)x) % 16 || ((uintptr_t)y) % 16 || ((uintptr_t)w) % 16)
         return fail(PCAD_ERR_INVALID, "pcad_causal_conv1d_silu_dir: x, y and w must be 16-byte aligned");
-    HIP_TRY(launch_conv_dir(x, ldx, w, b, y, ldy, S, L, E, dtype, reverse != 0, y_blocked != 0, x_blocked != 0, (hipStream_t)stream));
+    ConvLaunch cv{.x = x, .ldx = ldx, .ldy = ldy, .S = S, .L = L, .E = E, .dt = dtype, .in_blocked = x_blocked != 0, .out_blocked = y_blocked != 0};
+    ConvDirection& side = reverse ? cv.rev : cv.fwd;        // launch_conv_dir reads the side that `reverse` names
+    side = {.w = w, .b = b, .y = y};
+    HIP_TRY(launch_conv_dir(cv, reverse != 0, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -70,8 +74,9 @@ int pcad_conv_xproj_bidir(const void* x, const float* w_fwd, const float* b_fwd,
     if (S == 0 || L == 0) return PCAD_OK;
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(launch_pack_convw(w_fwd, b_fwd, w_rev, b_rev, (float*)scratch, E, dtype, s));
-    HIP_TRY(launch_convx(x, (const float*)scratch, Wx_fwd, xc_fwd, dtl_fwd, bc_fwd, Wx_rev, xc_rev, dtl_rev, bc_rev, S, L, E,
-                         dtype, s, Rp));
+    HIP_TRY(launch_convx({.x = x, .convw = (const float*)scratch,
+                          .dir = {{.Wx = Wx_fwd, .xc = xc_fwd, .dtl = dtl_fwd, .bc = bc_fwd}, {.Wx = Wx_rev, .xc = xc_rev, .dtl = dtl_rev, .bc = bc_rev}},
+                          .S = S, .L = L, .E = E, .dt = dtype, .Rp = Rp}, s));
     return PCAD_OK;
 }
 
@@ -119,8 +124,10 @@ int pcad_conv_xproj_bidir_engine(const void* x, const float* w_fwd, const float*
         HIP_TRY(launch_pack_convx_wsplit((const float*)Wx_rev, E, p1, Rp + 32, E, s));
         W0 = p0; W1 = p1;
     }
-    hipError_t err = launch_convx(x, (const float*)scratch, W0, xc_fwd, dtl_fwd, bc_fwd, W1, xc_rev, dtl_rev, bc_rev, S, L, E, dtype, s, Rp,
-                                  dtl_split != 0, w_split != 0, (float*)part_ws, policy_S);
+    hipError_t err = launch_convx({.x = x, .convw = (const float*)scratch,
+                                   .dir = {{.Wx = W0, .xc = xc_fwd, .dtl = dtl_fwd, .bc = bc_fwd}, {.Wx = W1, .xc = xc_rev, .dtl = dtl_rev, .bc = bc_rev}},
+                                   .S = S, .L = L, .E = E, .dt = dtype, .Rp = Rp, .dtl_split = dtl_split != 0, .w_split = w_split != 0,
+                                   .part_ws = (float*)part_ws, .policy_S = policy_S}, s);
     if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "pcad_conv_xproj_bidir_engine: unsupported shape / form");
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_conv_xproj_bidir_engine: %s", hipGetErrorString(err));
     return PCAD_OK;
@@ -141,8 +148,9 @@ int pcad_selective_scan(const void* u, const void* delta, const void* z, int64_t
     if (int rc = scan_args_ok(u, bc, A, Dskip, delta_bias, y, S, L, E)) return rc;
     if (S == 0 || L == 0) return PCAD_OK;
     // raw A is scaled by log2(e) when the kernel loads it into registers (the engine passes pre-scaled A)
-    HIP_TRY(launch_scan(u, z, ldz, delta, nullptr, 0, nullptr, 0, bc, A, 1.4426950408889634f, Dskip, delta_bias, y, S, L,
-                        E, reverse != 0, accumulate, dtype, (hipStream_t)stream));
+    HIP_TRY(launch_scan({.dir = {.u = u, .bc = bc, .A2 = A, .Dskip = Dskip, .dbias = delta_bias}, .delta = delta, .z = z, .ldz = ldz,
+                         .a_scale = 1.4426950408889634f, .y = y, .S = S, .L = L, .E = E, .dt = dtype, .reverse = reverse != 0, .accumulate = accumulate},
+                        (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -156,8 +164,10 @@ int pcad_selective_scan_dtproj(const void* u, const void* dt_low, int64_t lddt, 
         return fail(PCAD_ERR_INVALID, "pcad_selective_scan_dtproj: Rp must be a multiple of 32 (zero padded), rows 16-byte aligned");
     if (int rc = scan_args_ok(u, bc, A, Dskip, delta_bias, y, S, L, E)) return rc;
     if (S == 0 || L == 0) return PCAD_OK;
-    HIP_TRY(launch_scan(u, z, ldz, nullptr, dt_low, lddt, Wdt, Rp, bc, A, 1.4426950408889634f, Dskip, delta_bias, y, S, L,
-                        E, reverse != 0, accumulate, dtype, (hipStream_t)stream));
+    HIP_TRY(launch_scan({.dir = {.u = u, .dt_low = dt_low, .Wdt = Wdt, .bc = bc, .A2 = A, .Dskip = Dskip, .dbias = delta_bias}, .z = z, .ldz = ldz,
+                         .lddt = lddt, .Rp = Rp, .a_scale = 1.4426950408889634f, .y = y, .S = S, .L = L, .E = E, .dt = dtype,
+                         .reverse = reverse != 0, .accumulate = accumulate},
+                        (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -196,8 +206,11 @@ int pcad_selective_scan_engine(const void* u, const void* dt_low, int64_t lddt, 
         return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: tensors must be 16-byte aligned");
     if (seg_ws && (((uintptr_t)seg_ws) % 16 || seg_ws_bytes < scan_segment_bytes(S, L, E, policy_S)))
         return fail(PCAD_ERR_WORKSPACE, "pcad_selective_scan_engine: seg_ws must be 16-byte aligned and pcad_scan_segment_scratch_bytes large");
-    hipError_t err = launch_scan(u, z, E, nullptr, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, delta_bias, y, S, L, E, reverse != 0, accumulate,
-                                 dtype, (hipStream_t)stream, true, true, (float*)seg_ws, walk_len, ysplit, dt_split != 0, policy_S);
+    hipError_t err = launch_scan({.dir = {.u = u, .dt_low = dt_low, .Wdt = Wdt, .bc = bc, .A2 = A2, .Dskip = Dskip, .dbias = delta_bias}, .z = z, .ldz = E,
+                                  .lddt = lddt, .Rp = Rp, .a_scale = a_scale, .y = y, .S = S, .L = L, .E = E, .dt = dtype, .reverse = reverse != 0,
+                                  .accumulate = accumulate, .uy_blocked = true, .z_blocked = true, .seg_ws = (float*)seg_ws, .walk_len = walk_len,
+                                  .ysplit = ysplit, .dt_split = dt_split != 0, .policy_S = policy_S},
+                                 (hipStream_t)stream);
     if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_engine: unsupported shape / form (see include/pcad.h)");
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_selective_scan_engine: %s", hipGetErrorString(err));
     return PCAD_OK;
@@ -219,9 +232,11 @@ int pcad_selective_scan_pair(const void* u_fwd, const void* dt_low_fwd, const vo
         if (((uintptr_t)p) % 16) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: tensors must be 16-byte aligned");
     if (((uintptr_t)ws) % 16 || ws_bytes < scan_pair_bytes(S, E))
         return fail(PCAD_ERR_WORKSPACE, "pcad_selective_scan_pair: ws must be 16-byte aligned and pcad_scan_pair_scratch_bytes large");
-    const ScanDirection f{u_fwd, dt_low_fwd, Wdt_fwd, bc_fwd, A2_fwd, Dskip_fwd, delta_bias_fwd};
-    const ScanDirection r{u_rev, dt_low_rev, Wdt_rev, bc_rev, A2_rev, Dskip_rev, delta_bias_rev};
-    hipError_t err = launch_scan_pair(f, r, z, lddt, Rp, y, S, L, E, gate_each != 0, dtype, (hipStream_t)stream, (float*)ws, ysplit, dt_split != 0, phases);
+    hipError_t err = launch_scan_pair({.fwd = {.u = u_fwd, .dt_low = dt_low_fwd, .Wdt = Wdt_fwd, .bc = bc_fwd, .A2 = A2_fwd, .Dskip = Dskip_fwd, .dbias = delta_bias_fwd},
+                                       .rev = {.u = u_rev, .dt_low = dt_low_rev, .Wdt = Wdt_rev, .bc = bc_rev, .A2 = A2_rev, .Dskip = Dskip_rev, .dbias = delta_bias_rev},
+                                       .z = z, .lddt = lddt, .Rp = Rp, .y = y, .S = S, .L = L, .E = E, .dt = dtype, .gate_each = gate_each != 0,
+                                       .ws = (float*)ws, .ysplit = ysplit, .dt_split = dt_split != 0, .phases = phases},
+                                      (hipStream_t)stream);
     if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "pcad_selective_scan_pair: unsupported shape (L %% 64 == 0; bf16: Rp 64 or 96; see include/pcad.h)");
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_selective_scan_pair: %s", hipGetErrorString(err));
     return PCAD_OK;
@@ -230,7 +245,8 @@ int pcad_selective_scan_pair(const void* u_fwd, const void* dt_low_fwd, const vo
 int pcad_gemm_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int N, int K,
                  int dtype, int out_dtype, pcad_stream stream) {
     if (!A || !W || !C) return fail(PCAD_ERR_INVALID, "pcad_gemm_nt: null argument");
-    hipError_t err = launch_gemm_nt(A, lda, W, ldw, C, ldc, M, N, K, dtype, out_dtype, false, (hipStream_t)stream);
+    hipError_t err = launch_gemm_nt({.A = A, .lda = lda, .W = W, .ldw = ldw, .M = M, .N = N, .K = K, .dt = dtype}, {.C = C, .ldc = ldc, .out_dt = out_dtype},
+                                    (hipStream_t)stream);
     if (err == hipErrorInvalidValue)
         return fail(PCAD_ERR_INVALID, "pcad_gemm_nt: K*elem must be a multiple of 128 bytes; A/W 16-byte aligned rows");
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_gemm_nt: %s", hipGetErrorString(err));
@@ -256,7 +272,8 @@ int pcad_gemm_nt_split(const float* A, int64_t lda, const float* W, int64_t ldw,
     HIP_TRY(launch_split_rows(A, lda, As, M, K, false, false, s));                // [hi | lo]
     HIP_TRY(launch_pack_split_w(W, PCAD_F32, ldw, Ws, N, K, s));                  // [hi | lo]
     // 3 K / 64 K-tiles, the cursor wrapping around both operands: a_hi w_hi + a_lo w_hi + a_hi w_lo
-    hipError_t err = launch_gemm_nt(As, 2 * (int64_t)K, Ws, 2 * (int64_t)K, C, ldc, M, N, 3 * K, BF16, F32, false, s, false, K / 64);
+    hipError_t err = launch_gemm_nt({.A = As, .lda = 2 * (int64_t)K, .W = Ws, .ldw = 2 * (int64_t)K, .M = M, .N = N, .K = 3 * K, .dt = BF16, .ksplit = K / 64},
+                                    {.C = C, .ldc = ldc, .out_dt = F32}, s);
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_gemm_nt_split: %s", hipGetErrorString(err));
     return PCAD_OK;
 }
@@ -267,7 +284,8 @@ int pcad_gemm_nt_residual(const void* A, int64_t lda, const void* W, int64_t ldw
     if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: bad dtype");
     if (M < 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || M * (int64_t)N * 4 >= ((int64_t)1 << 32))
         return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: M and N must be multiples of 256 and M * N * 4 < 2^32");
-    hipError_t err = launch_gemm_nt_res(A, lda, W, ldw, C, res, ssq, M, N, K, dtype, (hipStream_t)stream, false);
+    hipError_t err = launch_gemm_nt_res({.A = A, .lda = lda, .W = W, .ldw = ldw, .M = M, .N = N, .K = K, .dt = dtype}, {.C = C, .res = res, .ssq = ssq},
+                                        (hipStream_t)stream);
     if (err == hipErrorInvalidValue)
         return fail(PCAD_ERR_INVALID, "pcad_gemm_nt_residual: K*elem must be a multiple of 128 bytes; 16-byte aligned rows; tensors < 4 GiB");
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "pcad_gemm_nt_residual: %s", hipGetErrorString(err));

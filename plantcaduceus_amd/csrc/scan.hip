@@ -29,7 +29,9 @@
 //     (profiles/r06a_kpmc_scan_pc2m_8192.txt: SQ_WAIT_ANY).
 // VALU/transcendental bound (measured on gfx950: v_exp_f32 8.5, v_fma_f32 3.7, v_pk_fma_f32 5.2 cycles per
 // wave-instruction at 4 waves/SIMD, not overlapping): ~19 cycles per (t, channel, state).
+#include <array>
 #include <cstdlib>
+#include <initializer_list>
 #include <type_traits>
 
 #include "common.hpp"
@@ -576,18 +578,7 @@ __global__ __launch_bounds__(64, PRE == 96 ? PCAD_SCAN_OCC96 : PCAD_SCAN_OCC) vo
 
 // Both directions of one layer in ONE launch (engine layouts only: fused dt_proj, blocked u / y / z, L % 64 == 0): blocks [0, n) run
 // the forward body on direction 0's operands, blocks [n, 2n) the reverse body on direction 1's.  PHASE 3 / 4 = scan_body's SEG.
-template <typename T>
-struct ScanDirArgs {
-    const T* u;            // conv output of the direction (xc)
-    const T* dsrc;         // dt_low
-    const T* Wdt;
-    const float* bc;
-    const float* A2;
-    const float* Dskip;
-    const float* dbias;
-    float* seg_state;      // [S][2][E][16] fp32: slot (strand, 1) carries the state between the two launches
-};
-
+// seg0 / seg1: [S][2][E][16] fp32 per direction: slot (strand, 1) carries the state between the two launches.
 // (Every operand is its own __restrict__ kernel argument: B_t | C_t are fetched through the scalar unit only when the compiler can
 // prove that the kernel's stores do not clobber them - with the pointers inside a by-value struct it could not, the B | C rows
 // arrived through eight vector loads per step and the kernel ran 2.3x slower.)
@@ -632,152 +623,228 @@ __global__ __launch_bounds__(256) void scan_carry_kernel(float* __restrict__ seg
     }
 }
 
-template <typename T, bool FUSED, int PRE = 0, bool BLK8 = false, bool ZB = false>
-static hipError_t launch_scan_t(const void* u, const void* z, int64_t ldz, const void* dsrc, int64_t ldd,
-                                const void* Wdt, int Rp, const float* bc, const float* A2, float a_scale,
-                                const float* Dskip, const float* dbias, void* y, int S, int L, int E, bool reverse,
-                                int accumulate, hipStream_t s, bool uyb, bool zblk = false, float* seg_ws = nullptr, int walk_len = 0,
-                                void* ysplit = nullptr, bool dt_split = false, int policy_S = 0) {
-    const int dts = dt_split ? 1 : 0;
-    const int Sp = policy_S > 0 ? policy_S : S;          // strands the segment policy is evaluated for (kernels.hpp scan_segment_bytes)
-    dim3 grid((unsigned)((int64_t)(E / 64) * S)), block(64);          // 1-D: the kernel maps blocks to (strand, channel block) XCD-affinely
-    const bool hz = z != nullptr;
-    if (ysplit != nullptr) {
-        // out_proj's split-bf16 operand written by the walk itself: the fp32 engine's reverse (gating) launch only
-        if constexpr (std::is_same<T, float>::value && FUSED && BLK8 && ZB) {
-            const bool seg = seg_ws && scan_segments(Sp, L, E, nullptr) > 1;
-            if (!reverse || !hz || (accumulate != 1 && accumulate != 2) || seg || (walk_len > 0 && walk_len < L)) return hipErrorInvalidValue;
-#define PCAD_SCAN_SPLITY(ACCM)                                                                                                       \
-            hipLaunchKernelGGL((scan_kernel<T, true, ACCM, true, FUSED, PRE, BLK8, 0, true, true>), grid, block, 0, s, (const T*)u, (const T*)z, ldz, \
-                               (const T*)dsrc, ldd, (const T*)Wdt, Rp, bc, A2, a_scale, Dskip, dbias, (const T*)y, (T*)y, L, E, (int)uyb, (int)zblk, \
-                               1, 0, (float*)nullptr, L, (bf16_t*)ysplit, dts)
-            if (accumulate == 2) PCAD_SCAN_SPLITY(2); else PCAD_SCAN_SPLITY(1);
-#undef PCAD_SCAN_SPLITY
-            return hipGetLastError();
-        } else {
+// ---- host side: decide, then launch ---------------------------------------------------------------------------------
+// The run-time form of a walk: the scan_kernel template arguments that are not the family's.  seg: scan_body's SEG (0 plain walk,
+// 1 / 2 pass A / B of a segmented walk).
+struct ScanForm {
+    bool rev; int acc; bool has_z; int seg; bool splity;
+    bool operator==(const ScanForm& o) const { return rev == o.rev && acc == o.acc && has_z == o.has_z && seg == o.seg && splity == o.splity; }
+};
+// the kernel of `form` in a table of {form, kernel} rows; nullptr: no such kernel
+template <typename Row, size_t N, typename Form>
+static auto find_kernel(const Row (&rows)[N], const Form& form) -> decltype(rows[0].kernel) {
+    for (const Row& r : rows)
+        if (r.form == form) return r.kernel;
+    return nullptr;
+}
+
+// One compile-time family <T, FUSED, PRE, BLK8, ZB> (scan_plan below picks it) and the table of the kernels it contains: a new
+// variant is a row here.  ZB is the family's only for gated rows (an ungated walk reads no z).
+template <typename T, bool FUSED, int PRE, bool BLK8, bool ZB>
+struct ScanFamily {
+    using Kernel = decltype(&scan_kernel<T, false, 0, false, FUSED, PRE, BLK8>);
+    struct Row { ScanForm form; Kernel kernel; };
+    template <bool REV, int ACC, bool HZ, int SEG = 0, bool SPLITY = false>
+    static Row row() { return {{REV, ACC, HZ, SEG, SPLITY}, scan_kernel<T, REV, ACC, HZ, FUSED, PRE, BLK8, SEG, ZB && HZ, SPLITY>}; }
+
+    // dense index of a form (seg 0..2, acc 0..2): the lookup is one load per launch, whatever the number of rows
+    static int slot(const ScanForm& f) { return (((f.seg * 2 + f.rev) * 3 + f.acc) * 2 + f.has_z) * 2 + f.splity; }
+    static Kernel kernel(const ScanForm& f) {        // nullptr: the family has no such kernel
+        static const std::array<Kernel, 72> table = [] {
+            std::array<Kernel, 72> t{};
+            auto add = [&t](std::initializer_list<Row> rows) { for (const Row& r : rows) t[slot(r.form)] = r.kernel; };
+            add({row<false, 0, false>(), row<false, 0, true>(), row<false, 1, false>(), row<false, 1, true>(), row<false, 2, true>(),
+                 row<true, 0, false>(),  row<true, 0, true>(),  row<true, 1, false>(),  row<true, 1, true>(),  row<true, 2, true>()});
+            if constexpr (FUSED)              // segmented walks: pass A of either direction; pass B of the forward walk and of the gated reverse ones
+                add({row<false, 0, false, 1>(), row<true, 0, false, 1>(),
+                     row<false, 0, false, 2>(), row<false, 0, true, 2>(), row<true, 0, true, 2>(), row<true, 1, true, 2>(), row<true, 2, true, 2>()});
+            if constexpr (std::is_same<T, float>::value && FUSED && BLK8 && ZB)
+                // out_proj's split-bf16 operand written by the walk itself: the fp32 engine's reverse (gating) launch only
+                add({row<true, 1, true, 0, true>(), row<true, 2, true, 0, true>()});
+            return t;
+        }();
+        return f.seg >= 0 && f.seg <= 2 && f.acc >= 0 && f.acc <= 2 ? table[slot(f)] : nullptr;
+    }
+};
+
+// The families the library contains.  *_ENGINE: every layout known at compile time (blocked u / y / z, L % 8 == 0): one scalar block
+// offset per 4-step chunk, per-step offsets in the immediates; bf16 with the dt_low operand prefetched (Rp 64 / 96), fp32 with
+// dt_proj on v_mfma_f32_32x32x2_f32 (or the split-bf16 products), unprefetched.
+enum class ScanFamilyId { BF16_ENGINE64, BF16_ENGINE96, BF16_BLK8, BF16_PRE64, BF16_FUSED, BF16_DELTA, F32_ENGINE, F32_FUSED, F32_DELTA };
+
+// What launch_scan decided about a validated ScanLaunch: the family, the walk's form and, for a segmented walk, its cut.
+struct ScanPlan {
+    ScanFamilyId family;
+    ScanForm form;                     // of the plain walk / of pass B
+    int G = 1, seg_blocks = 0;         // G > 1: pass A, carry, pass B over G segments of seg_blocks blocks
+};
+
+static hipError_t scan_plan(const ScanLaunch& a, ScanPlan& p) {
+    const bool fused = a.delta == nullptr;
+    const bool blk8 = a.uy_blocked && a.L % 8 == 0;
+    if (a.dt == BF16) {
+        static const bool nopre96 = dev_env("PCAD_SCAN_NOPRE96") != nullptr;       // PCAD_DEV=1 A/B: the non-prefetching walk instead
+        const bool pre = fused && a.lddt % 8 == 0;
+        if (pre && a.Rp == 64 && blk8 && a.z_blocked) p.family = ScanFamilyId::BF16_ENGINE64;                    // the engine's case
+        else if (!nopre96 && pre && a.Rp == 96 && blk8 && a.z_blocked) p.family = ScanFamilyId::BF16_ENGINE96;   // ... at dt_rank 65..96 (PlantCAD2 Large)
+        else if (pre && a.Rp == 64 && blk8) p.family = ScanFamilyId::BF16_BLK8;
+        else if (pre && a.Rp == 64) p.family = ScanFamilyId::BF16_PRE64;
+        else p.family = fused ? ScanFamilyId::BF16_FUSED : ScanFamilyId::BF16_DELTA;
+    } else {
+        static const bool f32_generic = dev_env("PCAD_SCAN_F32_GENERIC") != nullptr;       // PCAD_DEV=1 A/B: the run-time-layout instantiation
+        if (!f32_generic && fused && blk8 && a.z_blocked) p.family = ScanFamilyId::F32_ENGINE;
+        else p.family = fused ? ScanFamilyId::F32_FUSED : ScanFamilyId::F32_DELTA;
+    }
+    const int Sp = a.policy_S > 0 ? a.policy_S : a.S;          // strands the segment policy is evaluated for (kernels.hpp scan_segment_bytes)
+    const bool hz = a.z != nullptr, reverse = a.reverse;
+    const int accumulate = a.accumulate;
+    if (a.ysplit != nullptr) {
+        // out_proj's split-bf16 operand written by the walk itself: the fp32 engine's reverse (gating) launch only, unsegmented, whole walk
+        const bool seg = a.seg_ws && scan_segments(Sp, a.L, a.E, nullptr) > 1;
+        if (p.family != ScanFamilyId::F32_ENGINE || !reverse || !hz || (accumulate != 1 && accumulate != 2) || seg || (a.walk_len > 0 && a.walk_len < a.L))
             return hipErrorInvalidValue;
-        }
+        p.form = {true, accumulate, true, 0, true};
+        return hipSuccess;
     }
-#define PCAD_SCAN_ARGS(ZP) (const T*)u, (const T*)(ZP), ldz, (const T*)dsrc, ldd, (const T*)Wdt, Rp, bc, A2, a_scale, Dskip, dbias, \
-                           (const T*)y, (T*)y, L, E, (int)uyb, (int)zblk
-#define PCAD_WALK (walk_len > 0 && walk_len < L ? walk_len : L)
     // ---- long strands, few of them: G segments per strand as separate workgroups (pass A, carry, pass B) --------------------
-    if constexpr (FUSED) {
+    if (fused) {
         int sb = 0;
-        const int G = seg_ws ? scan_segments(Sp, L, E, &sb) : 1;
-        const bool combo = (!reverse && accumulate == 0) || (reverse && accumulate == 2 && hz) || (reverse && accumulate == 1 && hz) ||
-                           (reverse && accumulate == 0 && hz);
+        const int G = a.seg_ws ? scan_segments(Sp, a.L, a.E, &sb) : 1;
+        const bool combo = (!reverse && accumulate == 0) || (reverse && hz && (accumulate == 0 || accumulate == 1 || accumulate == 2));
         if (G > 1 && combo) {
-            dim3 gseg((unsigned)((int64_t)(E / 64) * S * G));
-#define PCAD_SEG(REV, ACC, HZ, SEGM, ZP)                                                                                  \
-            hipLaunchKernelGGL((scan_kernel<T, REV, ACC, HZ, FUSED, PRE, BLK8, SEGM, ZB && HZ>), gseg, block, 0, s, PCAD_SCAN_ARGS(ZP), G, sb, seg_ws, L, (bf16_t*)nullptr, dts)
-            if (reverse) PCAD_SEG(true, 0, false, 1, nullptr); else PCAD_SEG(false, 0, false, 1, nullptr);
-            hipLaunchKernelGGL(scan_carry_kernel, dim3((unsigned)(((int64_t)S * E + 255) / 256)), dim3(256), 0, s, seg_ws, A2, a_scale, S, G, E);
-            if (!reverse) { if (hz) PCAD_SEG(false, 0, true, 2, z); else PCAD_SEG(false, 0, false, 2, nullptr); }
-            else if (accumulate == 2) PCAD_SEG(true, 2, true, 2, z);
-            else if (accumulate == 1) PCAD_SEG(true, 1, true, 2, z);
-            else PCAD_SEG(true, 0, true, 2, z);
-#undef PCAD_SEG
-            return hipGetLastError();
+            p.form = {reverse, accumulate, hz, 2, false};
+            p.G = G;
+            p.seg_blocks = sb;
+            return hipSuccess;
         }
     }
-#define PCAD_SCAN(REV, ACC, HZ)                                                                                    \
-    hipLaunchKernelGGL((scan_kernel<T, REV, ACC, HZ, FUSED, PRE, BLK8, 0, ZB && HZ>), grid, block, 0, s, PCAD_SCAN_ARGS(z), 1, 0, (float*)nullptr, PCAD_WALK, (bf16_t*)nullptr, dts)
-    if (accumulate == 2) {                    // (y_prev + y) * silu(z): the bi-directional sum gated once
-        if (!hz) return hipErrorInvalidValue;
-        if (reverse) PCAD_SCAN(true, 2, true); else PCAD_SCAN(false, 2, true);
+    if (accumulate == 2 && !hz) return hipErrorInvalidValue;          // (y_prev + y) * silu(z): the bi-directional sum gated once
+    p.form = {reverse, accumulate == 2 ? 2 : (accumulate ? 1 : 0), hz, 0, false};
+    return hipSuccess;
+}
+
+// The launches of a planned walk in one family.  FUSED: the delta source is dt_low (rows of lddt elements); else delta (rows of E).
+template <typename T, bool FUSED, int PRE = 0, bool BLK8 = false, bool ZB = false>
+static hipError_t launch_scan_t(const ScanLaunch& a, const ScanPlan& p, hipStream_t s) {
+    using Family = ScanFamily<T, FUSED, PRE, BLK8, ZB>;
+    const ScanDirection& d = a.dir;
+    const T* dsrc = (const T*)(FUSED ? d.dt_low : a.delta);
+    const int64_t ldd = FUSED ? a.lddt : a.E;
+    const T* Wdt = FUSED ? (const T*)d.Wdt : nullptr;
+    const int Rp = FUSED ? a.Rp : 0, dts = a.dt_split ? 1 : 0, S = a.S, L = a.L, E = a.E;
+    // 1-D grid: the kernel maps blocks to (strand[, segment], channel block) XCD-affinely
+    auto launch = [&](const ScanForm& f, const T* z, int G, int seg_blocks, float* seg_ws, int walk, bf16_t* ysplit) {
+        const typename Family::Kernel k = Family::kernel(f);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, dim3((unsigned)((int64_t)(E / 64) * S * G)), dim3(64), 0, s, (const T*)d.u, z, a.ldz, dsrc, ldd, Wdt, Rp, d.bc, d.A2, a.a_scale,
+                           d.Dskip, d.dbias, (const T*)a.y, (T*)a.y, L, E, (int)a.uy_blocked, (int)a.z_blocked, G, seg_blocks, seg_ws, walk, ysplit, dts);
+        return hipSuccess;
+    };
+    if (p.G > 1) {
+        if (hipError_t e = launch({p.form.rev, 0, false, 1, false}, nullptr, p.G, p.seg_blocks, a.seg_ws, L, nullptr)) return e;
+        hipLaunchKernelGGL(scan_carry_kernel, dim3((unsigned)(((int64_t)S * E + 255) / 256)), dim3(256), 0, s, a.seg_ws, d.A2, a.a_scale, S, p.G, E);
+        if (hipError_t e = launch(p.form, (const T*)a.z, p.G, p.seg_blocks, a.seg_ws, L, nullptr)) return e;
+    } else {
+        const int walk = !p.form.splity && a.walk_len > 0 && a.walk_len < L ? a.walk_len : L;
+        if (hipError_t e = launch(p.form, (const T*)a.z, 1, 0, nullptr, walk, p.form.splity ? (bf16_t*)a.ysplit : nullptr)) return e;
     }
-    else if (!reverse && !accumulate) { if (hz) PCAD_SCAN(false, 0, true); else PCAD_SCAN(false, 0, false); }
-    else if (!reverse && accumulate) { if (hz) PCAD_SCAN(false, 1, true); else PCAD_SCAN(false, 1, false); }
-    else if (reverse && !accumulate) { if (hz) PCAD_SCAN(true, 0, true); else PCAD_SCAN(true, 0, false); }
-    else { if (hz) PCAD_SCAN(true, 1, true); else PCAD_SCAN(true, 1, false); }
-#undef PCAD_SCAN
-#undef PCAD_WALK
-#undef PCAD_SCAN_ARGS
     return hipGetLastError();
 }
+
+// ---- pair walks ---------------------------------------------------------------------------------------------------------
+struct ScanPairForm {        // scan_pair_kernel's <ACC, HASZ, PHASE, SPLITY>
+    int acc; bool has_z; int phase; bool splity;
+    bool operator==(const ScanPairForm& o) const { return acc == o.acc && has_z == o.has_z && phase == o.phase && splity == o.splity; }
+};
 
 template <typename T, int PRE>
-static hipError_t launch_scan_pair_t(const ScanDirection& f, const ScanDirection& r, const void* z, int64_t lddt, int Rp, void* y, int S, int L, int E,
-                                     bool gate_each, hipStream_t s, float* ws, void* ysplit, bool dt_split, int phases) {
-    const int dts = dt_split ? 1 : 0;
-    const int sb = (L / TB) / 2;                                          // blocks (of TB steps) per half: L % (2 TB) == 0
-    const size_t per_dir = (size_t)S * 2 * E * NSTATE;                   // floats
-    ScanDirArgs<T> d0{(const T*)f.u, (const T*)f.dt_low, (const T*)f.Wdt, f.bc, f.A2, f.Dskip, f.dbias, ws};
-    ScanDirArgs<T> d1{(const T*)r.u, (const T*)r.dt_low, (const T*)r.Wdt, r.bc, r.A2, r.Dskip, r.dbias, ws + per_dir};
-    dim3 grid((unsigned)((int64_t)2 * S * (E / 64))), block(64);
-#define PCAD_PAIR(ACCM, HZ, PH, SPY)                                                                                            \
-    hipLaunchKernelGGL((scan_pair_kernel<T, ACCM, HZ, PRE, PH, SPY>), grid, block, 0, s, d0.u, d0.dsrc, d0.Wdt, d0.bc, d0.A2, d0.Dskip, d0.dbias, \
-                       d0.seg_state, d1.u, d1.dsrc, d1.Wdt, d1.bc, d1.A2, d1.Dskip, d1.dbias, d1.seg_state, (const T*)z, lddt, Rp, 1.0f, (T*)y, L, E, sb, \
-                       (bf16_t*)ysplit, dts)
-    // first halves: forward rows [0, L/2), reverse rows [L/2, L) - ungated (or, "gate_each", each gated and rounded)
-    if (phases & 1) { if (gate_each) PCAD_PAIR(0, true, 3, false); else PCAD_PAIR(0, false, 3, false); }
-    if (!(phases & 2)) return hipGetLastError();
-    // second halves on top of the other direction's first-half output, gated
-    if constexpr (std::is_same<T, float>::value) {
-        if (ysplit) { if (gate_each) PCAD_PAIR(1, true, 4, true); else PCAD_PAIR(2, true, 4, true); return hipGetLastError(); }
-    } else if (ysplit) {
-        return hipErrorInvalidValue;
+struct ScanPairFamily {
+    using Kernel = decltype(&scan_pair_kernel<T, 0, false, PRE, 3, false>);
+    struct Row { ScanPairForm form; Kernel kernel; };
+    template <int ACC, bool HZ, int PHASE, bool SPLITY = false>
+    static Row row() { return {{ACC, HZ, PHASE, SPLITY}, scan_pair_kernel<T, ACC, HZ, PRE, PHASE, SPLITY>}; }
+    static Kernel kernel(const ScanPairForm& f) {
+        // first halves ungated or ("gate_each") gated; second halves gated each / once
+        static const Row rows[] = {row<0, false, 3>(), row<0, true, 3>(), row<1, true, 4>(), row<2, true, 4>()};
+        if (Kernel k = find_kernel(rows, f)) return k;
+        if constexpr (std::is_same<T, float>::value) {
+            static const Row splity[] = {row<1, true, 4, true>(), row<2, true, 4, true>()};
+            return find_kernel(splity, f);
+        }
+        return nullptr;
     }
-    if (gate_each) PCAD_PAIR(1, true, 4, false); else PCAD_PAIR(2, true, 4, false);
-#undef PCAD_PAIR
+};
+
+template <typename T, int PRE>
+static hipError_t launch_scan_pair_t(const ScanPairLaunch& a, hipStream_t s) {
+    const int sb = (a.L / TB) / 2;                                          // blocks (of TB steps) per half: L % (2 TB) == 0
+    float* seg0 = a.ws;                                                     // [dir][S][2][E][16] states
+    float* seg1 = a.ws + (size_t)a.S * 2 * a.E * NSTATE;
+    const ScanDirection &f = a.fwd, &r = a.rev;
+    auto launch = [&](const ScanPairForm& form) {
+        const typename ScanPairFamily<T, PRE>::Kernel k = ScanPairFamily<T, PRE>::kernel(form);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, dim3((unsigned)((int64_t)2 * a.S * (a.E / 64))), dim3(64), 0, s,
+                           (const T*)f.u, (const T*)f.dt_low, (const T*)f.Wdt, f.bc, f.A2, f.Dskip, f.dbias, seg0,
+                           (const T*)r.u, (const T*)r.dt_low, (const T*)r.Wdt, r.bc, r.A2, r.Dskip, r.dbias, seg1,
+                           (const T*)a.z, a.lddt, a.Rp, 1.0f, (T*)a.y, a.L, a.E, sb, (bf16_t*)a.ysplit, a.dt_split ? 1 : 0);
+        return hipSuccess;
+    };
+    // first halves: forward rows [0, L/2), reverse rows [L/2, L) - ungated (or, "gate_each", each gated and rounded)
+    if (a.phases & 1)
+        if (hipError_t e = launch({0, a.gate_each, 3, false})) return e;
+    if (!(a.phases & 2)) return hipGetLastError();
+    // second halves on top of the other direction's first-half output, gated (a bf16 ysplit: no such kernel)
+    if (hipError_t e = launch({a.gate_each ? 1 : 2, true, 4, a.ysplit != nullptr})) return e;
     return hipGetLastError();
 }
 
-hipError_t launch_scan_pair(const ScanDirection& fwd, const ScanDirection& rev, const void* z, int64_t lddt, int Rp, void* y, int S, int L, int E,
-                            bool gate_each, int dt, hipStream_t s, float* ws, void* ysplit, bool dt_split, int phases) {
+hipError_t launch_scan_pair(const ScanPairLaunch& a, hipStream_t s) {
+    const int S = a.S, L = a.L, E = a.E, Rp = a.Rp, dt = a.dt;
+    const int64_t lddt = a.lddt;
     if (S <= 0 || L <= 0) return hipSuccess;
-    if (!ws || !z || E % 64 || L % (2 * TB) || Rp <= 0 || Rp % 32) return hipErrorInvalidValue;
+    if (!a.ws || !a.z || E % 64 || L % (2 * TB) || Rp <= 0 || Rp % 32) return hipErrorInvalidValue;
     const int esz = dt == BF16 ? 2 : 4;
     if ((E * esz) % 128 || ((int64_t)S * L + 7) / 8 * 8 * E * esz >= ((int64_t)1 << 32)) return hipErrorInvalidValue;      // blocked layouts, 32-bit offsets
     if ((int64_t)L * E * 4 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    if (dt_split && !(dt == F32 && Rp <= 96 && lddt % 8 == 0 && lddt >= 2 * Rp)) return hipErrorInvalidValue;
-    if (ysplit && !(dt == F32 && ((int64_t)S * L + 7) / 8 * 8 * 2 * E * 2 < ((int64_t)1 << 32))) return hipErrorInvalidValue;
+    if (a.dt_split && !(dt == F32 && Rp <= 96 && lddt % 8 == 0 && lddt >= 2 * Rp)) return hipErrorInvalidValue;
+    if (a.ysplit && !(dt == F32 && ((int64_t)S * L + 7) / 8 * 8 * 2 * E * 2 < ((int64_t)1 << 32))) return hipErrorInvalidValue;
     if (dt == BF16) {
         if (lddt % 8) return hipErrorInvalidValue;
-        if (Rp == 64) return launch_scan_pair_t<bf16_t, 64>(fwd, rev, z, lddt, Rp, y, S, L, E, gate_each, s, ws, nullptr, false, phases);
-        if (Rp == 96) return launch_scan_pair_t<bf16_t, 96>(fwd, rev, z, lddt, Rp, y, S, L, E, gate_each, s, ws, nullptr, false, phases);
+        if (Rp == 64) return launch_scan_pair_t<bf16_t, 64>(a, s);
+        if (Rp == 96) return launch_scan_pair_t<bf16_t, 96>(a, s);
         return hipErrorInvalidValue;
     }
-    return launch_scan_pair_t<float, 0>(fwd, rev, z, lddt, Rp, y, S, L, E, gate_each, s, ws, ysplit, dt_split, phases);
+    return launch_scan_pair_t<float, 0>(a, s);
 }
 
-hipError_t launch_scan(const void* u, const void* z, int64_t ldz, const void* delta, const void* dt_low, int64_t lddt,
-                       const void* Wdt, int Rp, const float* bc, const float* A2, float a_scale, const float* Dskip,
-                       const float* dbias, void* y, int S, int L, int E, bool reverse, int accumulate, int dt,
-                       hipStream_t s, bool uyb, bool zblk, float* seg_ws, int walk_len, void* ysplit, bool dt_split, int policy_S) {
-    if (zblk && !uyb) return hipErrorInvalidValue;
-    if (dt_split && !(dt == F32 && delta == nullptr && Rp % 32 == 0 && Rp <= 96 && lddt % 8 == 0 && lddt >= 2 * Rp)) return hipErrorInvalidValue;   // bf16 [hi | lo] operands
-    if (ysplit && !(dt == F32 && delta == nullptr && uyb && zblk && L % 8 == 0 && ((int64_t)S * L + 7) / 8 * 8 * 2 * E * 2 < ((int64_t)1 << 32)))
+hipError_t launch_scan(const ScanLaunch& a, hipStream_t s) {
+    const int S = a.S, L = a.L, E = a.E, Rp = a.Rp, dt = a.dt;
+    const int64_t lddt = a.lddt, ldz = a.ldz;
+    if (a.z_blocked && !a.uy_blocked) return hipErrorInvalidValue;
+    if (a.dt_split && !(dt == F32 && a.delta == nullptr && Rp % 32 == 0 && Rp <= 96 && lddt % 8 == 0 && lddt >= 2 * Rp)) return hipErrorInvalidValue;   // bf16 [hi | lo] operands
+    if (a.ysplit && !(dt == F32 && a.delta == nullptr && a.uy_blocked && a.z_blocked && L % 8 == 0 && ((int64_t)S * L + 7) / 8 * 8 * 2 * E * 2 < ((int64_t)1 << 32)))
         return hipErrorInvalidValue;        // the split output exists in the fp32 engine's compile-time-layout instantiation only
     if (S <= 0 || L <= 0) return hipSuccess;
     if (E % 64) return hipErrorInvalidValue;
     if ((int64_t)L * (ldz > E ? ldz : E) * 4 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;   // 32-bit in-strand offsets
-    if (uyb && (((int64_t)S * L + 7) / 8 * 8 * E * (dt == BF16 ? 2 : 4) >= ((int64_t)1 << 32) || (E * (dt == BF16 ? 2 : 4)) % 128))
+    if (a.uy_blocked && (((int64_t)S * L + 7) / 8 * 8 * E * (dt == BF16 ? 2 : 4) >= ((int64_t)1 << 32) || (E * (dt == BF16 ? 2 : 4)) % 128))
         return hipErrorInvalidValue;     // blocked layout: 32-bit whole-tensor offsets
-    const bool fused = delta == nullptr;
-    if (fused && (!dt_low || !Wdt || Rp <= 0 || Rp % 32)) return hipErrorInvalidValue;
-    if (dt == BF16) {
-        if (fused && Rp == 64 && lddt % 8 == 0 && uyb && L % 8 == 0 && zblk)      // the engine's case: every layout known at compile time
-            return launch_scan_t<bf16_t, true, 64, true, true>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
-        static const bool nopre96 = dev_env("PCAD_SCAN_NOPRE96") != nullptr;       // PCAD_DEV=1 A/B: the non-prefetching walk instead
-        if (!nopre96 && fused && Rp == 96 && lddt % 8 == 0 && uyb && L % 8 == 0 && zblk)      // the engine's case at dt_rank 65..96 (PlantCAD2 Large)
-            return launch_scan_t<bf16_t, true, 96, true, true>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
-        if (fused && Rp == 64 && lddt % 8 == 0 && uyb && L % 8 == 0)
-            return launch_scan_t<bf16_t, true, 64, true>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
-        if (fused && Rp == 64 && lddt % 8 == 0)
-            return launch_scan_t<bf16_t, true, 64>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
-        if (fused) return launch_scan_t<bf16_t, true>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
-        return launch_scan_t<bf16_t, false>(u, z, ldz, delta, E, nullptr, 0, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
+    if (a.delta == nullptr && (!a.dir.dt_low || !a.dir.Wdt || Rp <= 0 || Rp % 32)) return hipErrorInvalidValue;
+    ScanPlan p;
+    if (hipError_t e = scan_plan(a, p)) return e;
+    switch (p.family) {
+    case ScanFamilyId::BF16_ENGINE64: return launch_scan_t<bf16_t, true, 64, true, true>(a, p, s);
+    case ScanFamilyId::BF16_ENGINE96: return launch_scan_t<bf16_t, true, 96, true, true>(a, p, s);
+    case ScanFamilyId::BF16_BLK8:     return launch_scan_t<bf16_t, true, 64, true>(a, p, s);
+    case ScanFamilyId::BF16_PRE64:    return launch_scan_t<bf16_t, true, 64>(a, p, s);
+    case ScanFamilyId::BF16_FUSED:    return launch_scan_t<bf16_t, true>(a, p, s);
+    case ScanFamilyId::BF16_DELTA:    return launch_scan_t<bf16_t, false>(a, p, s);
+    case ScanFamilyId::F32_ENGINE:    return launch_scan_t<float, true, 0, true, true>(a, p, s);
+    case ScanFamilyId::F32_FUSED:     return launch_scan_t<float, true>(a, p, s);
+    case ScanFamilyId::F32_DELTA:     return launch_scan_t<float, false>(a, p, s);
     }
-    // the fp32 engine's case (blocked u / y / z, L % 8 == 0): layouts known at compile time like the bf16 instantiation above (one
-    // scalar block offset per 4-step chunk, per-step offsets in the immediates); dt_proj stays on v_mfma_f32_32x32x2_f32, unprefetched
-    static const bool f32_generic = dev_env("PCAD_SCAN_F32_GENERIC") != nullptr;       // PCAD_DEV=1 A/B: the run-time-layout instantiation
-    if (!f32_generic && fused && uyb && L % 8 == 0 && zblk)
-        return launch_scan_t<float, true, 0, true, true>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, ysplit, dt_split, policy_S);
-    if (ysplit) return hipErrorInvalidValue;
-    if (fused) return launch_scan_t<float, true>(u, z, ldz, dt_low, lddt, Wdt, Rp, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, dt_split, policy_S);
-    return launch_scan_t<float, false>(u, z, ldz, delta, E, nullptr, 0, bc, A2, a_scale, Dskip, dbias, y, S, L, E, reverse, accumulate, s, uyb, zblk, seg_ws, walk_len, nullptr, false, policy_S);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace pcad

@@ -4,6 +4,7 @@
     python tools/isa_census.py plantcaduceus_amd/csrc/convx.hip 'convx_kernelItLb1ELi6E'      # mangled-name substring
     python tools/isa_census.py plantcaduceus_amd/csrc/scan.hip  'scan_kernelItLb1ELi2ELb1ELb1ELi64ELb1ELi0ELb1E'
     python tools/isa_census.py --check-res-waits [plantcaduceus_amd/csrc/gemm.hip]     # gemm.hip's hand-counted waits vs the emitted order
+    python tools/isa_census.py --same-kernels OLD.hip NEW.hip [OLD2.hip NEW2.hip ...]     # two versions of a source: same device code?
 
 Finds every loop (a label that a LATER branch jumps back to), takes the one with the most instructions that contains no inner
 loop of its own unless --outer is given, and counts its instructions by issue class: packed / plain / transcendental VALU, MFMA,
@@ -136,7 +137,55 @@ def check_res_waits(src):
     return bad
 
 
+DEVICE_ASM = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-S", "--cuda-device-only"]
+
+
+def _kernels(src):
+    """{symbol: text} of every kernel in `src`'s device assembly: the function from `_Z...:` up to its .Lfunc_end, plus its
+    .amdhsa_kernel descriptor block (registers, LDS, scratch).  The function index inside local labels (.LBB<n>_<m>, .Lfunc_begin<n>,
+    .Lfunc_end<n>) depends on the emission order only and is rewritten to a fixed token."""
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        subprocess.run(DEVICE_ASM + [os.path.basename(src), "-o", out], check=True, capture_output=True, cwd=os.path.dirname(os.path.abspath(src)))
+        txt = open(out).read()
+    # (also inside the loop comments, "in Loop: Header=BB<n>_<m>", whose column depends on the index's digits: runs of blanks -> one)
+    def norm(t):
+        t = re.sub(r"\.L(func_begin|func_end)\d+", r".L\1#", t)
+        t = re.sub(r"(?<![A-Za-z0-9_])(\.L)?BB\d+_", r"\1BB#_", t)
+        return re.sub(r"[ \t]+", " ", t)
+    kernels = {}
+    for m in re.finditer(r"^(_Z\w+):.*?^\.Lfunc_end\d+:", txt, flags=re.M | re.S):
+        kernels[m.group(1)] = norm(m.group(0))
+    for m in re.finditer(r"^\s*\.amdhsa_kernel (\w+)\n.*?^\s*\.end_amdhsa_kernel", txt, flags=re.M | re.S):
+        desc = norm(m.group(0))
+        if m.group(1) in kernels and desc not in kernels[m.group(1)]:       # (this hipcc emits it inside the span already)
+            kernels[m.group(1)] += "\n" + desc
+    return kernels
+
+
+def same_kernels(pairs):
+    """Text comparison, per kernel and independent of emission order, of the device code of (old, new) source pairs."""
+    bad = 0
+    for old, new in pairs:
+        ko, kn = _kernels(old), _kernels(new)
+        same = sum(1 for k in ko if kn.get(k) == ko[k])
+        gone, added = sorted(set(ko) - set(kn)), sorted(set(kn) - set(ko))
+        changed = sorted(k for k in ko if k in kn and kn[k] != ko[k])
+        print(f"{os.path.basename(new)}: {len(ko)} kernels before, {len(kn)} after, {same} identical")
+        for tag, names in (("REMOVED", gone), ("ADDED", added), ("CHANGED", changed)):
+            for k in names:
+                print(f"   {tag}: {k}")
+        bad += len(gone) + len(added) + len(changed)
+    print("same-kernels:", "OK" if bad == 0 else f"{bad} differences")
+    return bad
+
+
 def main():
+    if "--same-kernels" in sys.argv:
+        args = [a for a in sys.argv[1:] if not a.startswith("--")]
+        if not args or len(args) % 2:
+            sys.exit("usage: isa_census.py --same-kernels OLD.hip NEW.hip [OLD2.hip NEW2.hip ...]")
+        sys.exit(1 if same_kernels(list(zip(args[0::2], args[1::2]))) else 0)
     if "--check-res-waits" in sys.argv:
         args = [a for a in sys.argv[1:] if not a.startswith("--")]
         sys.exit(1 if check_res_waits(args[0] if args else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
