@@ -285,6 +285,27 @@ struct ScanPairLaunch {
 };
 hipError_t launch_scan_pair(const ScanPairLaunch& a, hipStream_t s);
 
+// scan_bwd.hip ----------------------------------------------------------------------------------
+// Backward of launch_scan's unfused plain-layout form (pcad_train.h pcad_selective_scan_bwd): inputs as ScanLaunch takes them there (A raw,
+// not scaled), dout / du / ddelta / dz [S, L, E] in dtype dt (dz exactly when z is given), dbc fp32 [S L, 32] = dB_t | dC_t, dA fp32
+// [E, 16], dD / ddbias fp32 [E]; every output is overwritten.  scratch: scan_bwd_bytes(S, L, E) bytes, 256-byte aligned - the states
+// at the chunk boundaries and the partial sums a second kernel adds in index order (no floating-point atomics).
+constexpr int SCAN_BWD_CHUNK = 8;     // walk steps between two stored states = steps whose states one lane keeps in registers
+struct ScanBwdLaunch {
+    const void *u, *delta;
+    const void* z = nullptr;  int64_t ldz = 0;
+    const float *bc, *A, *Dskip, *dbias;
+    const void* dout;
+    void *du, *ddelta;
+    void* dz = nullptr;
+    float *dbc, *dA, *dD, *ddbias;
+    void* scratch;
+    int S, L, E, dt;
+    bool reverse = false;
+};
+size_t scan_bwd_bytes(int S, int L, int E);
+hipError_t launch_scan_bwd(const ScanBwdLaunch& a, hipStream_t s);
+
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor (plain or blocked) -> out[(strand * P + q), E]
 hipError_t launch_gather_rows(const void* src, void* out, int B, int L, int E, Positions pos, int dt, bool blocked,

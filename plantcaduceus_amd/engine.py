@@ -116,6 +116,14 @@ SIGNATURES = {
                                   C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/pcad_train.h declares (libpcad_train.so: the backward operators)
+TRAIN_SIGNATURES = {
+    "pcad_selective_scan_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pcad_selective_scan_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 13 + [C.c_size_t] +
+                                [C.c_int] * 5 + [C.c_void_p]),
+}
+TRAIN_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_train.so")
+
 # include/pcad.h pcad_pooling (pooling_strategy of CaduceusForSequenceClassification)
 POOLING = {"mean": 0, "max": 1, "first": 2, "last": 3}
 MAX_LABELS = 256
@@ -198,6 +206,27 @@ def load_library():
                 f"{LIB_PATH} was built from other kernel sources (pcad_build_hash {built}, sources {have}): rebuild it with "
                 "`make -C plantcaduceus_amd/csrc` / `__graft_entry__.build()` (PCAD_ALLOW_STALE=1 overrides, for A/B of old builds)")
     _lib = lib
+    return lib
+
+
+_train_lib = None
+
+
+def load_train_library():
+    """Load libpcad_train.so (include/pcad_train.h) beside libpcad.so, which it links and which is loaded first; fails loudly if it
+    is missing - a missing backward kernel is an error, there is no fallback to torch."""
+    global _train_lib
+    if _train_lib is not None:
+        return _train_lib
+    load_library()
+    if not os.path.exists(TRAIN_LIB_PATH):
+        raise RuntimeError(f"{TRAIN_LIB_PATH} not found: build it with `make -C plantcaduceus_amd/csrc` / `__graft_entry__.build()`")
+    lib = C.CDLL(TRAIN_LIB_PATH)
+    for name, (res, args) in TRAIN_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _train_lib = lib
     return lib
 
 

@@ -19,7 +19,7 @@ from typing import Optional
 
 import torch
 
-from .engine import _DT, _check, _require_gpu, _stream_ptr, load_library
+from .engine import _DT, _check, _require_gpu, _stream_ptr, load_library, load_train_library
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -321,16 +321,108 @@ def _acc_mode(accumulate_into, gate_sum) -> int:
     return 2 if gate_sum else 1
 
 
+SCAN_BWD_CHUNK = 8       # csrc/kernels.hpp SCAN_BWD_CHUNK: walk steps between two states the backward stores (and re-runs at once)
+
+
+def _guarded(shape, dtype, dev, guard):
+    """an output buffer; guard: NaN where the kernel must write, between one row of sentinels before and one after.
+    -> (tensor of `shape`, the whole buffer or None)"""
+    if not guard:
+        return torch.empty(shape, dtype=dtype, device=dev), None
+    row, n = shape[-1], 1
+    for k in shape:
+        n *= k
+    whole = torch.full((n + 2 * row,), -1234.0, dtype=dtype, device=dev)
+    whole[row:row + n] = float("nan")
+    return whole[row:row + n].view(shape), whole
+
+
+def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False, poison=False):
+    """pcad_selective_scan_bwd on selective_scan_fn's operands (upstream layouts; D, z, delta_bias may be None) and dout (B, E, L).
+    -> namespace(du, ddelta, dz (B, E, L) in u's dtype (dz None without z); dB, dC fp32 (B, 16, L); dA fp32 (E, 16); dD, ddelta_bias fp32
+    (E); guards_ok).  poison (tests): the scratch starts as 0xFF bytes and every output as NaN inside a larger buffer with one row of
+    sentinels before and after it; guards_ok tells whether all sentinels are intact afterwards."""
+    from types import SimpleNamespace
+    _require_gpu(u, "u")
+    lib = load_train_library()
+    Bsz, E, L = u.shape
+    dt, dev = u.dtype, u.device
+    u_tm, z_tm, bc, A32, Dv, db = _scan_common(u, B, C, A, D, z, delta_bias)
+    d_tm = delta.to(dt).transpose(1, 2).contiguous()
+    g_tm = dout.to(dt).transpose(1, 2).contiguous()
+    f32 = torch.float32
+    outs = [_guarded(sh, ty, dev, poison) for sh, ty in (((Bsz, L, E), dt), ((Bsz, L, E), dt), ((Bsz, L, E), dt), ((Bsz, L, 32), f32),
+                                                         ((E, 16), f32), ((E,), f32), ((E,), f32))]
+    du, dd, dz, dbc, dA, dD, dbias = [o[0] for o in outs]
+    if z_tm is None:
+        dz = None
+    nb = lib.pcad_selective_scan_bwd_scratch_bytes(Bsz, L, E)
+    scratch = _nan_bytes(nb, dev) if poison else torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_selective_scan_bwd(u_tm.data_ptr(), d_tm.data_ptr(), z_tm.data_ptr() if z_tm is not None else None, E,
+                                           bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), g_tm.data_ptr(),
+                                           du.data_ptr(), dd.data_ptr(), dz.data_ptr() if dz is not None else None, dbc.data_ptr(),
+                                           dA.data_ptr(), dD.data_ptr(), dbias.data_ptr(), _aligned(scratch), nb, Bsz, L, E,
+                                           int(bool(reverse)), _dt(u_tm), _stream_ptr()), "pcad_selective_scan_bwd")
+    ok = True
+    for t, whole in outs:
+        if whole is not None:
+            row = t.shape[-1]
+            ok = ok and bool((whole[:row] == -1234.0).all()) and bool((whole[row + t.numel():] == -1234.0).all())
+    return SimpleNamespace(du=du.transpose(1, 2), ddelta=dd.transpose(1, 2), dz=dz.transpose(1, 2) if dz is not None else None,
+                           dB=dbc[..., :16].transpose(1, 2), dC=dbc[..., 16:].transpose(1, 2), dA=dA, dD=dD, ddelta_bias=dbias,
+                           guards_ok=ok)
+
+
+class _SelectiveScanFn(torch.autograd.Function):
+    """selective_scan_fn with a backward: the forward is the plain call, the backward pcad_selective_scan_bwd (include/pcad_train.h, libpcad_train.so).
+    Only the inputs are saved; the kernel recomputes the states."""
+
+    @staticmethod
+    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, reverse):
+        ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias)
+        ctx.reverse = bool(reverse)
+        return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, None, False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        u, delta, A, B, C, D, z, delta_bias = ctx.saved_tensors
+        g = selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, ctx.reverse)
+        need = ctx.needs_input_grad
+        return (g.du if need[0] else None,
+                g.ddelta.to(delta.dtype) if need[1] else None,
+                g.dA.to(A.dtype) if need[2] else None,
+                g.dB.to(B.dtype) if need[3] else None,
+                g.dC.to(C.dtype) if need[4] else None,
+                g.dD.to(D.dtype) if D is not None and need[5] else None,
+                g.dz.to(z.dtype) if z is not None and need[6] else None,
+                g.ddelta_bias.to(delta_bias.dtype) if delta_bias is not None and need[7] else None,
+                None)
+
+
 def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
                       return_last_state=False, reverse=False, accumulate_into=None, gate_sum=False):
     """u, delta, z: (B, E, L); A: (E, 16); B, C: (B, 16, L); D, delta_bias: (E).  Returns (B, E, L).
     accumulate_into: add this call's gated output to an earlier one (bi-directional "add"); with gate_sum=True the
-    earlier output is taken as UNGATED (its call had z=None) and SiLU(z) is applied once to the sum (the engine's form)."""
+    earlier output is taken as UNGATED (its call had z=None) and SiLU(z) is applied once to the sum (the engine's form).
+    When any of u, delta, A, B, C, D, z, delta_bias requires grad the call is differentiable (pcad_selective_scan_bwd; either
+    direction): each gradient comes back in its input's shape and dtype.  accumulate_into / gate_sum are inference forms and are
+    refused then - the bidirectional sum is two calls added in torch."""
     _require_gpu(u, "u")
     if not delta_softplus:
         raise NotImplementedError("the Caduceus path always uses delta_softplus=True")
     if return_last_state:
         raise NotImplementedError("return_last_state is not on the Caduceus path")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (u, delta, A, B, C, D, z, delta_bias)):
+        if accumulate_into is not None or gate_sum:
+            raise NotImplementedError("accumulate_into / gate_sum are inference forms: with an input that requires grad, add the "
+                                      "two directions' outputs in torch")
+        return _SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, reverse)
+    return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum)
+
+
+def _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum):
     lib = load_library()
     Bsz, E, L = u.shape
     u_tm, z_tm, bc, A32, Dv, db = _scan_common(u, B, C, A, D, z, delta_bias)
