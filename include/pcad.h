@@ -510,6 +510,41 @@ int pcad_gemm_nt_split(const float* A, int64_t lda, const float* W, int64_t ldw,
 int pcad_gemm_nt_residual(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, float* res, float* ssq,
                           int64_t M, int N, int K, int dtype, pcad_stream stream);
 
+/* Engine forms of the GEMMs: the four launches above with the operands and arguments the engine passes (csrc/forward.hip), for
+ * operator-level tests of the kernels and epilogues a pcad_forward call runs (tests/test_gpu_gemm_forms.py).  The entries pack nothing:
+ * every tensor is taken as the caller built it.  Common to all four:
+ *   A [M, K] (lda), W [N, K] (ldw) dtype, K * elem a multiple of 128 bytes, rows and base addresses 16-byte aligned
+ *   a_blocked  A is in the BLOCKED layout of pcad_conv_xproj_bidir with rows of lda elements (lda * elem a multiple of 128 bytes): the
+ *              byte at offset cb of row r lives at ((r / 8) * pieces + cb / 128) * 1024 + (r % 8) * 128 + cb % 128, pieces =
+ *              lda * elem / 128; the buffer holds M rounded up to 8 rows (csrc/common.hpp blocked_off; plantcaduceus_amd.ops.to_blocked)
+ *   ksplit     0, or the wrap-around K cursor of pcad_gemm_nt_split: A and W are bf16 [hi | lo] tensors of 2 Ko columns, K = 3 Ko,
+ *              ksplit = Ko / 64, the result is fp32 = A_hi W_hi^T + A_lo W_hi^T + A_hi W_lo^T accumulated in that order.  dtype PCAD_BF16
+ *              with out_dtype PCAD_F32 only, and only in pcad_gemm_nt_engine and pcad_gemm_nt_two
+ * PCAD_ERR_INVALID: null / misaligned tensors, rows shorter than the operand, and whatever the launcher of the form rejects; nothing
+ * is launched then.
+ *
+ * pcad_gemm_nt_engine (launch_gemm_nt: out_proj, and in_proj without "xzsplit"): C [M, N] (ldc) out_dtype, PCAD_F32 or dtype.  M >= 2048
+ *   and N >= 512 with N % 16 == 0 run a 256 x 256 kernel (whole tiles: four waves, else eight), everything else the 256 x 128 kernel.
+ * pcad_gemm_nt_xproj (launch_gemm_nt_split: x_proj wherever the fused conv + x_proj kernel is off): columns [0, nsplit) -> C [M, nsplit]
+ *   (ldc) dtype, columns [nsplit, N) -> C2 [M, N - nsplit] (ldc2) fp32 holding values rounded to dtype; nsplit and N - nsplit multiples
+ *   of 16.  Always the 256 x 128 kernel.
+ * pcad_gemm_nt_two (launch_gemm_nt_two: in_proj): columns [0, nsplit) -> C1 [M, nsplit], [nsplit, N) -> C2 [M, N - nsplit], contiguous
+ *   rows, or - out_blocked - both in the blocked layout (nsplit * elem and (N - nsplit) * elem multiples of 128 bytes; buffers of M rounded
+ *   up to 8 rows, padding rows never written).  Always a 256 x 256 kernel: four waves for whole tiles with nsplit % 64 == 0, else eight.
+ *   rscale     NULL, or fp32 [M]: row m of the result is multiplied by rscale[m] before it is rounded (the "norm_fold" in_proj, rscale =
+ *              the row's rstd); whole 256 x 256 tiles and out_dtype == dtype only
+ *   out_dtype  dtype, or PCAD_F32 with dtype PCAD_BF16 (the split-bf16 in_proj of the fp32 model, with ksplit)
+ *   a_blocked  must be 0: the form has no blocked A
+ * pcad_gemm_nt_residual_engine: pcad_gemm_nt_residual with a_blocked (the mixer output y as the scan leaves it). */
+int pcad_gemm_nt_engine(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int N, int K, int a_blocked,
+                        int ksplit, int dtype, int out_dtype, pcad_stream stream);
+int pcad_gemm_nt_xproj(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* C2, int64_t ldc2, int nsplit,
+                       int64_t M, int N, int K, int a_blocked, int ksplit, int dtype, pcad_stream stream);
+int pcad_gemm_nt_two(const void* A, int64_t lda, const void* W, int64_t ldw, void* C1, void* C2, int nsplit, const float* rscale, int64_t M,
+                     int N, int K, int a_blocked, int out_blocked, int ksplit, int dtype, int out_dtype, pcad_stream stream);
+int pcad_gemm_nt_residual_engine(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, float* res, float* ssq, int64_t M, int N,
+                                 int K, int a_blocked, int ksplit, int dtype, pcad_stream stream);
+
 /* Rows of a [2B * L, E] activation tensor (plain rows) that a forward evaluated at positions p_0..p_{P-1} consumes after the
  * last mixer: strand b row p_q and strand B + b row L - 1 - p_q  ->  out [(strand * P + q), E].  positions: HOST int32 [P],
  * P <= PCAD_MAX_POSITIONS.  (The last-layer shortcut of pcad_forward; reference callers read one position:

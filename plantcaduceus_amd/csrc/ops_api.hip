@@ -292,6 +292,79 @@ int pcad_gemm_nt_residual(const void* A, int64_t lda, const void* W, int64_t ldw
     return PCAD_OK;
 }
 
+// ---- the GEMM launch forms of the engine (csrc/forward.hip) as operators: pcad.h "engine forms of the GEMMs" --------------------------
+// what the four entries check alike: dtype, shape, rows that hold the operand, 16-byte alignment.  ksplit: A and W are bf16 [hi | lo]
+// tensors of 2 K / 3 columns.  -> the operands, or a PCAD_ERR_INVALID
+static int gemm_engine_args(const char* who, const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int a_blocked,
+                            int ksplit, int dtype) {
+    if (!A || !W) return fail(PCAD_ERR_INVALID, "%s: null argument", who);
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype", who);
+    const int64_t esz = dtype == PCAD_BF16 ? 2 : 4;
+    if (M < 0 || N <= 0 || K <= 0 || ksplit < 0 || (K * esz) % 128) return fail(PCAD_ERR_INVALID, "%s: K * elem must be a multiple of 128 bytes; M >= 0, N > 0, ksplit >= 0", who);
+    const int64_t cols = ksplit ? 2 * (int64_t)ksplit * 64 : K;                        // columns the cursor reads of either operand
+    if (lda < cols || ldw < cols || (lda * esz) % 16 || (ldw * esz) % 16 || (a_blocked && (lda * esz) % 128))
+        return fail(PCAD_ERR_INVALID, "%s: lda, ldw must hold the operand's columns in 16-byte aligned rows (blocked A: lda * elem a multiple of 128 bytes)", who);
+    if (((uintptr_t)A) % 16 || ((uintptr_t)W) % 16) return fail(PCAD_ERR_INVALID, "%s: A and W must be 16-byte aligned", who);
+    return PCAD_OK;
+}
+
+static int gemm_engine_result(const char* who, hipError_t err) {
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "%s: unsupported shape / form (see include/pcad.h)", who);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_gemm_nt_engine(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int N, int K, int a_blocked,
+                        int ksplit, int dtype, int out_dtype, pcad_stream stream) {
+    const char* who = "pcad_gemm_nt_engine";
+    if (!C) return fail(PCAD_ERR_INVALID, "%s: null argument", who);
+    if (int rc = gemm_engine_args(who, A, lda, W, ldw, M, N, K, a_blocked, ksplit, dtype)) return rc;
+    if (out_dtype != PCAD_F32 && out_dtype != dtype) return fail(PCAD_ERR_INVALID, "%s: out_dtype must be PCAD_F32 or dtype", who);
+    if (ldc < N || (ldc * (out_dtype == PCAD_BF16 ? 2 : 4)) % 16 || ((uintptr_t)C) % 16)
+        return fail(PCAD_ERR_INVALID, "%s: ldc >= N; C in 16-byte aligned rows", who);
+    return gemm_engine_result(who, launch_gemm_nt({.A = A, .lda = lda, .W = W, .ldw = ldw, .M = M, .N = N, .K = K, .dt = dtype, .a_blocked = a_blocked != 0, .ksplit = ksplit},
+                                                  {.C = C, .ldc = ldc, .out_dt = out_dtype}, (hipStream_t)stream));
+}
+
+int pcad_gemm_nt_xproj(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* C2, int64_t ldc2, int nsplit,
+                       int64_t M, int N, int K, int a_blocked, int ksplit, int dtype, pcad_stream stream) {
+    const char* who = "pcad_gemm_nt_xproj";
+    if (!C || !C2) return fail(PCAD_ERR_INVALID, "%s: null argument", who);
+    if (int rc = gemm_engine_args(who, A, lda, W, ldw, M, N, K, a_blocked, ksplit, dtype)) return rc;
+    const int64_t esz = dtype == PCAD_BF16 ? 2 : 4;
+    if (nsplit <= 0 || nsplit >= N || nsplit % 16 || (N - nsplit) % 16 || ldc < nsplit || ldc2 < N - nsplit)
+        return fail(PCAD_ERR_INVALID, "%s: 0 < nsplit < N, both in whole 16-column groups; ldc >= nsplit, ldc2 >= N - nsplit", who);
+    if ((ldc * esz) % 16 || (ldc2 * 4) % 16 || ((uintptr_t)C) % 16 || ((uintptr_t)C2) % 16)
+        return fail(PCAD_ERR_INVALID, "%s: C and C2 in 16-byte aligned rows", who);
+    return gemm_engine_result(who, launch_gemm_nt_split({.A = A, .lda = lda, .W = W, .ldw = ldw, .M = M, .N = N, .K = K, .dt = dtype, .a_blocked = a_blocked != 0, .ksplit = ksplit},
+                                                        {.C = C, .ldc = ldc, .C2 = C2, .ldc2 = ldc2, .nsplit = nsplit}, (hipStream_t)stream));
+}
+
+int pcad_gemm_nt_two(const void* A, int64_t lda, const void* W, int64_t ldw, void* C1, void* C2, int nsplit, const float* rscale, int64_t M,
+                     int N, int K, int a_blocked, int out_blocked, int ksplit, int dtype, int out_dtype, pcad_stream stream) {
+    const char* who = "pcad_gemm_nt_two";
+    if (!C1 || !C2) return fail(PCAD_ERR_INVALID, "%s: null argument", who);
+    if (int rc = gemm_engine_args(who, A, lda, W, ldw, M, N, K, a_blocked, ksplit, dtype)) return rc;
+    if (out_dtype != PCAD_F32 && out_dtype != dtype) return fail(PCAD_ERR_INVALID, "%s: out_dtype must be PCAD_F32 or dtype", who);
+    if (nsplit <= 0 || nsplit >= N || nsplit % 16 || N % 16) return fail(PCAD_ERR_INVALID, "%s: 0 < nsplit < N, both multiples of 16", who);
+    if (((uintptr_t)C1) % 16 || ((uintptr_t)C2) % 16 || ((uintptr_t)rscale) % 4) return fail(PCAD_ERR_INVALID, "%s: C1 and C2 must be 16-byte aligned", who);
+    return gemm_engine_result(who, launch_gemm_nt_two({.A = A, .lda = lda, .W = W, .ldw = ldw, .M = M, .N = N, .K = K, .dt = dtype, .a_blocked = a_blocked != 0, .ksplit = ksplit},
+                                                      {.C1 = C1, .C2 = C2, .nsplit = nsplit, .out_blocked = out_blocked != 0, .rscale = rscale, .out_dt = out_dtype},
+                                                      (hipStream_t)stream));
+}
+
+int pcad_gemm_nt_residual_engine(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, float* res, float* ssq, int64_t M, int N,
+                                 int K, int a_blocked, int ksplit, int dtype, pcad_stream stream) {
+    const char* who = "pcad_gemm_nt_residual_engine";
+    if (!C || !res || !ssq) return fail(PCAD_ERR_INVALID, "%s: null argument", who);
+    if (int rc = gemm_engine_args(who, A, lda, W, ldw, M, N, K, a_blocked, ksplit, dtype)) return rc;
+    if (M % 256 || N % 256 || M * (int64_t)N * 4 >= ((int64_t)1 << 32))
+        return fail(PCAD_ERR_INVALID, "%s: M and N must be multiples of 256 and M * N * 4 < 2^32", who);
+    if (((uintptr_t)C) % 16 || ((uintptr_t)res) % 16 || ((uintptr_t)ssq) % 4) return fail(PCAD_ERR_INVALID, "%s: C and res must be 16-byte aligned", who);
+    return gemm_engine_result(who, launch_gemm_nt_res({.A = A, .lda = lda, .W = W, .ldw = ldw, .M = M, .N = N, .K = K, .dt = dtype, .a_blocked = a_blocked != 0, .ksplit = ksplit},
+                                                      {.C = C, .res = res, .ssq = ssq}, (hipStream_t)stream));
+}
+
 int pcad_gather_rows(const void* src, void* out, int B, int L, int E, const int32_t* positions, int P, int dtype, pcad_stream stream) {
     if (!src || !out) return fail(PCAD_ERR_INVALID, "pcad_gather_rows: null argument");
     if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "pcad_gather_rows: bad dtype");

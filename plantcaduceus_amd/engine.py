@@ -88,6 +88,13 @@ SIGNATURES = {
     "pcad_gemm_nt_split_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "pcad_gemm_nt_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pcad_gemm_nt_engine": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int] * 6 + [C.c_void_p]),
+    "pcad_gemm_nt_xproj": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                     C.c_int64] + [C.c_int] * 5 + [C.c_void_p]),
+    "pcad_gemm_nt_two": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] +
+                         [C.c_int] * 7 + [C.c_void_p]),
+    "pcad_gemm_nt_residual_engine": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] +
+                                     [C.c_int] * 5 + [C.c_void_p]),
     "pcad_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                    C.c_void_p]),
     "pcad_final_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

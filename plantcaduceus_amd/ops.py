@@ -608,6 +608,136 @@ def linear_residual(x, weight, residual):
     return from_res_fragment(frag, M, N), out, ssq
 
 
+# ---- the engine's GEMM launch forms as operators (include/pcad.h "Engine forms of the GEMMs") ----------------------------------------
+# Layout conversion only (to_blocked / from_blocked, the residual's fragment layout): the operands are taken as the caller built them,
+# split [hi | lo] forms included.  Every output starts as NaN between two guards, as `_guarded` does for the scan's backward.
+GUARD = -1024.0                 # exact in bf16 and fp32
+
+
+def _guarded_rows(rows: int, width: int, dtype, dev):
+    """an output of `rows` rows of `width` elements (plain or blocked - the kernel's business): NaN where the kernel must write, a guard
+    of sentinels before and after (whole 128-byte lines, so the output keeps its alignment).  -> (flat [rows * width], whole buffer, guard)"""
+    g = (width + 63) // 64 * 64
+    n = rows * width
+    whole = torch.full((n + 2 * g,), GUARD, dtype=dtype, device=dev)
+    whole[g:g + n] = float("nan")
+    return whole[g:g + n], whole, g
+
+
+def _guards_intact(outs) -> bool:
+    return all(bool((w[:g] == GUARD).all()) and bool((w[w.numel() - g:] == GUARD).all()) for _, w, g in outs)
+
+
+def _gemm_a(a: torch.Tensor, a_blocked: bool, lda_extra: int):
+    """A as a launch takes it: blocked (padding rows NaN), or plain rows with lda_extra NaN columns behind each.  -> (tensor, lda)"""
+    a = a.contiguous()
+    if a_blocked:
+        if lda_extra:
+            raise ValueError("a blocked A has rows of exactly its own width")
+        return to_blocked(a, pad_value=float("nan")), a.shape[1]
+    if lda_extra:
+        buf = torch.full((a.shape[0], a.shape[1] + lda_extra), float("nan"), dtype=a.dtype, device=a.device)
+        buf[:, :a.shape[1]] = a
+        return buf, buf.shape[1]
+    return a, a.shape[1]
+
+
+def _unblock(flat: torch.Tensor, rows: int, width: int):
+    """a blocked output buffer -> (its `rows` rows as plain rows, its padding rows)"""
+    per = 128 // flat.element_size()
+    rows8 = (rows + 7) // 8 * 8
+    full = from_blocked(flat.view(rows8 // 8, width // per, 8, per), rows8)
+    return full[:rows].contiguous(), full[rows:].contiguous()
+
+
+def gemm_nt_engine(a, w, K: Optional[int] = None, a_blocked: bool = False, ksplit: int = 0, out_dtype: Optional[torch.dtype] = None,
+                   lda_extra: int = 0):
+    """pcad_gemm_nt_engine (the engine's out_proj launch): a [M, K] - or, ksplit = Ko / 64, bf16 [M, 2 Ko] = [hi | lo] with K = 3 Ko -,
+    w [N, K] (or [N, 2 Ko]); a_blocked: A goes through the blocked layout.  -> namespace(c [M, N] out_dtype, guards_ok)."""
+    from types import SimpleNamespace
+    _require_gpu(a, "a")
+    lib = load_library()
+    M, N = a.shape[0], w.shape[0]
+    K = a.shape[1] if K is None else K
+    od = out_dtype or a.dtype
+    ab, lda = _gemm_a(a, a_blocked, lda_extra)
+    wf = w.contiguous()
+    c = _guarded_rows(M, N, od, a.device)
+    with torch.cuda.device(a.device):
+        _check(lib.pcad_gemm_nt_engine(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c[0].data_ptr(), N, M, N, K, int(bool(a_blocked)),
+                                       int(ksplit), _dt(a), _DT[od], _stream_ptr()), "pcad_gemm_nt_engine")
+    return SimpleNamespace(c=c[0].view(M, N), guards_ok=_guards_intact([c]))
+
+
+def gemm_nt_xproj(a, w, nsplit: int, a_blocked: bool = False, ksplit: int = 0):
+    """pcad_gemm_nt_xproj (the engine's x_proj launch where the fused conv + x_proj kernel is off): a [M, K], w [N, K] ->
+    namespace(c [M, nsplit] in a's dtype, c2 fp32 [M, N - nsplit] holding values rounded to a's dtype, guards_ok)."""
+    from types import SimpleNamespace
+    _require_gpu(a, "a")
+    lib = load_library()
+    M, N, K = a.shape[0], w.shape[0], a.shape[1]
+    ab, lda = _gemm_a(a, a_blocked, 0)
+    wf = w.contiguous()
+    c = _guarded_rows(M, nsplit, a.dtype, a.device)
+    c2 = _guarded_rows(M, N - nsplit, torch.float32, a.device)
+    with torch.cuda.device(a.device):
+        _check(lib.pcad_gemm_nt_xproj(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c[0].data_ptr(), nsplit, c2[0].data_ptr(), N - nsplit,
+                                      nsplit, M, N, K, int(bool(a_blocked)), int(ksplit), _dt(a), _stream_ptr()), "pcad_gemm_nt_xproj")
+    return SimpleNamespace(c=c[0].view(M, nsplit), c2=c2[0].view(M, N - nsplit), guards_ok=_guards_intact([c, c2]))
+
+
+def gemm_nt_two(a, w, nsplit: int, K: Optional[int] = None, out_blocked: bool = False, rscale=None, ksplit: int = 0,
+                out_dtype: Optional[torch.dtype] = None, lda_extra: int = 0, a_blocked: bool = False):
+    """pcad_gemm_nt_two (the engine's in_proj launch): a, w, K, ksplit, lda_extra as in gemm_nt_engine; rscale fp32 [M] or None.
+    out_blocked: both outputs go through the blocked layout.  a_blocked is refused by the library (the form has none).
+    -> namespace(c1 [M, nsplit], c2 [M, N - nsplit] out_dtype; pad1, pad2: the blocked buffers' padding rows (empty for plain
+    outputs); guards_ok)."""
+    from types import SimpleNamespace
+    _require_gpu(a, "a")
+    lib = load_library()
+    M, N = a.shape[0], w.shape[0]
+    K = a.shape[1] if K is None else K
+    od = out_dtype or a.dtype
+    ab, lda = _gemm_a(a, a_blocked, lda_extra)
+    wf = w.contiguous()
+    rs = rscale.float().contiguous() if rscale is not None else None
+    rows = (M + 7) // 8 * 8 if out_blocked else M
+    c1, c2 = _guarded_rows(rows, nsplit, od, a.device), _guarded_rows(rows, N - nsplit, od, a.device)
+    with torch.cuda.device(a.device):
+        _check(lib.pcad_gemm_nt_two(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c1[0].data_ptr(), c2[0].data_ptr(), nsplit,
+                                    rs.data_ptr() if rs is not None else None, M, N, K, int(bool(a_blocked)), int(bool(out_blocked)),
+                                    int(ksplit), _dt(a), _DT[od], _stream_ptr()), "pcad_gemm_nt_two")
+    if out_blocked:
+        (o1, p1), (o2, p2) = _unblock(c1[0], M, nsplit), _unblock(c2[0], M, N - nsplit)
+    else:
+        o1, o2 = c1[0].view(M, nsplit), c2[0].view(M, N - nsplit)
+        p1, p2 = o1[M:], o2[M:]
+    return SimpleNamespace(c1=o1, c2=o2, pad1=p1, pad2=p2, guards_ok=_guards_intact([c1, c2]))
+
+
+def gemm_nt_residual_engine(a, w, residual, a_blocked: bool = False, ksplit: int = 0):
+    """pcad_gemm_nt_residual_engine: `linear_residual` with A through the blocked layout (the engine's "norm_fold" out_proj launch).
+    -> namespace(res fp32 [M, N], c [M, N] in a's dtype, ssq fp32 [M, N / 128], guards_ok)."""
+    from types import SimpleNamespace
+    _require_gpu(a, "a")
+    lib = load_library()
+    M, K = a.shape
+    N = w.shape[0]
+    if residual.dtype != torch.float32 or tuple(residual.shape) != (M, N):
+        raise ValueError("residual must be an fp32 [M, N] tensor")
+    ab, lda = _gemm_a(a, a_blocked, 0)
+    wf = w.contiguous()
+    res = _guarded_rows(M, N, torch.float32, a.device)
+    res[0].copy_(to_res_fragment(residual))
+    c, ssq = _guarded_rows(M, N, a.dtype, a.device), _guarded_rows(M, N // 128, torch.float32, a.device)
+    with torch.cuda.device(a.device):
+        _check(lib.pcad_gemm_nt_residual_engine(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c[0].data_ptr(), res[0].data_ptr(),
+                                                ssq[0].data_ptr(), M, N, K, int(bool(a_blocked)), int(ksplit), _dt(a), _stream_ptr()),
+               "pcad_gemm_nt_residual_engine")
+    return SimpleNamespace(res=from_res_fragment(res[0], M, N), c=c[0].view(M, N), ssq=ssq[0].view(M, N // 128),
+                           guards_ok=_guards_intact([res, c, ssq]))
+
+
 def gather_rows(src, B: int, L: int, positions):
     """src [2B*L, E] -> [2B*P, E]: strand b row p_q, strand B+b row L-1-p_q (include/pcad.h pcad_gather_rows)."""
     import ctypes as C

@@ -116,6 +116,52 @@ def predict(D, dt_rank, bf16, B, L, chunk_seqs=0, scan_segments_on=True, expand=
     return dict(G=G, seg_blocks=sb, pair=pair, ks=ks, chunk=Sc // 2, scratch=scratch)
 
 
+# ---- csrc/gemm.hip: which kernel a GEMM launch runs (launch_gemm_nt / _split / _two / _res -> launch_gemm256_t) ---------------------
+GEMM_NT, GEMM_256Q, GEMM_256R = "gemm_nt_kernel 256x128", "gemm256q_kernel 256x256 4-wave", "gemm256r_kernel 256x256 8-wave"
+GEMM_TILE = {GEMM_NT: (256, 128), GEMM_256Q: (256, 256), GEMM_256R: (256, 256)}
+GEMM_ROWB = 128                # bytes of K per K-tile row: 64 bf16 / 32 fp32 elements
+
+
+def gemm_quad_ok(M, N, lda, ldw, esz, two=False, nsplit=0):
+    """gemm.hip quad_ok: whole 256 x 256 tiles, the two outputs split on a 64-column group, unsigned 32-bit operand offsets"""
+    lim = (1 << 32) - 65536
+    return M % 256 == 0 and N % 256 == 0 and (not two or nsplit % 64 == 0) and M * lda * esz < lim and N * ldw * esz < lim
+
+
+def gemm_kernel(form, M, N, esz, lda, ldw, osz=None, ldc=None, nsplit=0, epilogue=False):
+    """The kernel a launch of `form` ("plain", "xproj", "two", "residual") runs; None: the launcher refuses it.  esz / osz: operand and
+    output element sizes; epilogue: a fused epilogue (the two form's rscale; the residual form always has one)."""
+    osz = esz if osz is None else osz
+    if form == "xproj":
+        return GEMM_NT
+    if form == "plain":
+        ldc = N if ldc is None else ldc
+        big = M >= 2048 and N >= 512 and N % 16 == 0 and (osz == esz or (esz == 2 and osz == 4)) and (ldc * osz) % 16 == 0
+        if not big:
+            return GEMM_NT
+        return GEMM_256Q if gemm_quad_ok(M, N, lda, ldw, esz) else GEMM_256R
+    two = form == "two"
+    qok = gemm_quad_ok(M, N, lda, ldw, esz, two, nsplit)
+    if form == "residual" or epilogue:
+        return GEMM_256Q if qok and osz == esz else None       # the fused epilogues exist on the 4-wave kernel only
+    return GEMM_256Q if qok else GEMM_256R
+
+
+def gemm_tiles(kernel, M, N):
+    bm, bn = GEMM_TILE[kernel]
+    return _cdiv(M, bm) * _cdiv(N, bn)
+
+
+def gemm_persistent_grid(cu_count, tiles):
+    """gemm.hip persistent_grid: one block per CU, a multiple of 8; a block walks tiles b, b + grid, ..."""
+    return min(tiles, cu_count // 8 * 8)
+
+
+def gemm_k_tiles(K, esz):
+    """K-tiles per output tile (the split form's K = 3 Ko counts all three passes)"""
+    return K * esz // GEMM_ROWB
+
+
 def _handle(lib, D, n_layer, dt_rank, bf16, opts, expand=2):
     c = engine.PcadConfig(d_model=D, n_layer=n_layer, d_state=16, d_conv=4, expand=expand, dt_rank=dt_rank, vocab=8, eps=1e-5,
                           dtype=1 if bf16 else 0, residual_in_fp32=1, complement=(C.c_int32 * 8)(0, 1, 2, 6, 5, 4, 3, 7))

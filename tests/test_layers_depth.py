@@ -16,6 +16,8 @@ pcad_selective_scan_dtproj pcad_set_option pcad_set_status_buffer pcad_version p
 # additions only, nothing above changed
 EXPORTS += """pcad_conv_xproj_bidir_engine pcad_conv_xproj_split_scratch_bytes pcad_scan_pair_scratch_bytes pcad_scan_segment_scratch_bytes
 pcad_selective_scan_engine pcad_selective_scan_pair""".split()
+# ... and for the engine's GEMM launch forms (tests/test_gpu_gemm_forms.py): additions only again
+EXPORTS += "pcad_gemm_nt_engine pcad_gemm_nt_residual_engine pcad_gemm_nt_two pcad_gemm_nt_xproj".split()
 
 
 def test_exported_c_symbols_are_unchanged():
