@@ -1,0 +1,77 @@
+// The entry points of libpcad_bwd.so (include/pcad_bwd.h): argument checks + the launch.  The library links libpcad.so and reports
+// through its pcad::fail, so pcad_last_error() of the calling thread carries the message.
+#include "../../include/pcad_bwd.h"
+#include "pcad_internal.hpp"
+using namespace pcad;
+
+extern "C" {
+
+size_t pcad_causal_conv1d_silu_bwd_scratch_bytes(int S, int L, int E) {
+    if (S <= 0 || L <= 0 || E <= 0) return 0;
+    return conv_bwd_bytes(S, L, E);
+}
+
+int pcad_causal_conv1d_silu_bwd(const void* x, int64_t ldx, const float* w, const float* b, const void* dout, void* dx, float* dw, float* db,
+                                void* scratch, size_t scratch_bytes, int S, int L, int E, int reverse, int dtype, pcad_stream stream) {
+    const char* who = "pcad_causal_conv1d_silu_bwd";
+    const struct { const void* p; const char* name; } req[] = {{x, "x"}, {w, "w"}, {b, "b"}, {dout, "dout"}, {dx, "dx"}, {dw, "dw"}, {db, "db"}};
+    for (const auto& r : req)
+        if (!r.p) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    const int V = dtype == PCAD_BF16 ? 8 : 4;
+    if (S < 0 || L < 0) return fail(PCAD_ERR_INVALID, "%s: S, L must be >= 0 (S=%d, L=%d)", who, S, L);
+    if (E <= 0 || E % V) return fail(PCAD_ERR_INVALID, "%s: E must be a positive multiple of 16 bytes = %d elements (E=%d)", who, V, E);
+    if (ldx < E) return fail(PCAD_ERR_INVALID, "%s: ldx must be >= E (ldx=%lld, E=%d)", who, (long long)ldx, E);
+    if (ldx % V) return fail(PCAD_ERR_INVALID, "%s: ldx must be a multiple of 16 bytes = %d elements (ldx=%lld)", who, V, (long long)ldx);
+    const struct { const void* p; const char* name; } al[] = {{x, "x"}, {dout, "dout"}, {dx, "dx"}, {w, "w"}};
+    for (const auto& r : al)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    if (S == 0 || L == 0) return PCAD_OK;
+    if (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < conv_bwd_bytes(S, L, E))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_causal_conv1d_silu_bwd_scratch_bytes large", who);
+    hipError_t err = launch_conv_bwd({.x = x, .ldx = ldx, .w = w, .b = b, .dout = dout, .dx = dx, .dw = dw, .db = db, .scratch = scratch,
+                                      .S = S, .L = L, .E = E, .dt = dtype, .reverse = reverse != 0},
+                                     (hipStream_t)stream);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "%s: S * ceil(L / 64) * E / %d lanes must fit a 32-bit grid of 256-lane blocks", who, V);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+size_t pcad_add_rmsnorm_bwd_scratch_bytes(int64_t rows, int D) {
+    if (rows <= 0 || D <= 0) return 0;
+    return norm_bwd_bytes(rows, D);
+}
+
+int pcad_add_rmsnorm_bwd(const void* x, const void* residual_in, const float* weight, const void* dy, const void* dresidual_out, void* dx,
+                         void* dresidual_in, float* dweight, void* scratch, size_t scratch_bytes, int64_t rows, int D, float eps, int dtype,
+                         int res_dtype, pcad_stream stream) {
+    const char* who = "pcad_add_rmsnorm_bwd";
+    const struct { const void* p; const char* name; } req[] = {{x, "x"}, {weight, "weight"}, {dy, "dy"}, {dx, "dx"}, {dweight, "dweight"}};
+    for (const auto& r : req)
+        if (!r.p) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);
+    if ((residual_in != nullptr) != (dresidual_in != nullptr))
+        return fail(PCAD_ERR_INVALID, "%s: dresidual_in is required exactly when residual_in is given (residual_in %s, dresidual_in %s)", who,
+                    residual_in ? "given" : "NULL", dresidual_in ? "given" : "NULL");
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (res_dtype != PCAD_F32 && !(res_dtype == PCAD_BF16 && dtype == PCAD_BF16))
+        return fail(PCAD_ERR_INVALID, "%s: bad res_dtype %d for dtype %d (BF16 / F32, BF16 / BF16 or F32 / F32)", who, res_dtype, dtype);
+    if (rows < 0) return fail(PCAD_ERR_INVALID, "%s: rows must be >= 0", who);
+    if (D <= 0 || D % 8) return fail(PCAD_ERR_INVALID, "%s: D must be a positive multiple of 8 (D=%d)", who, D);
+    if (D > 2048) return fail(PCAD_ERR_INVALID, "%s: D must be <= 2048 (D=%d)", who, D);
+    const struct { const void* p; const char* name; } al[] = {{x, "x"}, {residual_in, "residual_in"}, {weight, "weight"}, {dy, "dy"},
+                                                              {dresidual_out, "dresidual_out"}, {dx, "dx"}, {dresidual_in, "dresidual_in"}};
+    for (const auto& r : al)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    if (rows == 0) return PCAD_OK;
+    if (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < norm_bwd_bytes(rows, D))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_add_rmsnorm_bwd_scratch_bytes large", who);
+    hipError_t err = launch_norm_bwd({.x = x, .res_in = residual_in, .w = weight, .dy = dy, .dres_out = dresidual_out, .dx = dx,
+                                      .dres_in = dresidual_in, .dw = dweight, .scratch = scratch, .rows = rows, .D = D, .eps = eps,
+                                      .dt = dtype, .rdt = res_dtype},
+                                     (hipStream_t)stream);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "%s: rows / 64 must fit a 32-bit grid", who);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+}  // extern "C"

@@ -306,6 +306,51 @@ struct ScanBwdLaunch {
 size_t scan_bwd_bytes(int S, int L, int E);
 hipError_t launch_scan_bwd(const ScanBwdLaunch& a, hipStream_t s);
 
+// conv_bwd.hip, norm_bwd.hip (libpcad_bwd.so, include/pcad_bwd.h) --------------------
+// Both backward kernels keep their parameter-gradient partials in registers, store them once per unit of work to the caller's
+// scratch as rows of `n` floats, and launch_sum_partials adds the P rows into out[n]: the rows of each of 32 slices of P in index order, the
+// 32 slice sums in index order (a fixed order: no floating-point atomics, results are bit-reproducible).  out0 takes the first n0
+// floats of a row, out1 the rest.
+hipError_t launch_sum_partials(const float* part, int64_t P, float* out0, int n0, float* out1, int n1, hipStream_t s);
+
+// Backward of launch_conv_dir's plain-layout form (pcad_bwd.h pcad_causal_conv1d_silu_bwd): x [S, L, ldx] and dout / dx [S, L, E] in dtype
+// dt, w / dw fp32 [E, 4], b / db fp32 [E]; every output is overwritten.  scratch: conv_bwd_bytes(S, L, E) bytes, 256-byte aligned -
+// one row of 5 E partials (dw | db) per (strand, segment of CONV_BWD_SEG walk steps).
+constexpr int CONV_BWD_SEG = 64;      // walk steps per lane
+struct ConvBwdLaunch {
+    const void* x;  int64_t ldx;
+    const float *w, *b;
+    const void* dout;
+    void* dx;
+    float *dw, *db;
+    void* scratch;
+    int S, L, E, dt;
+    bool reverse = false;
+};
+size_t conv_bwd_bytes(int S, int L, int E);
+hipError_t launch_conv_bwd(const ConvBwdLaunch& a, hipStream_t s);
+
+// Backward of launch_add_rmsnorm (pcad_bwd.h pcad_add_rmsnorm_bwd): x, dy, dx [rows, D] in dtype dt; res_in, dres_out, dres_in
+// [rows, D] in dtype rdt (res_in and dres_in both given or both null; dres_out may be null); w, dw fp32 [D]; every output is
+// overwritten.  scratch: norm_bwd_bytes(rows, D) bytes, 256-byte aligned - one row of D partials of dw per slab of NORM_BWD_ROWS rows.
+constexpr int NORM_BWD_ROWS = 16;     // consecutive rows one wave walks
+struct NormBwdLaunch {
+    const void* x;
+    const void* res_in = nullptr;
+    const float* w;
+    const void* dy;
+    const void* dres_out = nullptr;
+    void* dx;
+    void* dres_in = nullptr;
+    float* dw;
+    void* scratch;
+    int64_t rows;  int D;
+    float eps;
+    int dt, rdt;
+};
+size_t norm_bwd_bytes(int64_t rows, int D);
+hipError_t launch_norm_bwd(const NormBwdLaunch& a, hipStream_t s);
+
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor (plain or blocked) -> out[(strand * P + q), E]
 hipError_t launch_gather_rows(const void* src, void* out, int B, int L, int E, Positions pos, int dt, bool blocked,

@@ -131,6 +131,16 @@ TRAIN_SIGNATURES = {
 }
 TRAIN_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_train.so")
 
+# name -> (restype, argtypes): every symbol include/pcad_bwd.h declares (libpcad_bwd.so: the conv and RMSNorm backward operators; the
+# table, the header and the library's exports are held to each other, not to a closed list - later backward operators go here)
+BWD_SIGNATURES = {
+    "pcad_causal_conv1d_silu_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pcad_causal_conv1d_silu_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
+    "pcad_add_rmsnorm_bwd_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "pcad_add_rmsnorm_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p]),
+}
+BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
+
 # include/pcad.h pcad_pooling (pooling_strategy of CaduceusForSequenceClassification)
 POOLING = {"mean": 0, "max": 1, "first": 2, "last": 3}
 MAX_LABELS = 256
@@ -234,6 +244,27 @@ def load_train_library():
         fn.restype = res
         fn.argtypes = args
     _train_lib = lib
+    return lib
+
+
+_bwd_lib = None
+
+
+def load_bwd_library():
+    """Load libpcad_bwd.so (include/pcad_bwd.h) beside libpcad.so, which it links and which is loaded first; fails loudly if it is
+    missing - a missing backward kernel is an error, there is no fallback to torch."""
+    global _bwd_lib
+    if _bwd_lib is not None:
+        return _bwd_lib
+    load_library()
+    if not os.path.exists(BWD_LIB_PATH):
+        raise RuntimeError(f"{BWD_LIB_PATH} not found: build it with `make -C plantcaduceus_amd/csrc` / `__graft_entry__.build()`")
+    lib = C.CDLL(BWD_LIB_PATH)
+    for name, (res, args) in BWD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _bwd_lib = lib
     return lib
 
 

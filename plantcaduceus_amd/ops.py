@@ -12,6 +12,10 @@ MI355X HIP kernels through the C ABI.  Same names, argument meaning and layouts 
 Inputs use the reference's channels-first (B, E, L) layout where the originals do; they are transposed
 to the engine's token-major layout here (test plumbing — the engine itself never transposes).
 All tensors must be ROCm tensors; there is no CPU fallback.
+
+Differentiable (each a torch.autograd.Function on this project's backward kernels as soon as grad mode is on and an input requires
+grad; otherwise the plain call, no graph): selective_scan_fn (include/pcad_train.h), causal_conv1d_fn / causal_conv1d_dir and
+rms_norm_fn (include/pcad_bwd.h), and mamba_inner_fn as a composition of those around stock F.linear.
 """
 from __future__ import annotations
 
@@ -19,7 +23,9 @@ from typing import Optional
 
 import torch
 
-from .engine import _DT, _check, _require_gpu, _stream_ptr, load_library, load_train_library
+import torch.nn.functional as F
+
+from .engine import _DT, _check, _require_gpu, _stream_ptr, load_bwd_library, load_library, load_train_library
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -29,9 +35,21 @@ def _dt(t: torch.Tensor) -> int:
 
 
 def rms_norm_fn(x, weight, bias=None, residual=None, eps=1e-6, prenorm=False, residual_in_fp32=False):
+    """When x, weight or residual requires grad the call is differentiable (pcad_add_rmsnorm_bwd): each gradient comes back in its
+    input's shape and dtype; the prenorm output carries its own gradient into the residual stream."""
     _require_gpu(x, "x")
     if bias is not None:
         raise NotImplementedError("RMSNorm bias is not used by Caduceus")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, residual)):
+        # the casts stay torch ops outside the Function, so that autograd returns each gradient in its input's dtype
+        rdt = torch.float32 if (residual_in_fp32 or x.dtype == torch.float32) else x.dtype
+        y, res_out = _RmsNormFn.apply(x, weight.float(), residual.to(rdt) if residual is not None else None, float(eps),
+                                      bool(residual_in_fp32))
+        return (y, res_out) if prenorm else y
+    return _rms_norm_forward(x, weight, residual, eps, prenorm, residual_in_fp32)
+
+
+def _rms_norm_forward(x, weight, residual, eps, prenorm, residual_in_fp32):
     lib = load_library()
     D = x.shape[-1]
     xf = x.contiguous().view(-1, D)
@@ -87,8 +105,18 @@ def from_blocked(xb: torch.Tensor, rows: int) -> torch.Tensor:
 def causal_conv1d_dir(x_tm, weight, bias, reverse: bool = False, blocked: bool = False):
     """One direction of the conv (pcad_causal_conv1d_silu_dir, what "untied_directions" runs per direction): x_tm [S, L, E] ->
     y [S, L, E]; reverse: anti-causal (the causal conv of the flipped strand, flipped back).  blocked: x is handed over and y is
-    returned through the engine's blocked layout (`to_blocked` / `from_blocked`) instead of plain rows."""
+    returned through the engine's blocked layout (`to_blocked` / `from_blocked`) instead of plain rows.
+    When x_tm, weight or bias requires grad the call is differentiable (pcad_causal_conv1d_silu_bwd), plain layout only."""
     _require_gpu(x_tm, "x")
+    S, L, E = x_tm.shape
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x_tm, weight, bias)):
+        if blocked:
+            raise NotImplementedError("the blocked layout is an inference form: with an input that requires grad, use plain rows")
+        return _CausalConv1dDirFn.apply(x_tm, weight.reshape(E, -1).float(), bias.float(), bool(reverse))
+    return _causal_conv1d_dir_forward(x_tm, weight, bias, reverse, blocked)
+
+
+def _causal_conv1d_dir_forward(x_tm, weight, bias, reverse, blocked):
     lib = load_library()
     S, L, E = x_tm.shape
     w = weight.reshape(E, -1).float().contiguous()
@@ -289,13 +317,17 @@ def conv_xproj_bidir_engine(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj
 
 
 def causal_conv1d_fn(x, weight, bias=None, activation=None):
-    """x (B, E, L), weight (E, W=4), bias (E), activation must be "silu"."""
+    """x (B, E, L), weight (E, W=4), bias (E), activation must be "silu".  When x, weight or bias requires grad the call is
+    differentiable: the one-direction kernel, whose values are the both-direction kernel's bit for bit (csrc/conv.hip), with
+    pcad_causal_conv1d_silu_bwd behind it."""
     if activation not in ("silu", "swish"):
         raise NotImplementedError("only activation='silu' is on the Caduceus path")
     if weight.shape[-1] != 4:
         raise NotImplementedError("only conv width 4")
     if bias is None:
         bias = torch.zeros(weight.shape[0], device=x.device)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, weight, bias)):
+        return causal_conv1d_dir(x.transpose(1, 2), weight, bias, False).transpose(1, 2)
     yf, _ = causal_conv1d_bidir(x.transpose(1, 2), weight, bias, weight, bias)
     return yf.transpose(1, 2)
 
@@ -372,6 +404,126 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False,
     return SimpleNamespace(du=du.transpose(1, 2), ddelta=dd.transpose(1, 2), dz=dz.transpose(1, 2) if dz is not None else None,
                            dB=dbc[..., :16].transpose(1, 2), dC=dbc[..., 16:].transpose(1, 2), dA=dA, dD=dD, ddelta_bias=dbias,
                            guards_ok=ok)
+
+
+CONV_BWD_SEG = 64        # csrc/kernels.hpp CONV_BWD_SEG: walk steps one lane of the conv backward owns (one row of dw | db partials each)
+NORM_BWD_ROWS = 16       # csrc/kernels.hpp NORM_BWD_ROWS: consecutive rows one wave of the norm backward walks (one dweight partial row each)
+
+
+def _sentinels_intact(outs) -> bool:
+    """outs: (tensor, whole buffer or None) pairs of `_guarded`: one row of sentinels before and after every guarded output untouched"""
+    ok = True
+    for t, whole in outs:
+        if whole is not None:
+            row = t.shape[-1]
+            ok = ok and bool((whole[:row] == -1234.0).all()) and bool((whole[row + t.numel():] == -1234.0).all())
+    return ok
+
+
+def _bwd_scratch(nb: int, dev, poison: bool):
+    return _nan_bytes(nb, dev) if poison else torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+
+
+def causal_conv1d_silu_bwd(x_tm, weight, bias, dout_tm, reverse=False, poison=False):
+    """pcad_causal_conv1d_silu_bwd on causal_conv1d_dir's plain operands: x_tm [S, L, E] (a view whose rows are ldx >= E elements apart,
+    such as the first half of a token-major xz, is read in place), weight (E, 4) or (E, 1, 4), bias (E), dout_tm [S, L, E].
+    -> namespace(dx [S, L, E] in x's dtype; dw fp32 (E, 4); db fp32 (E); guards_ok).  poison (tests): as selective_scan_bwd."""
+    from types import SimpleNamespace
+    _require_gpu(x_tm, "x")
+    lib = load_bwd_library()
+    S, L, E = x_tm.shape
+    dt, dev = x_tm.dtype, x_tm.device
+    ldx = x_tm.stride(1)
+    in_place = (S * L > 0 and x_tm.stride(2) == 1 and x_tm.stride(0) == L * ldx and ldx >= E and (ldx * x_tm.element_size()) % 16 == 0
+                and x_tm.data_ptr() % 16 == 0)
+    if not in_place:
+        x_tm, ldx = x_tm.contiguous(), E
+    w = weight.reshape(E, -1).float().contiguous()
+    b = bias.float().contiguous()
+    g = dout_tm.to(dt).contiguous()
+    f32 = torch.float32
+    outs = [_guarded(sh, ty, dev, poison) for sh, ty in (((S, L, E), dt), ((E, 4), f32), ((E,), f32))]
+    dx, dw, db = [o[0] for o in outs]
+    nb = lib.pcad_causal_conv1d_silu_bwd_scratch_bytes(S, L, E)
+    scratch = _bwd_scratch(nb, dev, poison)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_causal_conv1d_silu_bwd(x_tm.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), g.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                                               db.data_ptr(), _aligned(scratch), nb, S, L, E, int(bool(reverse)), _dt(x_tm), _stream_ptr()),
+               "pcad_causal_conv1d_silu_bwd")
+    return SimpleNamespace(dx=dx, dw=dw, db=db, guards_ok=_sentinels_intact(outs))
+
+
+def add_rmsnorm_bwd(x, residual, weight, dy, dresidual_out, eps, residual_in_fp32, poison=False):
+    """pcad_add_rmsnorm_bwd on rms_norm_fn's operands: x, dy [..., D]; residual [..., D] or None; dresidual_out [..., D] (the gradient
+    of the prenorm output) or None.  The residual tensors are taken in the residual dtype (fp32 with residual_in_fp32 or an fp32 x,
+    else x's).  -> namespace(dx like x; dresidual_in like x in the residual dtype, None without residual; dweight fp32 (D); guards_ok).
+    poison (tests): as selective_scan_bwd."""
+    from types import SimpleNamespace
+    _require_gpu(x, "x")
+    lib = load_bwd_library()
+    D = x.shape[-1]
+    dt, dev = x.dtype, x.device
+    rdt = torch.float32 if (residual_in_fp32 or dt == torch.float32) else dt
+    xf = x.contiguous().view(-1, D)
+    rows = xf.shape[0]
+    res = residual.to(rdt).contiguous().view(-1, D) if residual is not None else None
+    g = dy.to(dt).contiguous().view(-1, D)
+    gres = dresidual_out.to(rdt).contiguous().view(-1, D) if dresidual_out is not None else None
+    w = weight.float().contiguous()
+    outs = [_guarded(sh, ty, dev, poison) for sh, ty in (((rows, D), dt), ((rows, D), rdt), ((D,), torch.float32))]
+    dx, dres, dw = [o[0] for o in outs]
+    if res is None:
+        dres, outs[1] = None, (outs[1][0], None)
+    nb = lib.pcad_add_rmsnorm_bwd_scratch_bytes(rows, D)
+    scratch = _bwd_scratch(nb, dev, poison)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        _check(lib.pcad_add_rmsnorm_bwd(xf.data_ptr(), ptr(res), w.data_ptr(), g.data_ptr(), ptr(gres), dx.data_ptr(), ptr(dres), dw.data_ptr(),
+                                        _aligned(scratch), nb, rows, D, float(eps), _dt(xf), _DT[rdt], _stream_ptr()), "pcad_add_rmsnorm_bwd")
+    return SimpleNamespace(dx=dx.view(x.shape), dresidual_in=dres.view(x.shape) if dres is not None else None, dweight=dw,
+                           guards_ok=_sentinels_intact(outs))
+
+
+class _CausalConv1dDirFn(torch.autograd.Function):
+    """causal_conv1d_dir (plain rows) with a backward: pcad_causal_conv1d_silu_bwd (include/pcad_bwd.h, libpcad_bwd.so).  weight (E, 4) and
+    bias (E) arrive in fp32 (the casts are torch ops outside).  Only the inputs are saved; the kernel recomputes the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, x_tm, weight, bias, reverse):
+        ctx.save_for_backward(x_tm, weight, bias)
+        ctx.reverse = bool(reverse)
+        return _causal_conv1d_dir_forward(x_tm, weight, bias, reverse, False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        x_tm, weight, bias = ctx.saved_tensors
+        g = causal_conv1d_silu_bwd(x_tm, weight, bias, dout, ctx.reverse)
+        need = ctx.needs_input_grad
+        return g.dx if need[0] else None, g.dw if need[1] else None, g.db if need[2] else None, None
+
+
+class _RmsNormFn(torch.autograd.Function):
+    """rms_norm_fn (always with the prenorm output) with a backward: pcad_add_rmsnorm_bwd (include/pcad_bwd.h, libpcad_bwd.so).  weight
+    arrives in fp32 and residual in the residual dtype.  Only the inputs are saved; the kernel recomputes rstd."""
+
+    @staticmethod
+    def forward(ctx, x, weight, residual, eps, residual_in_fp32):
+        ctx.save_for_backward(x, weight, residual)
+        ctx.eps, ctx.res_fp32 = eps, residual_in_fp32
+        ctx.set_materialize_grads(False)              # an output nobody used arrives as None, not as a tensor of zeros
+        return _rms_norm_forward(x, weight, residual, eps, True, residual_in_fp32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, dres_out):
+        x, weight, residual = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(x)
+        g = add_rmsnorm_bwd(x, residual, weight, dy, dres_out, ctx.eps, ctx.res_fp32)
+        need = ctx.needs_input_grad
+        return (g.dx if need[0] else None, g.dweight if need[1] else None,
+                g.dresidual_in if residual is not None and need[2] else None, None, None)
 
 
 class _SelectiveScanFn(torch.autograd.Function):
@@ -479,7 +631,13 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
     reverse=True is the twin BiMambaWrapper needs for `mamba_rev`: the same operator walking right-to-left with the anti-causal
     conv on the SAME rows, i.e. mamba_inner_fn(xz, ..., reverse=True) == mamba_inner_fn(xz.flip(-1), ...).flip(1) without either
     flip copy.  Tensors are ROCm tensors in one dtype (fp32 or bf16); parameters are converted as the engine's
-    weight packing does (conv taps, A, D, biases to fp32; projections to xz.dtype)."""
+    weight packing does (conv taps, A, D, biases to fp32; projections to xz.dtype).
+
+    With grad mode on and any tensor input requiring grad the call takes a composed path of the differentiable operators, chained by
+    torch autograd: causal_conv1d_dir (pcad_causal_conv1d_silu_bwd), F.linear for x_proj, dt_proj and out_proj (differentiated by stock
+    PyTorch-ROCm), selective_scan_fn (pcad_selective_scan_bwd).  That path stores xc, x_dbl, delta and y in the model dtype - upstream's
+    own rounding points - so its forward value agrees with the fused inference path within test_mamba_inner_fn's bars (3e-5 fp32,
+    2^-7 bf16 against the oracle), not bit for bit.  With nothing requiring grad the function is unchanged."""
     _require_gpu(xz, "xz")
     if B is not None or C is not None:
         raise NotImplementedError("constant B / C are not on the Caduceus path (Mamba.forward passes None: input-dependent B, C)")
@@ -500,6 +658,14 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
     if w.shape[1] != 4:
         raise NotImplementedError("only conv width 4")
     bias = conv1d_bias if conv1d_bias is not None else torch.zeros(E, device=dev)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
+                                                                                  out_proj_weight, A, D, delta_bias)):
+        xc = causal_conv1d_dir(xz[:, :E].transpose(1, 2), w, bias, reverse)                      # (B, L, E)
+        x_dbl = F.linear(xc, x_proj_weight.to(dt))                                               # (B, L, R + 32)
+        delta = F.linear(x_dbl[..., :R], delta_proj_weight.to(dt)).transpose(1, 2)               # (B, E, L)
+        y = selective_scan_fn(xc.transpose(1, 2), delta, A, x_dbl[..., R:R + 16].transpose(1, 2), x_dbl[..., R + 16:].transpose(1, 2), D,
+                              z=xz[:, E:], delta_bias=delta_bias, delta_softplus=True, reverse=reverse)
+        return F.linear(y.transpose(1, 2), out_proj_weight.to(dt))
     x_tm = xz[:, :E].transpose(1, 2).contiguous()                    # the engine is token-major (test plumbing: it never transposes)
     z_tm = xz[:, E:].transpose(1, 2).contiguous()
     rows = Bsz * L
