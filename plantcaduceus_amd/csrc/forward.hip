@@ -165,6 +165,15 @@ struct Walk {
     void* y_rev(const Lane& c) const { return pl.strict ? c.w.xc[0] : c.w.y; }
     const int32_t* ids_of(const Lane& c) const { return rq.ids + (int64_t)c.b0 * L; }
     const int32_t* ppw_of(const Lane& c) const { return rq.pos_per_window ? rq.pos_per_window + (size_t)c.b0 * rq.Pw : nullptr; }      // its rows of the [B, Pw] list
+    // what every head reads of the lane: the last mixer output, the residual stream (folded form: fragment layout) and norm_f
+    HeadInput head_in(const Lane& c) const {
+        return {.h = c.w.h, .res = c.w.res, .w = e->normf_w, .B = c.Bc, .L = L, .D = D, .eps = eps, .dt = dt, .rdt = rdt, .res_frag = pl.fold ? Dp : 0,
+                .ids = ids_of(c), .status = e->status};
+    }
+    // the evaluated rows of a [2 Bc L, E] mixer tensor -> u (dead since in_proj): the last-layer shortcut's operand
+    hipError_t gather_rows(const Lane& c, const void* src) const {
+        return launch_gather_rows({.src = src, .out = c.w.u, .B = c.Bc, .L = L, .E = E, .pos = pos, .dt = dt, .blocked = e->blocked}, s);
+    }
     // the full-size tied out_proj of one [rows, E] tensor (y, or in the strict order each direction's own): fp32 / bf16 GEMM, or the
     // split-bf16 form (operand conversion unless the scan wrote it + bf16 GEMM with K' = 3E, fp32 result)
     // Also the last-layer shortcut's: src = the n_rows gathered rows, plain (a_blocked false).  d: whose weight (untied form only)
@@ -222,7 +231,8 @@ struct Walk {
         }
         const int slot = lay_slot(level);
         if (slot >= 0)
-            HIP_TRY(launch_layer_rows(c.w.h, lay_dst(slot, c.b0), c.Bc, L, D, pos, ppw_of(c), layP, false, 0, 0, rq.lay.average, dt, e->status, s, compact));
+            HIP_TRY(launch_layer_rows({.src = c.w.h, .out = lay_dst(slot, c.b0), .B = c.Bc, .L = L, .D = D, .dt = dt, .pos = pos, .pos_per_window = ppw_of(c), .P = layP,
+                                       .average = rq.lay.average, .compact = compact, .status = e->status}, s));
         return PCAD_OK;
     }
     // A head's scratch goes to the buffers that are dead once the last out_proj has run (everything carved after h: xz, zb, xc,
@@ -239,20 +249,21 @@ struct Walk {
     }
     int add_norm(Lane& c, int li) const {        // residual add + norm (layer 0: RCPS embedding + norm)
         const LayerWeights& W = e->layers[li];
-        const int64_t rows = (int64_t)2 * c.Bc * L;
+        const EmbedRows emb{.ids = ids_of(c), .emb = e->emb, .comp8 = e->comp, .B = c.Bc, .L = L};
         if (pl.fold) {
             if (li == 0) {      // res = Emb[token] (fp32, fragment layout) [+ u = the same rows in the model dtype and rstd when layer 0's in_proj runs as a GEMM]
                 ProfScope ps(e, PCAD_K_NORM, s);
-                HIP_TRY(launch_embed_rmsnorm(ids_of(c), e->emb, e->comp, W.norm_w, pl.tab0 ? nullptr : c.w.u, c.w.res, c.Bc, L, D, eps, dt, rdt, s, c.w.rstd, Dp));
+                HIP_TRY(launch_embed_rmsnorm({.w = W.norm_w, .y = pl.tab0 ? nullptr : c.w.u, .res_out = c.w.res, .D = D, .eps = eps, .dt = dt, .rdt = rdt, .rstd_out = c.w.rstd, .Dp = Dp}, emb, s));
             }
             return PCAD_OK;     // later layers: the previous out_proj's epilogue already produced res, round(res) and rstd
         }
         if (li == 0) {
             ProfScope ps(e, PCAD_K_NORM, s);
-            HIP_TRY(launch_embed_rmsnorm(ids_of(c), e->emb, e->comp, W.norm_w, c.w.u, c.w.res, c.Bc, L, D, eps, dt, rdt, s, nullptr, 0, pl.sp));
+            HIP_TRY(launch_embed_rmsnorm({.w = W.norm_w, .y = c.w.u, .res_out = c.w.res, .D = D, .eps = eps, .dt = dt, .rdt = rdt, .split_y = pl.sp}, emb, s));
         } else {
             ProfScope ps(e, PCAD_K_NORM, s);
-            HIP_TRY(launch_add_rmsnorm(c.w.h, c.w.res, W.norm_w, c.w.u, c.w.res, rows, D, eps, dt, rdt, s, pl.sp));
+            HIP_TRY(launch_add_rmsnorm({.x = c.w.h, .res_in = c.w.res, .w = W.norm_w, .y = c.w.u, .res_out = c.w.res, .rows = (int64_t)2 * c.Bc * L, .D = D, .eps = eps, .dt = dt, .rdt = rdt,
+                                        .split_y = pl.sp}, s));
         }
         return PCAD_OK;
     }
@@ -358,9 +369,9 @@ struct Walk {
             ProfScope ps(e, PCAD_K_HEAD, s);
             // the gathered rows of one direction (in u) through the tied out_proj: the same product as the full-size launch
             // (split-bf16 with "f32_gemm_split": bit-identical rows)
-            HIP_TRY(launch_gather_rows(c.w.y, c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
+            HIP_TRY(gather_rows(c, c.w.y));
             HIP_TRY(out_proj(c, li, c.w.u, (int64_t)S * P, c.w.h, 0, false));
-            HIP_TRY(launch_gather_rows(y_rev(c), c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
+            HIP_TRY(gather_rows(c, y_rev(c)));
             HIP_TRY(out_proj(c, li, c.w.u, (int64_t)S * P, c.w.xz, 1, false));
             HIP_TRY(launch_add_round(c.w.h, c.w.xz, (int64_t)S * P * D, dt, s));
             return truncated() ? emit_level(c, li + 1, true) : PCAD_OK;
@@ -375,7 +386,7 @@ struct Walk {
     }
     int out_proj_shortcut(Lane& c, int li) const {       // out_proj on the evaluated rows only: gather (-> u, dead since in_proj) and a small GEMM (-> first rows of h)
         ProfScope ps(e, PCAD_K_HEAD, s);          // counted with the head: not a full-size out_proj launch
-        HIP_TRY(launch_gather_rows(c.w.y, c.w.u, c.Bc, L, E, pos, dt, e->blocked, s));
+        HIP_TRY(gather_rows(c, c.w.y));
         // split: the same split-bf16 product as the full-size out_proj (same operand values, same K order: bit-identical rows)
         HIP_TRY(out_proj(c, li, c.w.u, (int64_t)2 * c.Bc * P, c.w.h, 0, false));
         return truncated() ? emit_level(c, li + 1, true) : PCAD_OK;      // a truncated walk: level `depth` from the compact rows
@@ -406,8 +417,8 @@ struct Walk {
         float* lout = rq.logits_out ? rq.logits_out + (size_t)c.b0 * pl.Q * e->V : nullptr;
         if (!hout && !lout) return PCAD_OK;
         ProfScope ps(e, PCAD_K_HEAD, s);
-        HIP_TRY(launch_final_head(c.w.h, c.w.res, e->normf_w, e->emb, e->emb_f32, e->comp, hout, lout, c.Bc, L, D, eps,
-                                  pos, ppw_of(c), dt, rdt, s, pl.walk_len > 0, ids_of(c), e->status, pl.fold ? Dp : 0));
+        HIP_TRY(launch_final_head({.in = head_in(c), .emb_f32 = e->emb_f32, .comp8 = e->comp, .hidden_out = hout, .logits_out = lout, .pos = pos,
+                                   .pos_per_seq = ppw_of(c), .h_compact = pl.walk_len > 0}, s));
         return PCAD_OK;
     }
     int head_pooled(Lane& c) const {
@@ -415,8 +426,8 @@ struct Walk {
         const size_t part = pool_partial_bytes(c.Bc, L, D, pool.pooling);
         if (int rc = fits_dead(c, part, "pcad_forward_pooled", "head's partials")) return rc;
         ProfScope ps(e, PCAD_K_HEAD, s);
-        HIP_TRY(launch_pooled_head(c.w.h, c.w.res, e->normf_w, pool.score_w, pool.num_labels, pool.pooled_out ? pool.pooled_out + (size_t)c.b0 * 2 * D : nullptr,
-                                   pool.logits_out + (size_t)c.b0 * pool.num_labels, c.Bc, L, D, eps, pool.pooling, ids_of(c), e->status, dt, rdt, pl.fold ? Dp : 0, c.w.xz, s));
+        HIP_TRY(launch_pooled_head({.in = head_in(c), .score_w = pool.score_w, .NL = pool.num_labels, .pooled_out = pool.pooled_out ? pool.pooled_out + (size_t)c.b0 * 2 * D : nullptr,
+                                    .logits_out = pool.logits_out + (size_t)c.b0 * pool.num_labels, .pooling = pool.pooling, .part = c.w.xz}, s));
         return PCAD_OK;
     }
     int head_loss(Lane& c) const {       // per-segment partials in the dead buffers, as the pooled head's
@@ -424,17 +435,18 @@ struct Walk {
         if (int rc = fits_dead(c, loss_partial_bytes(c.Bc, L), "pcad_forward_loss", "head's partials")) return rc;
         const size_t o = (size_t)c.b0 * L;
         ProfScope ps(e, PCAD_K_HEAD, s);
-        HIP_TRY(launch_loss_head(c.w.h, c.w.res, e->normf_w, e->emb_f32, e->comp, loss.labels + o, loss.loss_weights ? loss.loss_weights + o : nullptr, loss.ignore_index,
-                                 loss.sums_out + (size_t)c.b0 * 4, loss.nll_out ? loss.nll_out + o : nullptr, loss.logits_out ? loss.logits_out + o * e->V : nullptr, c.Bc, L, D, eps,
-                                 ids_of(c), e->status, dt, rdt, pl.fold ? Dp : 0, c.w.xz, s));
+        HIP_TRY(launch_loss_head({.in = head_in(c), .emb_f32 = e->emb_f32, .comp8 = e->comp, .labels = loss.labels + o, .loss_w = loss.loss_weights ? loss.loss_weights + o : nullptr,
+                                  .ignore_index = loss.ignore_index, .sums_out = loss.sums_out + (size_t)c.b0 * 4, .nll_out = loss.nll_out ? loss.nll_out + o : nullptr,
+                                  .logits_out = loss.logits_out ? loss.logits_out + o * e->V : nullptr, .part = c.w.xz}, s));
         return PCAD_OK;
     }
     int head_probs(Lane& c) const {
         const auto& probs = rq.probs; const int Qp = pl.Q;
         ProfScope ps(e, PCAD_K_HEAD, s);
-        HIP_TRY(launch_probs_head(c.w.h, c.w.res, e->normf_w, e->emb_f32, e->comp, probs.cols, probs.probs_out ? probs.probs_out + (size_t)c.b0 * Qp * 4 : nullptr,
-                                  probs.logits_out ? probs.logits_out + (size_t)c.b0 * Qp * e->V : nullptr, c.Bc, L, D, eps, pos,
-                                  ppw_of(c), rq.Pw, dt, rdt, s, pl.walk_len > 0, ids_of(c), e->status, pl.fold ? Dp : 0));
+        HIP_TRY(launch_probs_head({.in = head_in(c), .emb_f32 = e->emb_f32, .comp8 = e->comp, .cols = probs.cols,
+                                   .probs_out = probs.probs_out ? probs.probs_out + (size_t)c.b0 * Qp * 4 : nullptr,
+                                   .logits_out = probs.logits_out ? probs.logits_out + (size_t)c.b0 * Qp * e->V : nullptr, .pos = pos, .pos_per_window = ppw_of(c),
+                                   .Pw = rq.Pw, .h_compact = pl.walk_len > 0}, s));
         return PCAD_OK;
     }
     int head_layers(Lane& c) const {
@@ -448,6 +460,12 @@ struct Walk {
         const bool columns = ppw && layP > 1;
         if (int rc = fits_dead(c, rows_bytes + (columns ? align_up((size_t)c.Bc * layP * 4) : 0), "pcad_forward_layers", "last level's rows", rows_bytes)) return rc;
         const int slot = lay_slot(e->nl);
+        // the assembled rows -> the caller's tensor; sb / sq: rows_tmp's rows between two windows / two slots
+        auto emit = [&](int64_t sb, int64_t sq) {
+            return launch_layer_rows({.src = rows_tmp, .out = lay_dst(slot, c.b0), .B = c.Bc, .L = L, .D = D, .dt = dt, .pos = pos, .P = layP, .assembled = true, .sb = sb, .sq = sq,
+                                      .average = rq.lay.average}, s);
+        };
+        FinalHeadLaunch fh{.in = head_in(c), .emb_f32 = e->emb_f32, .comp8 = e->comp, .hidden_out = rows_tmp, .pos = pos, .h_compact = pl.walk_len > 0};
         ProfScope ps(e, PCAD_K_HEAD, s);
         if (ppw) {
             const int32_t* col = ppw;                // P == 1: the list is its own column (pcad_forward_at's launch)
@@ -455,16 +473,16 @@ struct Walk {
                 col = (const int32_t*)(rows_tmp + rows_bytes);
                 HIP_TRY(launch_position_columns(ppw, (int32_t*)(rows_tmp + rows_bytes), c.Bc, layP, s));
             }
-            for (int q = 0; q < layP; ++q)
-                HIP_TRY(launch_final_head(c.w.h, c.w.res, e->normf_w, e->emb, e->emb_f32, e->comp, rows_tmp + slot_bytes * q, nullptr, c.Bc, L, D,
-                                          eps, pos, col + (size_t)q * c.Bc, dt, rdt, s, false, ids_of(c), e->status, pl.fold ? Dp : 0));
-            if (slot >= 0)
-                HIP_TRY(launch_layer_rows(rows_tmp, lay_dst(slot, c.b0), c.Bc, L, D, pos, nullptr, layP, true, 1, c.Bc, rq.lay.average, dt, nullptr, s));
+            fh.h_compact = false;
+            for (int q = 0; q < layP; ++q) {         // slot q of every window: [P, Bc, 2D]
+                fh.hidden_out = rows_tmp + slot_bytes * q;
+                fh.pos_per_seq = col + (size_t)q * c.Bc;
+                HIP_TRY(launch_final_head(fh, s));
+            }
+            if (slot >= 0) HIP_TRY(emit(1, c.Bc));
         } else {
-            HIP_TRY(launch_final_head(c.w.h, c.w.res, e->normf_w, e->emb, e->emb_f32, e->comp, rows_tmp, nullptr, c.Bc, L, D, eps, pos, nullptr, dt,
-                                      rdt, s, pl.walk_len > 0, ids_of(c), e->status, pl.fold ? Dp : 0));
-            if (slot >= 0)
-                HIP_TRY(launch_layer_rows(rows_tmp, lay_dst(slot, c.b0), c.Bc, L, D, pos, nullptr, layP, true, layP, 1, rq.lay.average, dt, nullptr, s));
+            HIP_TRY(launch_final_head(fh, s));      // [Bc, P, 2D]
+            if (slot >= 0) HIP_TRY(emit(layP, 1));
         }
         return PCAD_OK;
     }

@@ -4,8 +4,27 @@
 // points at the mixer output's row.  res_frag != 0: fp32 residual in the GEMM's fragment layout of that (padded) width.
 #pragma once
 #include "common.hpp"
+#include "kernels.hpp"
 
 namespace pcad {
+
+// ---- host side: which <T, RT, MAXC> instantiation of a one-wave-per-row kernel family (norm.hip, pool.hip, loss.hip, probs.hip) a
+// launch runs.  A launcher names its family once, in a generic callable that takes the RowForm, and launches with one statement.
+template <typename T, typename RT, int MC>
+struct RowForm { using X = T;  using R = RT;  static constexpr int MAXC = MC; };      // activation type, residual type, 64-lane steps of 8 columns per row
+// the width selector: D <= 512 / <= 1024 / <= 2048 columns
+template <typename T, typename RT, typename F>
+static hipError_t select_row_width(int D, F&& f) {
+    return D <= 512 ? f(RowForm<T, RT, 1>{}) : D <= 1024 ? f(RowForm<T, RT, 2>{}) : f(RowForm<T, RT, 4>{});
+}
+// the dtype-pair selector: the three (activation, residual) pairs the library contains
+template <typename F>
+static hipError_t select_row_form(int dt, int rdt, int D, F&& f) {
+    if (dt == BF16 && rdt == F32) return select_row_width<bf16_t, float>(D, f);
+    if (dt == BF16 && rdt == BF16) return select_row_width<bf16_t, bf16_t>(D, f);
+    if (dt == F32 && rdt == F32) return select_row_width<float, float>(D, f);
+    return hipErrorInvalidValue;
+}
 
 // hidden_dst (or nullptr): the [2D] row of hidden_states[-1] this strand's half is written to (rc strand: reversed channels).
 // want_logits: acc[0..7] = the strand's 8 partial logits, rounded to the model dtype, the same value in every lane.

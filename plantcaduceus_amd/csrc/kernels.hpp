@@ -27,65 +27,122 @@ struct Positions {            // by-value kernel argument: the positions evaluat
 };
 
 // norm.hip --------------------------------------------------------------------------------------
-// fused residual add + RMSNorm (rms_norm_fn prenorm=True).  x/y dtype `dt`; residuals `rdt`.
-// split_y (dt == F32 only): y is written as a bf16 tensor [rows, 2 D] = [hi | lo] (pack.hip launch_split_rows' format).
-hipError_t launch_add_rmsnorm(const void* x, const void* res_in, const float* w, void* y, void* res_out,
-                              int64_t rows, int D, float eps, int dt, int rdt, hipStream_t s, bool split_y = false);
-// layer-0 variant: x = Emb[strand token] gathered on the fly (RCPS strands by index arithmetic).
-// rstd_out != nullptr: the norm-folded form - y (may be nullptr) = the un-normalised embedding row, rstd_out[row] = its rstd, and
-// res_out (fp32) is written in the 4-wave GEMM's fragment layout (common.hpp res_frag_off; 2 B L % 256 == 0) as a tensor of
-// Dp = round_up(D, 256) columns whose padding columns are zeroed; y rows are Dp elements apart.
-hipError_t launch_embed_rmsnorm(const int32_t* ids, const void* emb, const int32_t* comp8, const float* w,
-                                void* y, void* res_out, int B, int L, int D, float eps, int dt, int rdt,
-                                hipStream_t s, float* rstd_out = nullptr, int Dp = 0,     // Dp: padded width of res / y rows (0: D)
-                                bool split_y = false);
+// The norm and head launchers take a plain struct of named fields (defaults in place) and the stream, like the mixer launchers below.
+// fused residual add + RMSNorm (rms_norm_fn prenorm=True).
+struct NormLaunch {
+    const void* x = nullptr;          // [rows, D], dtype dt (launch_embed_rmsnorm: unused, the rows are gathered from EmbedRows::emb)
+    const void* res_in = nullptr;     // [rows, D], dtype rdt, or nullptr (launch_embed_rmsnorm: unused)
+    const float* w;                   // norm weight [D]
+    void* y;                          // [rows, D], dtype dt
+    void* res_out;                    // [rows, D], dtype rdt, or nullptr
+    int64_t rows = 0;                 // (launch_embed_rmsnorm: unused, 2 B L)
+    int D;  float eps;  int dt, rdt;
+    bool split_y = false;             // (dt == rdt == F32 only): y is written as a bf16 tensor [rows, 2 D] = [hi | lo] (pack.hip launch_split_rows' format)
+    // launch_embed_rmsnorm only.  rstd_out != nullptr: the norm-folded form - y (may be nullptr) = the un-normalised embedding row,
+    // rstd_out[row] = its rstd, and res_out (fp32) is written in the 4-wave GEMM's fragment layout (common.hpp res_frag_off;
+    // 2 B L % 256 == 0) as a tensor of Dp = round_up(D, 256) columns whose padding columns are zeroed; y rows are Dp elements apart.
+    float* rstd_out = nullptr;
+    int Dp = 0;                       // padded width of res / y rows (0: D)
+};
+hipError_t launch_add_rmsnorm(const NormLaunch& n, hipStream_t s);
+// layer-0 variant: x = Emb[strand token] gathered on the fly (RCPS strands by index arithmetic), rows = 2 B L.
+struct EmbedRows { const int32_t* ids;  const void* emb;  const int32_t* comp8;  int B, L; };     // ids [B, L], emb [8, D] (dtype dt)
+hipError_t launch_embed_rmsnorm(const NormLaunch& n, const EmbedRows& e, hipStream_t s);
 // rstd[row] = rsqrt(sum of the np partial sums of squares of the row / D + eps)
 hipError_t launch_rstd(const float* ssq, float* rstd, int64_t rows, int np, int D, float eps, hipStream_t s);
-// final add + norm_f + RC re-assembly + tied RCPS LM head, only at the requested positions (a shared list `pos`,
-// or one position per window from the device array `pos_per_seq` [B]).  h_compact: h holds only the evaluated rows,
-// [(strand * P + q), D] as launch_gather_rows orders them (the residual stream `res` is always the full tensor).
-// ids [B, L] + status (device word, or nullptr): token ids outside [0, 8) / per-window positions outside [0, L) set bits 1 / 2.
-hipError_t launch_final_head(const void* h, const void* res, const float* w, const void* emb,
-                             const float* emb_f32, const int32_t* comp8, void* hidden_out, float* logits_out,
-                             int B, int L, int D, float eps, Positions pos, const int32_t* pos_per_seq, int dt, int rdt,
-                             hipStream_t s, bool h_compact = false, const int32_t* ids = nullptr, int32_t* status = nullptr,
-                             int res_frag = 0);            // res_frag != 0: fp32 residual in the fragment layout (common.hpp res_frag_off) of that (padded) width
+
+// What every head (final / pooled / loss / probs) reads: the last mixer output, the residual stream and norm_f.
+struct HeadInput {
+    const void* h;                    // mixer output [2B * L, D], dtype dt (final / probs with h_compact: the evaluated rows only)
+    const void* res;                  // residual stream, always the full tensor [2B * L, D], dtype rdt
+    const float* w;                   // norm_f weight [D]
+    int B, L, D;  float eps;  int dt, rdt;
+    int res_frag = 0;                 // != 0: fp32 residual in the GEMM's fragment layout (common.hpp res_frag_off) of that (padded) width
+    const int32_t* ids = nullptr;     // [B, L] + status (device word): token ids outside [0, 8) set status bit 1
+    int32_t* status = nullptr;
+};
+// the heads' shared preconditions: the width the row kernels cover, a dtype pair they exist for, the fragment layout's shape
+inline hipError_t head_input_check(const HeadInput& in) {
+    if (in.D % 8 || in.D > 2048) return hipErrorInvalidValue;
+    if ((in.dt != BF16 && in.dt != F32) || (in.rdt != F32 && in.rdt != in.dt)) return hipErrorInvalidValue;
+    if (in.res_frag && (in.rdt != F32 || in.res_frag % 256 || in.res_frag < in.D || ((int64_t)2 * in.B * in.L) % 256)) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+// final add + norm_f + RC re-assembly + tied RCPS LM head, only at the requested positions.  Per-window positions outside [0, L)
+// are clamped and set bit 2 of in.status.
+struct FinalHeadLaunch {
+    HeadInput in;
+    const float* emb_f32;  const int32_t* comp8;      // the tied embedding [8, D] in fp32, the complement map [8]
+    void* hidden_out = nullptr;       // [B, Q, 2D], dtype dt, or nullptr
+    float* logits_out = nullptr;      // [B, Q, 8], or nullptr
+    Positions pos = {};               // the shared list (n == 0: all L positions)
+    const int32_t* pos_per_seq = nullptr;     // device [B]: one position per window instead (pos.n == 0)
+    bool h_compact = false;           // (shared list only): in.h holds only the evaluated rows, [(strand * P + q), D] as launch_gather_rows orders them
+};
+hipError_t launch_final_head(const FinalHeadLaunch& a, hipStream_t s);
 // pool.hip: pooled sequence-classification head (pcad.h pcad_pooled_head).  pooling: POOL_* (= pcad.h pcad_pooling).  Stage 1 writes
 // pool_partial_bytes(B, L, D, pooling) bytes of fp32 partials to `part` (256-byte aligned); the segmentation depends on L only.
 enum { POOL_MEAN = 0, POOL_MAX = 1, POOL_FIRST = 2, POOL_LAST = 3 };
 int pool_segments(int L, int pooling);
 size_t pool_partial_bytes(int B, int L, int D, int pooling);
-hipError_t launch_pooled_head(const void* h, const void* res, const float* w, const float* score_w, int NL, float* pooled_out,
-                              float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids, int32_t* status,
-                              int dt, int rdt, int res_frag, void* part, hipStream_t s);
-// loss.hip: masked-LM loss head (pcad.h pcad_loss_head): launch_final_head's logits at every position (positions == NULL form) + the cross
-// entropy of the labelled ones, reduced per window into sums_out [B, 4] = { sum w nll, sum w, labelled, arg-max hits }.  labels [B, L]
-// (ignored: == ignore_index or < 0; other values outside [0, 8) set status bit 4), loss_w [B, L] or nullptr (all 1); nll_out [B, L] and
-// logits_out [B, L, 8] may be nullptr.  Stage 1 writes loss_partial_bytes(B, L) bytes of fp32 partials to `part` (16-byte aligned);
+struct PooledHeadLaunch {
+    HeadInput in;
+    const float* score_w = nullptr;  int NL = 0;      // score head [NL, D], 1 <= NL <= 256 (needed for logits_out)
+    float* pooled_out = nullptr;      // [B, 2D] fp32, or nullptr
+    float* logits_out = nullptr;      // [B, NL], or nullptr
+    int pooling;
+    void* part;                       // the stage-1 partials
+};
+hipError_t launch_pooled_head(const PooledHeadLaunch& a, hipStream_t s);
+// loss.hip: masked-LM loss head (pcad.h pcad_loss_head): launch_final_head's logits at every position + the cross entropy of the
+// labelled ones, reduced per window.  Stage 1 writes loss_partial_bytes(B, L) bytes of fp32 partials to `part` (16-byte aligned);
 // the segmentation depends on L only.
 int loss_segments(int L);
 size_t loss_partial_bytes(int B, int L);
-hipError_t launch_loss_head(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8,
-                            const int32_t* labels, const float* loss_w, int ignore_index, float* sums_out, float* nll_out,
-                            float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dt, int rdt,
-                            int res_frag, void* part, hipStream_t s);
+struct LossHeadLaunch {
+    HeadInput in;
+    const float* emb_f32;  const int32_t* comp8;
+    const int32_t* labels;            // [B, L]; ignored: == ignore_index or < 0; other values outside [0, 8) set status bit 4
+    const float* loss_w = nullptr;    // [B, L], or nullptr (all 1)
+    int ignore_index;
+    float* sums_out;                  // [B, 4] = { sum w nll, sum w, labelled, arg-max hits }
+    float* nll_out = nullptr;         // [B, L], or nullptr
+    float* logits_out = nullptr;      // [B, L, 8], or nullptr
+    void* part;                       // the stage-1 partials
+};
+hipError_t launch_loss_head(const LossHeadLaunch& a, hipStream_t s);
 // probs.hip: nucleotide-probability head (pcad.h pcad_probs_head): launch_final_head's logits at the evaluated positions + the fp32
-// softmax over the four vocabulary columns `cols`, probs_out [B, Q, 4] (16-byte aligned); logits_out [B, Q, 8]; either may be nullptr.
-// Positions: all L (pos.n == 0), the shared list `pos` (h_compact allowed), or pos_per_window (device [B, Pw], 1 <= Pw <= 16, pos.n == 0;
-// values outside [0, L) are clamped and set status bit 2).
+// softmax over the four vocabulary columns `cols`.
 struct ProbCols { int c[4]; };        // by-value kernel argument
-hipError_t launch_probs_head(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8, ProbCols cols,
-                             float* probs_out, float* logits_out, int B, int L, int D, float eps, Positions pos,
-                             const int32_t* pos_per_window, int Pw, int dt, int rdt, hipStream_t s, bool h_compact = false,
-                             const int32_t* ids = nullptr, int32_t* status = nullptr, int res_frag = 0);
-// layers.hip: one level of hidden_states at the evaluated positions only (pcad.h pcad_layer_rows).  src: plain rows [2B * L, D] (a mixer
-// output h / the RCPS embedding), or - assembled - rows of 2D elements already in the reference's layout, the row of (window b, slot q)
-// at row index b * sb + q * sq (final_head_kernel's hidden_out; positions are not read).  out: model dtype [B, P, 2D] =
-// launch_assemble_hidden's rows (b, p_q), or - average - fp32 [B, P, D] = (fwd + rc) * 0.5 in straight channel order.  Positions: the
-// shared list `pos` (pos.n == P) or pos_per_window (device [B, P]; values outside [0, L) are clamped and set status bit 2).
-hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* pos_per_window, int P,
-                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s,
-                             bool compact = false);     // compact (shared list, not assembled): src = launch_gather_rows' [2B, P, D] rows of h
+struct ProbsHeadLaunch {
+    HeadInput in;
+    const float* emb_f32;  const int32_t* comp8;
+    ProbCols cols;
+    float* probs_out = nullptr;       // [B, Q, 4] (16-byte aligned), or nullptr
+    float* logits_out = nullptr;      // [B, Q, 8], or nullptr
+    Positions pos = {};               // the shared list (n == 0: all L positions, or the per-window list)
+    const int32_t* pos_per_window = nullptr;  int Pw = 0;     // device [B, Pw], 1 <= Pw <= 16, pos.n == 0; values outside [0, L) are clamped and set status bit 2
+    bool h_compact = false;           // (shared list only): in.h holds only the evaluated rows
+};
+hipError_t launch_probs_head(const ProbsHeadLaunch& a, hipStream_t s);
+// layers.hip: one level of hidden_states at the evaluated positions only (pcad.h pcad_layer_rows).
+struct LayerRowsLaunch {
+    const void* src;                  // plain rows [2B * L, D] (a mixer output h / the RCPS embedding), or see assembled / compact
+    // model dtype [B, P, 2D] = launch_assemble_hidden's rows (b, p_q), or - average - fp32 [B, P, D] = (fwd + rc) * 0.5 in straight channel order
+    void* out;
+    int B, L, D, dt;
+    Positions pos = {};               // the shared list (pos.n == P), unless pos_per_window or assembled
+    const int32_t* pos_per_window = nullptr;  // device [B, P]; values outside [0, L) are clamped and set status bit 2
+    int P;
+    // src holds rows of 2D elements already in the reference's layout (final_head_kernel's hidden_out; positions are not read):
+    bool assembled = false;
+    int64_t sb = 0;                   // (assembled) rows between two windows' slot 0: the row of (window b, slot q) is b * sb + q * sq
+    int64_t sq = 0;                   // (assembled) rows between two slots of a window
+    bool average = false;
+    bool compact = false;             // (shared list, not assembled): src = launch_gather_rows' [2B, P, D] rows of h
+    int32_t* status = nullptr;
+};
+hipError_t launch_layer_rows(const LayerRowsLaunch& a, hipStream_t s);
 // token ids outside [0, 8) among ids[0, n) (any 4-byte alignment) set status bit 1, as the heads' own check does; status == nullptr: no launch
 hipError_t launch_ids_check(const int32_t* ids, int64_t n, int32_t* status, hipStream_t s);
 // dst [P, B] = the columns of src [B, P] (device int32): slot q's positions of every window as one contiguous list
@@ -352,9 +409,15 @@ size_t norm_bwd_bytes(int64_t rows, int D);
 hipError_t launch_norm_bwd(const NormBwdLaunch& a, hipStream_t s);
 
 // pack.hip --------------------------------------------------------------------------------------
-// rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor (plain or blocked) -> out[(strand * P + q), E]
-hipError_t launch_gather_rows(const void* src, void* out, int B, int L, int E, Positions pos, int dt, bool blocked,
-                              hipStream_t s);
+// rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor -> out[(strand * P + q), E]
+struct GatherRowsLaunch {
+    const void* src;  void* out;
+    int B, L, E;
+    Positions pos;
+    int dt;
+    bool blocked = false;             // src is in the blocked layout (common.hpp::blocked_off)
+};
+hipError_t launch_gather_rows(const GatherRowsLaunch& g, hipStream_t s);
 // generic 2-D copy/convert with zero padding: dst[r, c] (dst_dt, ld = dst_ld) = src[r, c] for r < rows, c < cols else 0
 hipError_t launch_pack2d(const void* src, int src_dt, int64_t src_ld, void* dst, int dst_dt, int64_t dst_ld,
                          int rows, int cols, int dst_rows, int dst_cols, hipStream_t s);

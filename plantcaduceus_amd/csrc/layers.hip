@@ -107,31 +107,30 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void layer_rows_kernel(const T* 
 }
 
 template <typename T>
-static hipError_t launch_layer_rows_t(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* ppw, int P,
-                                      bool assembled, int64_t sb, int64_t sq, bool average, int32_t* status, hipStream_t s, bool compact) {
-    const int64_t items = (int64_t)B * P;
-    const dim3 grid((unsigned)((items + LAYERS_WAVES - 1) / LAYERS_WAVES)), blk(64 * LAYERS_WAVES);
-#define PCAD_LAYER_ROWS(AVG, ASM, CMP) \
-    hipLaunchKernelGGL((layer_rows_kernel<T, AVG, ASM, CMP>), grid, blk, 0, s, (const T*)src, out, B, L, D, pos, ppw, P, sb, sq, status)
-    if (average) { if (assembled) PCAD_LAYER_ROWS(true, true, false); else if (compact) PCAD_LAYER_ROWS(true, false, true); else PCAD_LAYER_ROWS(true, false, false); }
-    else { if (assembled) PCAD_LAYER_ROWS(false, true, false); else if (compact) PCAD_LAYER_ROWS(false, false, true); else PCAD_LAYER_ROWS(false, false, false); }
-#undef PCAD_LAYER_ROWS
+static hipError_t launch_layer_rows_t(const LayerRowsLaunch& a, hipStream_t s) {
+    // the six instantiations, by [average][source: plain / assembled / compact]
+    static constexpr decltype(&layer_rows_kernel<T, false, false, false>) kernels[2][3] = {
+        {layer_rows_kernel<T, false, false, false>, layer_rows_kernel<T, false, true, false>, layer_rows_kernel<T, false, false, true>},
+        {layer_rows_kernel<T, true, false, false>, layer_rows_kernel<T, true, true, false>, layer_rows_kernel<T, true, false, true>}};
+    const int64_t blocks = ((int64_t)a.B * a.P + LAYERS_WAVES - 1) / LAYERS_WAVES;
+    hipLaunchKernelGGL(kernels[a.average ? 1 : 0][a.assembled ? 1 : a.compact ? 2 : 0], dim3((unsigned)blocks), dim3(64 * LAYERS_WAVES), 0, s, (const T*)a.src, a.out,
+                       a.B, a.L, a.D, a.pos, a.pos_per_window, a.P, a.sb, a.sq, a.status);
     return hipGetLastError();
 }
 
-hipError_t launch_layer_rows(const void* src, void* out, int B, int L, int D, Positions pos, const int32_t* pos_per_window, int P,
-                             bool assembled, int64_t sb, int64_t sq, bool average, int dt, int32_t* status, hipStream_t s, bool compact) {
-    if (compact && (assembled || pos_per_window)) return hipErrorInvalidValue;        // the gathered rows exist for a shared list only
-    if (D <= 0 || D % 8 || L <= 0 || P < 1 || P > 16) return hipErrorInvalidValue;
-    if (!assembled && !pos_per_window && pos.n != P) return hipErrorInvalidValue;
-    if (!assembled && !pos_per_window)
-        for (int i = 0; i < P; ++i)
-            if (pos.p[i] < 0 || pos.p[i] >= L) return hipErrorInvalidValue;
-    if (((uintptr_t)src) % 16 || ((uintptr_t)out) % 16) return hipErrorInvalidValue;      // 16-byte pieces
-    if (B <= 0) return hipSuccess;
-    if (((int64_t)B * P + LAYERS_WAVES - 1) / LAYERS_WAVES > 0x7fffffff) return hipErrorInvalidValue;
-    if (dt == BF16) return launch_layer_rows_t<bf16_t>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s, compact);
-    if (dt == F32) return launch_layer_rows_t<float>(src, out, B, L, D, pos, pos_per_window, P, assembled, sb, sq, average, status, s, compact);
+hipError_t launch_layer_rows(const LayerRowsLaunch& a, hipStream_t s) {
+    const bool shared = !a.assembled && !a.pos_per_window;
+    if (a.compact && !shared) return hipErrorInvalidValue;        // the gathered rows exist for a shared list only
+    if (a.D <= 0 || a.D % 8 || a.L <= 0 || a.P < 1 || a.P > 16) return hipErrorInvalidValue;
+    if (shared && a.pos.n != a.P) return hipErrorInvalidValue;
+    if (shared)
+        for (int i = 0; i < a.P; ++i)
+            if (a.pos.p[i] < 0 || a.pos.p[i] >= a.L) return hipErrorInvalidValue;
+    if (((uintptr_t)a.src) % 16 || ((uintptr_t)a.out) % 16) return hipErrorInvalidValue;      // 16-byte pieces
+    if (a.B <= 0) return hipSuccess;
+    if (((int64_t)a.B * a.P + LAYERS_WAVES - 1) / LAYERS_WAVES > 0x7fffffff) return hipErrorInvalidValue;
+    if (a.dt == BF16) return launch_layer_rows_t<bf16_t>(a, s);
+    if (a.dt == F32) return launch_layer_rows_t<float>(a, s);
     return hipErrorInvalidValue;
 }
 

@@ -110,41 +110,23 @@ __global__ __launch_bounds__(64) void loss_stage2_kernel(const float* __restrict
     sums_out[(int64_t)b * 4 + k] = a;
 }
 
-template <typename T, typename RT>
-static hipError_t launch_loss_t(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8,
-                                const int32_t* labels, const float* loss_w, int ignore_index, float* sums_out, float* nll_out,
-                                float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int res_frag,
-                                float* part, hipStream_t s) {
-    const int nseg = loss_segments(L);
-    const dim3 g1((unsigned)((int64_t)B * nseg)), blk(256);
-#define PCAD_LOSS1(MC)                                                                                                          \
-    hipLaunchKernelGGL((loss_stage1_kernel<T, RT, MC>), g1, blk, 0, s, (const T*)h, (const RT*)res, w, emb_f32, comp8, labels, \
-                       loss_w, ignore_index, part, nll_out, logits_out, B, L, D, eps, nseg, ids, status, res_frag)
-    if (D <= 512) PCAD_LOSS1(1);
-    else if (D <= 1024) PCAD_LOSS1(2);
-    else PCAD_LOSS1(4);
-#undef PCAD_LOSS1
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(loss_stage2_kernel, dim3((unsigned)B), dim3(64), 0, s, (const float*)part, sums_out, nseg);
-    return hipGetLastError();
-}
-
-hipError_t launch_loss_head(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8,
-                            const int32_t* labels, const float* loss_w, int ignore_index, float* sums_out, float* nll_out,
-                            float* logits_out, int B, int L, int D, float eps, const int32_t* ids, int32_t* status, int dt, int rdt,
-                            int res_frag, void* part, hipStream_t s) {
-    if (D % 8 || D > 2048 || L <= 0 || labels == nullptr || sums_out == nullptr || part == nullptr) return hipErrorInvalidValue;
-    if (res_frag && (rdt != F32 || res_frag % 256 || res_frag < D || ((int64_t)2 * B * L) % 256)) return hipErrorInvalidValue;
-    if (B <= 0) return hipSuccess;
-    if ((int64_t)B * loss_segments(L) > 0x7fffffff) return hipErrorInvalidValue;
-    float* pp = (float*)part;
-    if (dt == BF16 && rdt == F32)
-        return launch_loss_t<bf16_t, float>(h, res, w, emb_f32, comp8, labels, loss_w, ignore_index, sums_out, nll_out, logits_out, B, L, D, eps, ids, status, res_frag, pp, s);
-    if (dt == BF16 && rdt == BF16)
-        return launch_loss_t<bf16_t, bf16_t>(h, res, w, emb_f32, comp8, labels, loss_w, ignore_index, sums_out, nll_out, logits_out, B, L, D, eps, ids, status, res_frag, pp, s);
-    if (dt == F32 && rdt == F32)
-        return launch_loss_t<float, float>(h, res, w, emb_f32, comp8, labels, loss_w, ignore_index, sums_out, nll_out, logits_out, B, L, D, eps, ids, status, res_frag, pp, s);
-    return hipErrorInvalidValue;
+hipError_t launch_loss_head(const LossHeadLaunch& a, hipStream_t s) {
+    const HeadInput& in = a.in;
+    if (hipError_t e = head_input_check(in)) return e;
+    if (in.L <= 0 || a.labels == nullptr || a.sums_out == nullptr || a.part == nullptr) return hipErrorInvalidValue;
+    if (in.B <= 0) return hipSuccess;
+    const int nseg = loss_segments(in.L);
+    if ((int64_t)in.B * nseg > 0x7fffffff) return hipErrorInvalidValue;
+    return select_row_form(in.dt, in.rdt, in.D, [&](auto form) {
+        using T = typename decltype(form)::X;
+        using RT = typename decltype(form)::R;
+        hipLaunchKernelGGL((loss_stage1_kernel<T, RT, decltype(form)::MAXC>), dim3((unsigned)((int64_t)in.B * nseg)), dim3(256), 0, s, (const T*)in.h, (const RT*)in.res,
+                           in.w, a.emb_f32, a.comp8, a.labels, a.loss_w, a.ignore_index, (float*)a.part, a.nll_out, a.logits_out, in.B, in.L, in.D, in.eps, nseg,
+                           in.ids, in.status, in.res_frag);
+        if (hipError_t e = hipGetLastError()) return e;
+        hipLaunchKernelGGL(loss_stage2_kernel, dim3((unsigned)in.B), dim3(64), 0, s, (const float*)a.part, a.sums_out, nseg);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace pcad

@@ -135,75 +135,37 @@ hipError_t launch_rstd(const float* ssq, float* rstd, int64_t rows, int np, int 
     return hipGetLastError();
 }
 
-template <typename T, typename RT, bool EMBED>
-static hipError_t launch_norm_t(const T* x, const RT* res_in, const float* w, T* y, RT* res_out, int64_t rows, int D,
-                                float eps, const int32_t* ids, const int32_t* comp8, int B, int L, hipStream_t s,
-                                float* rstd_out = nullptr, int Dp = 0, bool split = false) {
-    if (rows <= 0) return hipSuccess;
-    dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    if constexpr (std::is_same<T, float>::value && std::is_same<RT, float>::value) {
-        if (split) {                          // fp32 model, split-bf16 in_proj operand
-            if (D <= 512)
-                hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 1, EMBED, false, true>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D, eps, ids, comp8, B, L, nullptr, 0);
-            else if (D <= 1024)
-                hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 2, EMBED, false, true>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D, eps, ids, comp8, B, L, nullptr, 0);
-            else
-                hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 4, EMBED, false, true>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D, eps, ids, comp8, B, L, nullptr, 0);
-            return hipGetLastError();
-        }
-    }
-    if (split) return hipErrorInvalidValue;
-    if constexpr (EMBED) {
-        if (rstd_out != nullptr) {            // layer 0 of the norm-folded form
-            if (D <= 512)
-                hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 1, true, true>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D, eps, ids, comp8, B, L, rstd_out, Dp);
-            else if (D <= 1024)
-                hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 2, true, true>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D, eps, ids, comp8, B, L, rstd_out, Dp);
-            else
-                hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 4, true, true>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D, eps, ids, comp8, B, L, rstd_out, Dp);
-            return hipGetLastError();
-        }
-    }
-    if (D <= 512)
-        hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 1, EMBED>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D,
-                           eps, ids, comp8, B, L);
-    else if (D <= 1024)
-        hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 2, EMBED>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D,
-                           eps, ids, comp8, B, L);
-    else
-        hipLaunchKernelGGL((add_rmsnorm_kernel<T, RT, 4, EMBED>), grid, block, 0, s, x, res_in, w, y, res_out, rows, D,
-                           eps, ids, comp8, B, L);
-    return hipGetLastError();
-}
-
+// One entry for both forms.  The kernel family: <T, RT, MAXC, EMBED> plain, <.., EMBED, false, true> split (fp32 only) and
+// <.., true, true> folded (embed only).
 template <bool EMBED>
-static hipError_t dispatch_norm(const void* x, const void* res_in, const float* w, void* y, void* res_out,
-                                int64_t rows, int D, float eps, int dt, int rdt, const int32_t* ids,
-                                const int32_t* comp8, int B, int L, hipStream_t s, float* rstd_out = nullptr, int Dp = 0, bool split = false) {
-    if (D % 8 || D > 2048) return hipErrorInvalidValue;
-    if (split && !(dt == F32 && rdt == F32 && rstd_out == nullptr)) return hipErrorInvalidValue;
-    if (Dp == 0) Dp = D;
-    if (dt == BF16 && rdt == F32)
-        return launch_norm_t<bf16_t, float, EMBED>((const bf16_t*)x, (const float*)res_in, w, (bf16_t*)y,
-                                                    (float*)res_out, rows, D, eps, ids, comp8, B, L, s, rstd_out, Dp);
-    if (dt == BF16 && rdt == BF16)
-        return launch_norm_t<bf16_t, bf16_t, EMBED>((const bf16_t*)x, (const bf16_t*)res_in, w, (bf16_t*)y,
-                                                     (bf16_t*)res_out, rows, D, eps, ids, comp8, B, L, s, rstd_out, Dp);
-    if (dt == F32 && rdt == F32)
-        return launch_norm_t<float, float, EMBED>((const float*)x, (const float*)res_in, w, (float*)y,
-                                                   (float*)res_out, rows, D, eps, ids, comp8, B, L, s, rstd_out, Dp, split);
-    return hipErrorInvalidValue;
+static hipError_t launch_norm(const NormLaunch& n, const EmbedRows& e, int64_t rows, hipStream_t s) {
+    if (n.D % 8 || n.D > 2048) return hipErrorInvalidValue;
+    if (n.split_y && !(n.dt == F32 && n.rdt == F32 && n.rstd_out == nullptr)) return hipErrorInvalidValue;
+    if (!EMBED && (n.rstd_out != nullptr || n.Dp != 0)) return hipErrorInvalidValue;
+    return select_row_form(n.dt, n.rdt, n.D, [&](auto form) {
+        using T = typename decltype(form)::X;
+        using RT = typename decltype(form)::R;
+        constexpr int MAXC = decltype(form)::MAXC;
+        if (rows <= 0) return hipSuccess;
+        auto launch = [&](auto kernel, float* rstd_out, int Dp) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const T*)(EMBED ? e.emb : n.x), (const RT*)(EMBED ? nullptr : n.res_in),
+                               n.w, (T*)n.y, (RT*)n.res_out, rows, n.D, n.eps, e.ids, e.comp8, e.B, e.L, rstd_out, Dp);
+            return hipGetLastError();
+        };
+        if constexpr (std::is_same<T, float>::value)
+            if (n.split_y) return launch(add_rmsnorm_kernel<T, RT, MAXC, EMBED, false, true>, nullptr, 0);      // fp32 model, split-bf16 in_proj operand
+        if constexpr (EMBED)
+            if (n.rstd_out != nullptr) return launch(add_rmsnorm_kernel<T, RT, MAXC, true, true>, n.rstd_out, n.Dp ? n.Dp : n.D);      // layer 0 of the norm-folded form
+        return launch(add_rmsnorm_kernel<T, RT, MAXC, EMBED>, nullptr, 0);
+    });
 }
 
-hipError_t launch_add_rmsnorm(const void* x, const void* res_in, const float* w, void* y, void* res_out, int64_t rows,
-                              int D, float eps, int dt, int rdt, hipStream_t s, bool split_y) {
-    return dispatch_norm<false>(x, res_in, w, y, res_out, rows, D, eps, dt, rdt, nullptr, nullptr, 0, 1, s, nullptr, 0, split_y);
+hipError_t launch_add_rmsnorm(const NormLaunch& n, hipStream_t s) {
+    return launch_norm<false>(n, {.ids = nullptr, .emb = nullptr, .comp8 = nullptr, .B = 0, .L = 1}, n.rows, s);
 }
 
-hipError_t launch_embed_rmsnorm(const int32_t* ids, const void* emb, const int32_t* comp8, const float* w, void* y,
-                                void* res_out, int B, int L, int D, float eps, int dt, int rdt, hipStream_t s, float* rstd_out, int Dp,
-                                bool split_y) {
-    return dispatch_norm<true>(emb, nullptr, w, y, res_out, (int64_t)2 * B * L, D, eps, dt, rdt, ids, comp8, B, L, s, rstd_out, Dp, split_y);
+hipError_t launch_embed_rmsnorm(const NormLaunch& n, const EmbedRows& e, hipStream_t s) {
+    return launch_norm<true>(n, e, (int64_t)2 * e.B * e.L, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -267,40 +229,20 @@ __global__ __launch_bounds__(128) void final_head_kernel(const T* __restrict__ h
     }
 }
 
-template <typename T, typename RT>
-static hipError_t launch_final_t(const void* h, const void* res, const float* w, const float* emb_f32,
-                                 const int32_t* comp8, void* hidden_out, float* logits_out, int B, int L, int D,
-                                 float eps, Positions pos, const int32_t* pos_per_seq, hipStream_t s, int h_compact,
-                                 const int32_t* ids, int32_t* status, int res_frag) {
-    const int Q = pos_per_seq ? 1 : (pos.n ? pos.n : L);
-    dim3 grid((unsigned)(B * Q)), block(128);
-    if (B * Q == 0) return hipSuccess;
-#define PCAD_FH(MC)                                                                                          \
-    hipLaunchKernelGGL((final_head_kernel<T, RT, MC>), grid, block, 0, s, (const T*)h, (const RT*)res, w, emb_f32, \
-                       comp8, (T*)hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq, h_compact, ids, status, res_frag)
-    if (D <= 512) PCAD_FH(1);
-    else if (D <= 1024) PCAD_FH(2);
-    else PCAD_FH(4);
-#undef PCAD_FH
-    return hipGetLastError();
-}
-
-hipError_t launch_final_head(const void* h, const void* res, const float* w, const void* /*emb*/,
-                             const float* emb_f32, const int32_t* comp8, void* hidden_out, float* logits_out, int B,
-                             int L, int D, float eps, Positions pos, const int32_t* pos_per_seq, int dt, int rdt,
-                             hipStream_t s, bool h_compact, const int32_t* ids, int32_t* status, int res_frag) {
-    if (D % 8 || D > 2048) return hipErrorInvalidValue;
-    if (h_compact && (pos_per_seq || pos.n == 0)) return hipErrorInvalidValue;
-    if (res_frag && (rdt != F32 || res_frag % 256 || res_frag < D || ((int64_t)2 * B * L) % 256)) return hipErrorInvalidValue;
-    const int hc = h_compact ? 1 : 0;
-    const int rf = res_frag;
-    if (dt == BF16 && rdt == F32)
-        return launch_final_t<bf16_t, float>(h, res, w, emb_f32, comp8, hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq, s, hc, ids, status, rf);
-    if (dt == BF16 && rdt == BF16)
-        return launch_final_t<bf16_t, bf16_t>(h, res, w, emb_f32, comp8, hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq, s, hc, ids, status, rf);
-    if (dt == F32 && rdt == F32)
-        return launch_final_t<float, float>(h, res, w, emb_f32, comp8, hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq, s, hc, ids, status, rf);
-    return hipErrorInvalidValue;
+hipError_t launch_final_head(const FinalHeadLaunch& a, hipStream_t s) {
+    const HeadInput& in = a.in;
+    if (hipError_t e = head_input_check(in)) return e;
+    if (a.h_compact && (a.pos_per_seq || a.pos.n == 0)) return hipErrorInvalidValue;
+    const int Q = a.pos_per_seq ? 1 : (a.pos.n ? a.pos.n : in.L);
+    if (in.B * Q == 0) return hipSuccess;
+    return select_row_form(in.dt, in.rdt, in.D, [&](auto form) {
+        using T = typename decltype(form)::X;
+        using RT = typename decltype(form)::R;
+        hipLaunchKernelGGL((final_head_kernel<T, RT, decltype(form)::MAXC>), dim3((unsigned)(in.B * Q)), dim3(128), 0, s, (const T*)in.h, (const RT*)in.res, in.w,
+                           a.emb_f32, a.comp8, (T*)a.hidden_out, a.logits_out, in.B, in.L, in.D, in.eps, a.pos, a.pos_per_seq, a.h_compact ? 1 : 0,
+                           in.ids, in.status, in.res_frag);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -11,6 +11,12 @@ static int head_args(const char* who, int B, int L, int D, int dtype, int res_dt
     if (B < 0 || L <= 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "%s: bad B / L / D", who);
     return PCAD_OK;
 }
+// the checked arguments as the launchers' HeadInput
+static HeadInput head_input(const void* h, const void* res, const float* norm_weight, int B, int L, int D, float eps, int dtype, int res_dtype,
+                            int res_fragment_layout, const int32_t* ids, int32_t* status) {
+    return {.h = h, .res = res, .w = norm_weight, .B = B, .L = L, .D = D, .eps = eps, .dt = dtype, .rdt = res_dtype, .res_frag = res_fragment_layout ? D : 0,
+            .ids = ids, .status = status};
+}
 
 extern "C" {
 
@@ -18,7 +24,7 @@ int pcad_add_rmsnorm(const void* x, const void* residual_in, const float* weight
                      int64_t rows, int D, float eps, int dtype, int res_dtype, pcad_stream stream) {
     if (!x || !weight || !y) return fail(PCAD_ERR_INVALID, "pcad_add_rmsnorm: null argument");
     if (rows < 0 || D <= 0 || D % 8 || D > 2048) return fail(PCAD_ERR_INVALID, "pcad_add_rmsnorm: bad rows/D");
-    HIP_TRY(launch_add_rmsnorm(x, residual_in, weight, y, residual_out, rows, D, eps, dtype, res_dtype,
+    HIP_TRY(launch_add_rmsnorm({.x = x, .res_in = residual_in, .w = weight, .y = y, .res_out = residual_out, .rows = rows, .D = D, .eps = eps, .dt = dtype, .rdt = res_dtype},
                                (hipStream_t)stream));
     return PCAD_OK;
 }
@@ -373,7 +379,7 @@ int pcad_gather_rows(const void* src, void* out, int B, int L, int E, const int3
     Positions pos;
     if (int rc = positions_arg("pcad_gather_rows", positions, P, L, &pos)) return rc;
     if (B == 0) return PCAD_OK;
-    HIP_TRY(launch_gather_rows(src, out, B, L, E, pos, dtype, false, (hipStream_t)stream));
+    HIP_TRY(launch_gather_rows({.src = src, .out = out, .B = B, .L = L, .E = E, .pos = pos, .dt = dtype}, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -389,8 +395,8 @@ int pcad_layer_rows(const void* src, void* out, int B, int L, int D, const int32
     if (int rc = positions_arg("pcad_layer_rows", pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, L, &pos)) return rc;
     if (P > PCAD_MAX_POSITIONS) return fail(PCAD_ERR_INVALID, "pcad_layer_rows: bad positions (P=%d)", P);
     if (B == 0) return PCAD_OK;
-    HIP_TRY(launch_layer_rows(src, out, B, L, D, pos, assembled ? nullptr : pos_per_window, P, assembled != 0, P, 1, average != 0, dtype, status,
-                              (hipStream_t)stream));
+    HIP_TRY(launch_layer_rows({.src = src, .out = out, .B = B, .L = L, .D = D, .dt = dtype, .pos = pos, .pos_per_window = assembled ? nullptr : pos_per_window, .P = P,
+                               .assembled = assembled != 0, .sb = P, .sq = 1, .average = average != 0, .status = status}, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -405,8 +411,9 @@ int pcad_final_head(const void* h, const void* res, const float* norm_weight, co
     Positions pos;
     if (int rc = positions_arg("pcad_final_head", positions, P, L, &pos)) return rc;
     if (B == 0) return PCAD_OK;
-    HIP_TRY(launch_final_head(h, res, norm_weight, nullptr, emb_f32, complement, hidden_out, logits_out, B, L, D, eps, pos, pos_per_seq,
-                              dtype, res_dtype, (hipStream_t)stream, h_compact != 0, ids, status, res_fragment_layout ? D : 0));
+    HIP_TRY(launch_final_head({.in = head_input(h, res, norm_weight, B, L, D, eps, dtype, res_dtype, res_fragment_layout, ids, status), .emb_f32 = emb_f32,
+                               .comp8 = complement, .hidden_out = hidden_out, .logits_out = logits_out, .pos = pos, .pos_per_seq = pos_per_seq,
+                               .h_compact = h_compact != 0}, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -428,8 +435,8 @@ int pcad_pooled_head(const void* h, const void* res, const float* norm_weight, c
     if (B == 0) return PCAD_OK;
     if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_pooled_head_scratch_bytes(B, L, D, pooling))
         return fail(PCAD_ERR_WORKSPACE, "pcad_pooled_head: scratch must be 256-byte aligned and pcad_pooled_head_scratch_bytes large");
-    HIP_TRY(launch_pooled_head(h, res, norm_weight, score_w, num_labels, pooled_out, logits_out, B, L, D, eps, pooling, ids, status,
-                               dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
+    HIP_TRY(launch_pooled_head({.in = head_input(h, res, norm_weight, B, L, D, eps, dtype, res_dtype, res_fragment_layout, ids, status), .score_w = score_w,
+                                .NL = num_labels, .pooled_out = pooled_out, .logits_out = logits_out, .pooling = pooling, .part = scratch}, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -448,8 +455,9 @@ int pcad_loss_head(const void* h, const void* res, const float* norm_weight, con
     if (B == 0) return PCAD_OK;
     if (((uintptr_t)scratch) % 256 || scratch_bytes < pcad_loss_head_scratch_bytes(B, L))
         return fail(PCAD_ERR_WORKSPACE, "pcad_loss_head: scratch must be 256-byte aligned and pcad_loss_head_scratch_bytes large");
-    HIP_TRY(launch_loss_head(h, res, norm_weight, emb_f32, complement, labels, loss_weights, ignore_index, sums_out, nll_out, logits_out,
-                             B, L, D, eps, ids, status, dtype, res_dtype, res_fragment_layout ? D : 0, scratch, (hipStream_t)stream));
+    HIP_TRY(launch_loss_head({.in = head_input(h, res, norm_weight, B, L, D, eps, dtype, res_dtype, res_fragment_layout, ids, status), .emb_f32 = emb_f32,
+                              .comp8 = complement, .labels = labels, .loss_w = loss_weights, .ignore_index = ignore_index, .sums_out = sums_out, .nll_out = nll_out,
+                              .logits_out = logits_out, .part = scratch}, (hipStream_t)stream));
     return PCAD_OK;
 }
 
@@ -470,9 +478,9 @@ int pcad_probs_head(const void* h, const void* res, const float* norm_weight, co
     Positions pos;
     if (int rc = positions_arg("pcad_probs_head", pos_per_window ? nullptr : positions, pos_per_window ? 0 : P, L, &pos)) return rc;
     if (B == 0) return PCAD_OK;
-    HIP_TRY(launch_probs_head(h, res, norm_weight, emb_f32, complement, pc, probs_out, logits_out, B, L, D, eps, pos, pos_per_window,
-                              pos_per_window ? P : 0, dtype, res_dtype, (hipStream_t)stream, h_compact != 0, ids, status,
-                              res_fragment_layout ? D : 0));
+    HIP_TRY(launch_probs_head({.in = head_input(h, res, norm_weight, B, L, D, eps, dtype, res_dtype, res_fragment_layout, ids, status), .emb_f32 = emb_f32,
+                               .comp8 = complement, .cols = pc, .probs_out = probs_out, .logits_out = logits_out, .pos = pos, .pos_per_window = pos_per_window,
+                               .Pw = pos_per_window ? P : 0, .h_compact = h_compact != 0}, (hipStream_t)stream));
     return PCAD_OK;
 }
 

@@ -235,15 +235,14 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ 
     }
 }
 
-hipError_t launch_gather_rows(const void* src, void* out, int B, int L, int E, Positions pos, int dt, bool blocked,
-                              hipStream_t s) {
-    const int64_t rows = (int64_t)2 * B * pos.n;
+hipError_t launch_gather_rows(const GatherRowsLaunch& g, hipStream_t s) {
+    const int64_t rows = (int64_t)2 * g.B * g.pos.n;
     if (rows <= 0) return hipSuccess;
-    const int esz = dt == BF16 ? 2 : 4;
-    if ((E * esz) % 16 || (blocked && (E * esz) % 128)) return hipErrorInvalidValue;
+    const int esz = g.dt == BF16 ? 2 : 4;
+    if ((g.E * esz) % 16 || (g.blocked && (g.E * esz) % 128)) return hipErrorInvalidValue;
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    if (dt == BF16) hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)src, (bf16_t*)out, B, L, E, pos, (int)blocked);
-    else hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, s, (const float*)src, (float*)out, B, L, E, pos, (int)blocked);
+    if (g.dt == BF16) hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)g.src, (bf16_t*)g.out, g.B, g.L, g.E, g.pos, (int)g.blocked);
+    else hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, s, (const float*)g.src, (float*)g.out, g.B, g.L, g.E, g.pos, (int)g.blocked);
     return hipGetLastError();
 }
 

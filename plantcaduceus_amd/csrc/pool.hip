@@ -13,6 +13,7 @@
 //            vectors are kept in LDS and 4 waves run the [2, D] x [NL, D]^T product (fp32 accumulation, a fixed lane order).
 // The segmentation depends on L only, so a window's logits do not depend on the batch or chunk it runs in.
 #include "common.hpp"
+#include "head_row.hpp"
 #include "kernels.hpp"
 
 namespace pcad {
@@ -158,40 +159,23 @@ __global__ __launch_bounds__(256) void pool_stage2_kernel(const float* __restric
     }
 }
 
-template <typename T, typename RT>
-static hipError_t launch_pool_t(const void* h, const void* res, const float* w, const float* score_w, int NL, float* pooled_out,
-                                float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids, int32_t* status,
-                                int res_frag, float* part, hipStream_t s) {
-    const int nseg = pool_segments(L, pooling);
-    const dim3 g1((unsigned)((int64_t)B * 2 * nseg)), blk(256);
-#define PCAD_POOL1(MC)                                                                                                       \
-    hipLaunchKernelGGL((pool_stage1_kernel<T, RT, MC>), g1, blk, 0, s, (const T*)h, (const RT*)res, w, part, B, L, D, eps, \
-                       pooling, nseg, ids, status, res_frag)
-    if (D <= 512) PCAD_POOL1(1);
-    else if (D <= 1024) PCAD_POOL1(2);
-    else PCAD_POOL1(4);
-#undef PCAD_POOL1
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL((pool_stage2_kernel<T>), dim3((unsigned)B), blk, 0, s, (const float*)part, score_w, pooled_out, logits_out, L,
-                       D, NL, pooling, nseg);
-    return hipGetLastError();
-}
-
-hipError_t launch_pooled_head(const void* h, const void* res, const float* w, const float* score_w, int NL, float* pooled_out,
-                              float* logits_out, int B, int L, int D, float eps, int pooling, const int32_t* ids, int32_t* status,
-                              int dt, int rdt, int res_frag, void* part, hipStream_t s) {
-    if (D % 8 || D > 2048 || L <= 0 || pooling < POOL_MEAN || pooling > POOL_LAST) return hipErrorInvalidValue;
-    if (logits_out != nullptr && (score_w == nullptr || NL < 1 || NL > 256)) return hipErrorInvalidValue;
-    if (res_frag && (rdt != F32 || res_frag % 256 || res_frag < D || ((int64_t)2 * B * L) % 256)) return hipErrorInvalidValue;
-    if (B <= 0) return hipSuccess;
-    float* pp = (float*)part;
-    if (dt == BF16 && rdt == F32)
-        return launch_pool_t<bf16_t, float>(h, res, w, score_w, NL, pooled_out, logits_out, B, L, D, eps, pooling, ids, status, res_frag, pp, s);
-    if (dt == BF16 && rdt == BF16)
-        return launch_pool_t<bf16_t, bf16_t>(h, res, w, score_w, NL, pooled_out, logits_out, B, L, D, eps, pooling, ids, status, res_frag, pp, s);
-    if (dt == F32 && rdt == F32)
-        return launch_pool_t<float, float>(h, res, w, score_w, NL, pooled_out, logits_out, B, L, D, eps, pooling, ids, status, res_frag, pp, s);
-    return hipErrorInvalidValue;
+hipError_t launch_pooled_head(const PooledHeadLaunch& a, hipStream_t s) {
+    const HeadInput& in = a.in;
+    if (hipError_t e = head_input_check(in)) return e;
+    if (in.L <= 0 || a.pooling < POOL_MEAN || a.pooling > POOL_LAST) return hipErrorInvalidValue;
+    if (a.logits_out != nullptr && (a.score_w == nullptr || a.NL < 1 || a.NL > 256)) return hipErrorInvalidValue;
+    if (in.B <= 0) return hipSuccess;
+    const int nseg = pool_segments(in.L, a.pooling);
+    return select_row_form(in.dt, in.rdt, in.D, [&](auto form) {
+        using T = typename decltype(form)::X;
+        using RT = typename decltype(form)::R;
+        hipLaunchKernelGGL((pool_stage1_kernel<T, RT, decltype(form)::MAXC>), dim3((unsigned)((int64_t)in.B * 2 * nseg)), dim3(256), 0, s, (const T*)in.h,
+                           (const RT*)in.res, in.w, (float*)a.part, in.B, in.L, in.D, in.eps, a.pooling, nseg, in.ids, in.status, in.res_frag);
+        if (hipError_t e = hipGetLastError()) return e;
+        hipLaunchKernelGGL((pool_stage2_kernel<T>), dim3((unsigned)in.B), dim3(256), 0, s, (const float*)a.part, a.score_w, a.pooled_out, a.logits_out, in.L,
+                           in.D, a.NL, a.pooling, nseg);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace pcad

@@ -81,45 +81,26 @@ __global__ __launch_bounds__(64 * PROBS_WAVES) void probs_head_kernel(const T* _
     *reinterpret_cast<f32x4*>(probs_out + item * 4) = f32x4{ex[0] / se, ex[1] / se, ex[2] / se, ex[3] / se};
 }
 
-template <typename T, typename RT>
-static hipError_t launch_probs_t(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8,
-                                 ProbCols cols, float* probs_out, float* logits_out, int B, int L, int D, float eps, Positions pos,
-                                 const int32_t* pos_per_window, int Pw, int h_compact, const int32_t* ids, int32_t* status,
-                                 int res_frag, hipStream_t s) {
-    const int64_t items = (int64_t)B * (pos_per_window ? Pw : (pos.n ? pos.n : L));
-    const dim3 grid((unsigned)((items + PROBS_WAVES - 1) / PROBS_WAVES)), blk(64 * PROBS_WAVES);
-#define PCAD_PROBS(MC)                                                                                                           \
-    hipLaunchKernelGGL((probs_head_kernel<T, RT, MC>), grid, blk, 0, s, (const T*)h, (const RT*)res, w, emb_f32, comp8, cols,   \
-                       probs_out, logits_out, B, L, D, eps, pos, pos_per_window, Pw, h_compact, ids, status, res_frag)
-    if (D <= 512) PCAD_PROBS(1);
-    else if (D <= 1024) PCAD_PROBS(2);
-    else PCAD_PROBS(4);
-#undef PCAD_PROBS
-    return hipGetLastError();
-}
-
-hipError_t launch_probs_head(const void* h, const void* res, const float* w, const float* emb_f32, const int32_t* comp8, ProbCols cols,
-                             float* probs_out, float* logits_out, int B, int L, int D, float eps, Positions pos,
-                             const int32_t* pos_per_window, int Pw, int dt, int rdt, hipStream_t s, bool h_compact, const int32_t* ids,
-                             int32_t* status, int res_frag) {
-    if (D % 8 || D > 2048 || L <= 0) return hipErrorInvalidValue;
-    if (pos_per_window && (pos.n != 0 || Pw < 1 || Pw > 16)) return hipErrorInvalidValue;
-    if (h_compact && (pos_per_window || pos.n == 0)) return hipErrorInvalidValue;
-    if (((uintptr_t)probs_out) % 16) return hipErrorInvalidValue;                    // one 16-byte store per row
+hipError_t launch_probs_head(const ProbsHeadLaunch& a, hipStream_t s) {
+    const HeadInput& in = a.in;
+    if (hipError_t e = head_input_check(in)) return e;
+    if (in.L <= 0) return hipErrorInvalidValue;
+    if (a.pos_per_window && (a.pos.n != 0 || a.Pw < 1 || a.Pw > 16)) return hipErrorInvalidValue;
+    if (a.h_compact && (a.pos_per_window || a.pos.n == 0)) return hipErrorInvalidValue;
+    if (((uintptr_t)a.probs_out) % 16) return hipErrorInvalidValue;                  // one 16-byte store per row
     for (int j = 0; j < 4; ++j)
-        if ((unsigned)cols.c[j] > 7u) return hipErrorInvalidValue;
-    if (res_frag && (rdt != F32 || res_frag % 256 || res_frag < D || ((int64_t)2 * B * L) % 256)) return hipErrorInvalidValue;
-    if (B <= 0 || (probs_out == nullptr && logits_out == nullptr)) return hipSuccess;
-    const int64_t items = (int64_t)B * (pos_per_window ? Pw : (pos.n ? pos.n : L));
-    if ((items + PROBS_WAVES - 1) / PROBS_WAVES > 0x7fffffff) return hipErrorInvalidValue;
-    const int hc = h_compact ? 1 : 0;
-    if (dt == BF16 && rdt == F32)
-        return launch_probs_t<bf16_t, float>(h, res, w, emb_f32, comp8, cols, probs_out, logits_out, B, L, D, eps, pos, pos_per_window, Pw, hc, ids, status, res_frag, s);
-    if (dt == BF16 && rdt == BF16)
-        return launch_probs_t<bf16_t, bf16_t>(h, res, w, emb_f32, comp8, cols, probs_out, logits_out, B, L, D, eps, pos, pos_per_window, Pw, hc, ids, status, res_frag, s);
-    if (dt == F32 && rdt == F32)
-        return launch_probs_t<float, float>(h, res, w, emb_f32, comp8, cols, probs_out, logits_out, B, L, D, eps, pos, pos_per_window, Pw, hc, ids, status, res_frag, s);
-    return hipErrorInvalidValue;
+        if ((unsigned)a.cols.c[j] > 7u) return hipErrorInvalidValue;
+    if (in.B <= 0 || (a.probs_out == nullptr && a.logits_out == nullptr)) return hipSuccess;
+    const int64_t blocks = ((int64_t)in.B * (a.pos_per_window ? a.Pw : (a.pos.n ? a.pos.n : in.L)) + PROBS_WAVES - 1) / PROBS_WAVES;
+    if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+    return select_row_form(in.dt, in.rdt, in.D, [&](auto form) {
+        using T = typename decltype(form)::X;
+        using RT = typename decltype(form)::R;
+        hipLaunchKernelGGL((probs_head_kernel<T, RT, decltype(form)::MAXC>), dim3((unsigned)blocks), dim3(64 * PROBS_WAVES), 0, s, (const T*)in.h, (const RT*)in.res,
+                           in.w, a.emb_f32, a.comp8, a.cols, a.probs_out, a.logits_out, in.B, in.L, in.D, in.eps, a.pos, a.pos_per_window, a.Pw,
+                           a.h_compact ? 1 : 0, in.ids, in.status, in.res_frag);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace pcad

@@ -38,7 +38,7 @@ def rand_weights(B, L, g):
 
 
 def run_loss_head(lib, h, res, w, emb, labels, weights, B, L, D, dt, frag, ignore_index=-100, want_logits=True, status=None,
-                  ids=None):
+                  ids=None, res_dt=engine.PCAD_F32):
     comp = torch.tensor(COMP, dtype=torch.int32, device=DEV)
     res_dev = (to_res_fragment(res) if frag else res).to(DEV).contiguous()
     hd, wd, ed = h.to(DEV), w.to(DEV), emb.to(DEV)
@@ -54,7 +54,7 @@ def run_loss_head(lib, h, res, w, emb, labels, weights, B, L, D, dt, frag, ignor
                             wt.data_ptr() if wt is not None else None, ignore_index, sums.data_ptr(), nll.data_ptr(),
                             lg.data_ptr() if lg is not None else None, B, L, D, C.c_float(1e-5),
                             ids.data_ptr() if ids is not None else None, status.data_ptr() if status is not None else None,
-                            dt, engine.PCAD_F32, int(frag), sp, nb, engine._stream_ptr())
+                            dt, res_dt, int(frag), sp, nb, engine._stream_ptr())
     assert rc == 0, lib.pcad_last_error()
     torch.cuda.synchronize()
     return sums.cpu(), nll.cpu(), (lg.cpu() if lg is not None else None)
@@ -125,6 +125,27 @@ def test_loss_head_operator(dtype):
         assert torch.equal(sums3[:, 1], sums3[:, 2]), case
         assert ((sums3[:, 0].double() - nll.double().sum(1)).abs() <= L * 2.0 ** -24 * nll.double().abs().sum(1)).all(), case
     print(f"loss head {dtype}: worst |nll - f64| {worst:.3e}")
+
+
+@pytest.mark.parametrize("D", [384, 1024, 1536])
+def test_loss_head_bf16_residual(D):
+    """The <bf16, bf16> pair (a bf16 model with residual_in_fp32 = False) at each width class: bf16 h and a bf16 residual against the
+    same call with that residual widened to fp32.  The head only reads the residual and adds it to h in fp32 (csrc/head_row.hpp), and
+    a bf16 value is exact in fp32, so sums, nll and logits are bit-equal; the outputs start as NaN, so an unwritten row shows."""
+    lib = engine.load_library()
+    g = torch.Generator().manual_seed(D)
+    B, L = 3, 24
+    h = torch.randn(2 * B * L, D, generator=g).to(torch.bfloat16)
+    res = (torch.randn(2 * B * L, D, generator=g) * 0.5 + 0.25).to(torch.bfloat16)
+    w = torch.rand(D, generator=g) + 0.5
+    emb = rnd(torch.randn(8, D, generator=g) * (3.0 / math.sqrt(D)), torch.bfloat16)
+    labels = rand_labels(B, L, 0.5, g)
+    weights = rand_weights(B, L, g)
+    got = run_loss_head(lib, h, res, w, emb, labels, weights, B, L, D, engine.PCAD_BF16, False, res_dt=engine.PCAD_BF16)
+    want = run_loss_head(lib, h, res.float(), w, emb, labels, weights, B, L, D, engine.PCAD_BF16, False)
+    for name, a, b in zip(("sums", "nll", "logits"), got, want):
+        assert not torch.isnan(b).any(), name
+        assert torch.equal(a, b), name
 
 
 def test_loss_head_label_semantics():

@@ -90,6 +90,40 @@ def test_pooled_head_operator(dtype, pooling):
                 assert torch.equal(pooled, pooled_ref), case
 
 
+@pytest.mark.parametrize("pooling", ["mean", "max"])
+@pytest.mark.parametrize("D", [384, 1024, 1536])
+def test_pooled_head_bf16_residual(D, pooling):
+    """The <bf16, bf16> pair (a bf16 model with residual_in_fp32 = False) at each width class: bf16 h and a bf16 residual against the
+    same call with that residual widened to fp32.  pool_stage1_kernel only reads the residual and forms v = h + res in fp32, and a
+    bf16 value is exact in fp32, so pooled and logits are bit-equal; the outputs start as NaN, so an unwritten row shows."""
+    lib = engine.load_library()
+    g = torch.Generator().manual_seed(D)
+    B, L, NL = 3, 45, 2
+    h = torch.randn(2 * B * L, D, generator=g).to(torch.bfloat16).to(DEV)
+    res = (torch.randn(2 * B * L, D, generator=g) * 0.5 + 1.0).to(torch.bfloat16).to(DEV)
+    w = (torch.rand(D, generator=g) + 0.5).to(DEV)
+    W = rnd(torch.randn(NL, D, generator=g) * 0.05, torch.bfloat16).to(DEV)
+    pid = engine.POOLING[pooling]
+    nb = lib.pcad_pooled_head_scratch_bytes(B, L, D, pid)
+    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=DEV)
+    sp = (scratch.data_ptr() + 255) // 256 * 256
+
+    def run(r, res_dt):
+        pooled = torch.full((B, 2, D), float("nan"), device=DEV)
+        lg = torch.full((B, NL), float("nan"), device=DEV)
+        rc = lib.pcad_pooled_head(h.data_ptr(), r.data_ptr(), w.data_ptr(), W.data_ptr(), NL, pooled.data_ptr(), lg.data_ptr(), B, L, D,
+                                  C.c_float(1e-5), pid, None, None, engine.PCAD_BF16, res_dt, 0, sp, nb, engine._stream_ptr())
+        assert rc == 0, lib.pcad_last_error()
+        torch.cuda.synchronize()
+        return pooled.cpu(), lg.cpu()
+
+    got = run(res, engine.PCAD_BF16)
+    want = run(res.float().contiguous(), engine.PCAD_F32)
+    for name, a, b in zip(("pooled", "logits"), got, want):
+        assert not torch.isnan(b).any(), name
+        assert torch.equal(a, b), name
+
+
 def test_pooled_head_reports_bad_tokens():
     lib = engine.load_library()
     B, L, D = 2, 45, 64
