@@ -74,4 +74,43 @@ int pcad_add_rmsnorm_bwd(const void* x, const void* residual_in, const float* we
     return PCAD_OK;
 }
 
+size_t pcad_loss_head_bwd_scratch_bytes(int B, int L, int D) {
+    if (B <= 0 || L <= 0 || D <= 0) return 0;
+    return loss_head_bwd_bytes(B, L, D);
+}
+
+int pcad_loss_head_bwd(const void* h, const void* res, const float* norm_weight, const float* emb_f32, const int32_t* complement,
+                       const int32_t* labels, const float* loss_weights, int ignore_index, const float* dsum, const float* dnll, void* dh,
+                       void* dres, float* dnorm_weight, float* demb, void* scratch, size_t scratch_bytes, int B, int L, int D, float eps,
+                       int dtype, int res_dtype, pcad_stream stream) {
+    const char* who = "pcad_loss_head_bwd";
+    const struct { const void* p; const char* name; } req[] = {{h, "h"}, {res, "res"}, {norm_weight, "norm_weight"}, {emb_f32, "emb_f32"},
+                                                               {complement, "complement"}, {labels, "labels"}, {dsum, "dsum"}};
+    for (const auto& r : req)
+        if (!r.p) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);
+    if (!dh && !dres && !dnorm_weight && !demb)
+        return fail(PCAD_ERR_INVALID, "%s: no output requested (dh, dres, dnorm_weight and demb are all NULL)", who);
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (res_dtype != PCAD_F32 && !(res_dtype == PCAD_BF16 && dtype == PCAD_BF16))
+        return fail(PCAD_ERR_INVALID, "%s: bad res_dtype %d for dtype %d (BF16 / F32, BF16 / BF16 or F32 / F32)", who, res_dtype, dtype);
+    if (B < 0 || L < 0) return fail(PCAD_ERR_INVALID, "%s: B, L must be >= 0 (B=%d, L=%d)", who, B, L);
+    if (D <= 0 || D % 8) return fail(PCAD_ERR_INVALID, "%s: D must be a positive multiple of 8 (D=%d)", who, D);
+    if (D > 2048) return fail(PCAD_ERR_INVALID, "%s: D must be <= 2048 (D=%d)", who, D);
+    const struct { const void* p; const char* name; } al[] = {{h, "h"}, {res, "res"}, {norm_weight, "norm_weight"}, {emb_f32, "emb_f32"},
+                                                              {dh, "dh"}, {dres, "dres"}};
+    for (const auto& r : al)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    if (B == 0 || L == 0) return PCAD_OK;
+    if (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < loss_head_bwd_bytes(B, L, D))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_loss_head_bwd_scratch_bytes large", who);
+    hipError_t err = launch_loss_head_bwd({.in = {.h = h, .res = res, .w = norm_weight, .B = B, .L = L, .D = D, .eps = eps, .dt = dtype, .rdt = res_dtype},
+                                           .emb_f32 = emb_f32, .comp8 = complement, .labels = labels, .loss_w = loss_weights,
+                                           .ignore_index = ignore_index, .dsum = dsum, .dnll = dnll, .dh = dh, .dres = dres,
+                                           .dnorm_w = dnorm_weight, .demb = demb, .scratch = scratch},
+                                          (hipStream_t)stream);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "%s: B * ceil(L / 64) must fit a 32-bit grid", who);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 }  // extern "C"

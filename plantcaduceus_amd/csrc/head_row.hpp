@@ -1,4 +1,5 @@
-// One strand's row of the LM head, shared by final_head_kernel (norm.hip), loss_stage1_kernel (loss.hip) and probs_head_kernel (probs.hip): ONE
+// One strand's row of the LM head, shared by final_head_kernel (norm.hip), loss_stage1_kernel (loss.hip), probs_head_kernel (probs.hip) and
+// loss_head_bwd_kernel (loss_bwd.hip, which recomputes the forward's logits through it): ONE
 // head arithmetic:  v = h + res (fp32);  o = round(v * rstd(v) * w);  acc[k] = round(o . Emb[strand 0: k, strand 1: comp[k]]).
 // One wave per row, 8 columns per lane and step (16-byte accesses); `row` indexes the full [2B * L, D] residual tensor, h_row
 // points at the mixer output's row.  res_frag != 0: fp32 residual in the GEMM's fragment layout of that (padded) width.
@@ -28,11 +29,30 @@ static hipError_t select_row_form(int dt, int rdt, int D, F&& f) {
 
 // hidden_dst (or nullptr): the [2D] row of hidden_states[-1] this strand's half is written to (rc strand: reversed channels).
 // want_logits: acc[0..7] = the strand's 8 partial logits, rounded to the model dtype, the same value in every lane.
-template <typename T, typename RT, int MAXC>
+// `keep` is handed what a backward needs of the row: v = h + res of the lane's chunks and the row's rstd.  The inference callers pass
+// none and both are dropped (HeadRowDrop); loss_bwd.hip passes a HeadRowKept, which stores them.
+struct HeadRowDrop {
+    template <int MAXC> __device__ __forceinline__ void take(const float (&)[MAXC][8], float, int, int) {}
+};
+template <int MAXC>
+struct HeadRowKept {
+    float v[MAXC][8];                 // chunks beyond the row are not written
+    float rstd;
+    __device__ __forceinline__ void take(const float (&src)[MAXC][8], float r, int lane, int nchunk) {
+        rstd = r;
+#pragma unroll
+        for (int j = 0; j < MAXC; ++j)
+            if (lane + 64 * j < nchunk) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[j][i] = src[j][i];
+            }
+    }
+};
+template <typename T, typename RT, int MAXC, typename Keep = HeadRowDrop>
 __device__ __forceinline__ void head_row(const T* __restrict__ h_row, const RT* __restrict__ res, int64_t row,
                                          const float* __restrict__ w, const float* __restrict__ emb,
                                          const int32_t* __restrict__ comp8, int D, float eps, int res_frag, int strand, int lane,
-                                         T* __restrict__ hidden_dst, bool want_logits, float (&acc)[8]) {
+                                         T* __restrict__ hidden_dst, bool want_logits, float (&acc)[8], Keep&& keep = Keep{}) {
     // every product below is rounded before it is added (no fused multiply-add), whatever kernel this is inlined into: the two
     // callers must give the same logits bit for bit, and contraction is otherwise decided per call site
 #pragma clang fp contract(off)
@@ -58,6 +78,7 @@ __device__ __forceinline__ void head_row(const T* __restrict__ h_row, const RT* 
     }
     ss = wave_sum(ss);
     const float rstd = rsqrtf(ss / (float)D + eps);
+    keep.take(v, rstd, lane, nchunk);
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = 0.f;
 #pragma unroll

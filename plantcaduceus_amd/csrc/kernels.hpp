@@ -97,6 +97,7 @@ hipError_t launch_pooled_head(const PooledHeadLaunch& a, hipStream_t s);
 // loss.hip: masked-LM loss head (pcad.h pcad_loss_head): launch_final_head's logits at every position + the cross entropy of the
 // labelled ones, reduced per window.  Stage 1 writes loss_partial_bytes(B, L) bytes of fp32 partials to `part` (16-byte aligned);
 // the segmentation depends on L only.
+constexpr int LOSS_SEG = 64;          // positions per stage-1 segment (and per block of loss_bwd.hip)
 int loss_segments(int L);
 size_t loss_partial_bytes(int B, int L);
 struct LossHeadLaunch {
@@ -407,6 +408,28 @@ struct NormBwdLaunch {
 };
 size_t norm_bwd_bytes(int64_t rows, int D);
 hipError_t launch_norm_bwd(const NormBwdLaunch& a, hipStream_t s);
+
+// loss_bwd.hip (libpcad_bwd.so): backward of launch_loss_head on plain rows (pcad_bwd.h pcad_loss_head_bwd).  `in` as
+// the forward takes it (res_frag, ids and status unused).  dh [2B * L, D] dtype dt and dres [2B * L, D] dtype rdt: every row is
+// written, zeros where the position carries no label; demb fp32 [8, D], dnorm_w fp32 [D]; each output may be null, not all of them.
+// scratch (needed for demb / dnorm_w): loss_head_bwd_bytes(B, L, D) bytes, 256-byte aligned - one row of 9 D partials
+// (demb | dnorm_w) per (window, segment of LOSS_SEG positions), which launch_sum_partials adds, and one spare row.
+struct LossHeadBwdLaunch {
+    HeadInput in;
+    const float* emb_f32;  const int32_t* comp8;
+    const int32_t* labels;            // [B, L], read as launch_loss_head reads them
+    const float* loss_w = nullptr;    // [B, L], or nullptr (all 1)
+    int ignore_index;
+    const float* dsum;                // [B]: the gradient of sums_out[b, 0]
+    const float* dnll = nullptr;      // [B, L]: the gradient of nll_out, or nullptr (zero)
+    void* dh = nullptr;
+    void* dres = nullptr;
+    float* dnorm_w = nullptr;
+    float* demb = nullptr;
+    void* scratch = nullptr;
+};
+size_t loss_head_bwd_bytes(int B, int L, int D);
+hipError_t launch_loss_head_bwd(const LossHeadBwdLaunch& a, hipStream_t s);
 
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor -> out[(strand * P + q), E]

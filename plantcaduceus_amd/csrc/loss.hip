@@ -18,7 +18,6 @@
 
 namespace pcad {
 
-constexpr int LOSS_SEG = 64;      // positions per stage-1 segment
 constexpr int LOSS_STATUS_BAD_TOKEN_BIT = 1, LOSS_STATUS_BAD_LABEL_BIT = 4;     // = pcad.h PCAD_STATUS_BAD_TOKEN / PCAD_STATUS_BAD_LABEL
 
 int loss_segments(int L) { return (L + LOSS_SEG - 1) / LOSS_SEG; }

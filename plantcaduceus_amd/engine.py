@@ -131,13 +131,16 @@ TRAIN_SIGNATURES = {
 }
 TRAIN_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_train.so")
 
-# name -> (restype, argtypes): every symbol include/pcad_bwd.h declares (libpcad_bwd.so: the conv and RMSNorm backward operators; the
+# name -> (restype, argtypes): every symbol include/pcad_bwd.h declares (libpcad_bwd.so: the conv, RMSNorm and loss head backward operators; the
 # table, the header and the library's exports are held to each other, not to a closed list - later backward operators go here)
 BWD_SIGNATURES = {
     "pcad_causal_conv1d_silu_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "pcad_causal_conv1d_silu_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
     "pcad_add_rmsnorm_bwd_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "pcad_add_rmsnorm_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_size_t, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p]),
+    "pcad_loss_head_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pcad_loss_head_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 7 + [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                     C.c_int, C.c_void_p]),
 }
 BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
 
