@@ -7,7 +7,7 @@
  * library; what is held is that this header, that table and the library's exports name the same pcad_* symbols.
  * libpcad_bwd.so links libpcad.so (same directory) and shares its conventions: status codes (pcad_status), dtypes (pcad_dtype),
  * pcad_stream, and the calling thread's pcad_last_error() text.  Built by the same Makefile from csrc/bwd_api.hip, csrc/conv_bwd.hip,
- * csrc/norm_bwd.hip and csrc/loss_bwd.hip.
+ * csrc/norm_bwd.hip, csrc/loss_bwd.hip and csrc/optim.hip (the optimizer step that uses the gradients: the last section below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
@@ -83,6 +83,69 @@ int pcad_loss_head_bwd(const void* h, const void* res, const float* norm_weight,
                        const int32_t* labels, const float* loss_weights, int ignore_index, const float* dsum, const float* dnll,
                        void* dh, void* dres, float* dnorm_weight, float* demb, void* scratch, size_t scratch_bytes,
                        int B, int L, int D, float eps, int dtype, int res_dtype, pcad_stream stream);
+
+/* ---- The optimizer step: AdamW with global-norm gradient clipping over a whole parameter set ----------------
+ * Replaces: torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step + zero_grad, in three (one) launches however many tensors there are.
+ *
+ * The caller describes the set once: a table of pcad_optim_tensor records, and beside it a chunk map.  The work is cut into chunks of
+ * PCAD_OPTIM_CHUNK elements that never straddle two tensors: tensor i has ceil(n_i / PCAD_OPTIM_CHUNK) chunks, in table order.  The
+ * chunking is a function of the table alone - not of the grid, not of the device - and one block works on one chunk, which is what
+ * makes the step bit-reproducible.  pcad_optim_plan checks a table in HOST memory and fills the map; the caller uploads both, and the
+ * step entries read only the device copies (which they cannot check: a device table that pcad_optim_plan has not accepted, or a map
+ * that is not its own, is undefined behaviour). */
+#define PCAD_OPTIM_CHUNK 4096          /* elements per chunk */
+#define PCAD_OPTIM_DECAY 1             /* flags bit 0: weight decay applies to this tensor */
+#define PCAD_OPTIM_MAX_CHUNKS 16777215  /* 2^24 - 1: one 256-lane block per chunk, the grid below 2^32 lanes (6.8e10 elements) */
+
+typedef struct pcad_optim_tensor {     /* 64 bytes; every pointer is device memory, 16-byte aligned */
+    void* param;                       /* [n] param_dtype (PCAD_BF16 / PCAD_F32) */
+    void* grad;                        /* [n] grad_dtype (PCAD_BF16 / PCAD_F32) */
+    float* master;                     /* [n] fp32, or NULL: an fp32 param is its own master (a bf16 param needs one) */
+    float* exp_avg;                    /* [n] fp32 */
+    float* exp_avg_sq;                 /* [n] fp32 */
+    int64_t n;                         /* >= 0; 0: the record has no chunk and its pointers are not read */
+    int32_t param_dtype, grad_dtype;
+    int32_t flags;                     /* PCAD_OPTIM_DECAY or 0 */
+    int32_t reserved;                  /* 0 */
+} pcad_optim_tensor;
+
+typedef struct pcad_optim_state {      /* 16 bytes of device memory, 16-byte aligned, the caller's; zeroed once, then only the step writes it */
+    float norm;                        /* the last step's total norm of grad_scale * grad */
+    float coef;                        /* the factor the last step applied to every gradient */
+    int32_t finite;                    /* 1: norm was finite and the step was applied; 0: it was skipped */
+    int32_t skipped;                   /* steps skipped so far */
+} pcad_optim_state;
+
+/* Checks `table` (HOST memory, count records) and counts its chunks into *chunks_out.  chunk_map (HOST, may be NULL: count only) gets
+ * two int32 per chunk, (record index, chunk index within the record), chunk_capacity chunks of room (less than needed: PCAD_ERR_INVALID).
+ * PCAD_ERR_INVALID, naming the record and the field: n < 0; a dtype other than PCAD_BF16 / PCAD_F32; unknown flag bits; for n > 0 a
+ * NULL param, grad, exp_avg or exp_avg_sq, a bf16 param without master, any of the five pointers not 16-byte aligned; more than
+ * PCAD_OPTIM_MAX_CHUNKS chunks in all.  Pointers are compared, never dereferenced. */
+int pcad_optim_plan(const pcad_optim_tensor* table, int64_t count, int32_t* chunk_map, int64_t chunk_capacity, int64_t* chunks_out);
+
+/* One step.  table / chunk_map: the DEVICE copies of what pcad_optim_plan accepted / filled; chunks: its count.  Three launches:
+ *   1. part[c] = sum over chunk c of (grad_scale g)^2     a lane adds its elements in index order, the 64 lanes of a wave by the xor
+ *                                                          butterfly, the 4 waves of the block in index order
+ *   2. one block adds part[] (lane t of 1024: t, t + 1024, ... in index order, then the same tree) and writes `state`:
+ *        norm = sqrt(sum)     finite = norm is neither inf nor NaN     skipped += !finite
+ *        coef = grad_scale * min(1, max_norm / (norm + 1e-6))          (torch.nn.utils.clip_grad_norm_; max_norm <= 0: coef = grad_scale)
+ *   3. per element, everything in fp32, only when finite (else nothing at all is stored):
+ *        g = coef grad     p = master (param without one)     p = p (1 - lr wd) when PCAD_OPTIM_DECAY
+ *        m = b1 m + (1 - b1) g     v = b2 v + (1 - b2) g^2     p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ *        store master (param without one), m, v; a bf16 param = round-to-nearest-even(master), an fp32 param beside a master = master
+ * The host passes lr, bc1 = 1 - b1^t and bc2 = 1 - b2^t (t = the 1-based step) in double; 1 - lr wd, lr / bc1, sqrt(bc2), 1 - b1 and
+ * 1 - b2 are formed in double and rounded to fp32 once.  The host never sees the norm unless it reads `state`.
+ * A tensor's last n % 4 (both fp32) / n % 8 (a bf16 side) elements are walked one by one: nothing past n is read or written.
+ *   scratch    pcad_adamw_step_scratch_bytes(chunks) bytes: part[]
+ * PCAD_ERR_INVALID: count or chunks < 0, chunks > PCAD_OPTIM_MAX_CHUNKS, NULL or misaligned table / chunk_map (chunks > 0) / state, bc1 or bc2 not
+ * in (0, 1], a non-finite scalar.  chunks == 0: phase 2 alone runs (norm 0). */
+size_t pcad_adamw_step_scratch_bytes(int64_t chunks);
+int pcad_adamw_step(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, void* state, void* scratch, size_t scratch_bytes,
+                    double lr, double beta1, double beta2, double eps, double weight_decay, double bc1, double bc2, double max_norm,
+                    double grad_scale, pcad_stream stream);
+
+/* Sets every gradient of the table to zero (all n elements, nothing beyond them) in one launch. */
+int pcad_zero_grads(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, pcad_stream stream);
 
 #ifdef __cplusplus
 }

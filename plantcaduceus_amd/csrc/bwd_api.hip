@@ -2,6 +2,8 @@
 // through its pcad::fail, so pcad_last_error() of the calling thread carries the message.
 #include "../../include/pcad_bwd.h"
 #include "pcad_internal.hpp"
+#include <math.h>
+#include <string.h>
 using namespace pcad;
 
 extern "C" {
@@ -109,6 +111,94 @@ int pcad_loss_head_bwd(const void* h, const void* res, const float* norm_weight,
                                            .dnorm_w = dnorm_weight, .demb = demb, .scratch = scratch},
                                           (hipStream_t)stream);
     if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "%s: B * ceil(L / 64) must fit a 32-bit grid", who);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_optim_plan(const pcad_optim_tensor* table, int64_t count, int32_t* chunk_map, int64_t chunk_capacity, int64_t* chunks_out) {
+    const char* who = "pcad_optim_plan";
+    if (count < 0) return fail(PCAD_ERR_INVALID, "%s: count must be >= 0", who);
+    if (!table && count > 0) return fail(PCAD_ERR_INVALID, "%s: null table", who);
+    if (!chunks_out) return fail(PCAD_ERR_INVALID, "%s: null chunks_out", who);
+    if (chunk_map && chunk_capacity < 0) return fail(PCAD_ERR_INVALID, "%s: chunk_capacity must be >= 0", who);
+    int64_t chunks = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const pcad_optim_tensor& t = table[i];
+        if (t.n < 0) return fail(PCAD_ERR_INVALID, "%s: table[%lld].n must be >= 0 (n=%lld)", who, (long long)i, (long long)t.n);
+        if (t.param_dtype != PCAD_F32 && t.param_dtype != PCAD_BF16)
+            return fail(PCAD_ERR_INVALID, "%s: table[%lld].param_dtype: bad dtype %d", who, (long long)i, t.param_dtype);
+        if (t.grad_dtype != PCAD_F32 && t.grad_dtype != PCAD_BF16)
+            return fail(PCAD_ERR_INVALID, "%s: table[%lld].grad_dtype: bad dtype %d", who, (long long)i, t.grad_dtype);
+        if (t.flags & ~PCAD_OPTIM_DECAY) return fail(PCAD_ERR_INVALID, "%s: table[%lld].flags: unknown bits 0x%x", who, (long long)i, t.flags);
+        if (t.n == 0) continue;
+        const struct { const void* p; const char* name; bool required; } ptr[] = {
+            {t.param, "param", true}, {t.grad, "grad", true}, {t.master, "master", t.param_dtype == PCAD_BF16},
+            {t.exp_avg, "exp_avg", true}, {t.exp_avg_sq, "exp_avg_sq", true}};
+        for (const auto& r : ptr) {
+            if (!r.p && r.required)
+                return fail(PCAD_ERR_INVALID, "%s: table[%lld].%s is null%s", who, (long long)i, r.name,
+                            strcmp(r.name, "master") == 0 ? " (a bf16 param needs an fp32 master)" : "");
+            if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: table[%lld].%s must be 16-byte aligned", who, (long long)i, r.name);
+        }
+        const int64_t nc = (t.n - 1) / PCAD_OPTIM_CHUNK + 1;
+        if (nc > PCAD_OPTIM_MAX_CHUNKS - chunks) return fail(PCAD_ERR_INVALID, "%s: the table has more than 2^24 - 1 chunks (at table[%lld])", who, (long long)i);
+        if (chunk_map) {
+            if (chunks + nc > chunk_capacity)
+                return fail(PCAD_ERR_INVALID, "%s: chunk_capacity %lld is too small (at table[%lld])", who, (long long)chunk_capacity, (long long)i);
+            for (int64_t c = 0; c < nc; ++c) {
+                chunk_map[2 * (chunks + c)] = (int32_t)i;
+                chunk_map[2 * (chunks + c) + 1] = (int32_t)c;
+            }
+        }
+        chunks += nc;
+    }
+    *chunks_out = chunks;
+    return PCAD_OK;
+}
+
+size_t pcad_adamw_step_scratch_bytes(int64_t chunks) { return optim_scratch_bytes(chunks); }
+
+static int optim_table_check(const char* who, const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks) {
+    if (count < 0 || chunks < 0) return fail(PCAD_ERR_INVALID, "%s: count, chunks must be >= 0 (count=%lld, chunks=%lld)", who, (long long)count, (long long)chunks);
+    if (chunks > PCAD_OPTIM_MAX_CHUNKS) return fail(PCAD_ERR_INVALID, "%s: chunks must be <= 2^24 - 1, a grid of 256-lane blocks below 2^32 lanes (chunks=%lld)", who, (long long)chunks);
+    if (count > 0x7fffffff) return fail(PCAD_ERR_INVALID, "%s: count must fit the chunk map's 32-bit index (count=%lld)", who, (long long)count);
+    if (chunks > 0) {
+        if (!table || count == 0) return fail(PCAD_ERR_INVALID, "%s: null table", who);
+        if (!chunk_map) return fail(PCAD_ERR_INVALID, "%s: null chunk_map", who);
+        if (((uintptr_t)table) % 16) return fail(PCAD_ERR_INVALID, "%s: table must be 16-byte aligned", who);
+        if (((uintptr_t)chunk_map) % 8) return fail(PCAD_ERR_INVALID, "%s: chunk_map must be 8-byte aligned", who);
+    }
+    return PCAD_OK;
+}
+
+int pcad_adamw_step(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, void* state, void* scratch, size_t scratch_bytes,
+                    double lr, double beta1, double beta2, double eps, double weight_decay, double bc1, double bc2, double max_norm,
+                    double grad_scale, pcad_stream stream) {
+    const char* who = "pcad_adamw_step";
+    if (int rc = optim_table_check(who, table, chunk_map, count, chunks)) return rc;
+    if (!state) return fail(PCAD_ERR_INVALID, "%s: null state", who);
+    if (((uintptr_t)state) % 16) return fail(PCAD_ERR_INVALID, "%s: state must be 16-byte aligned", who);
+    const struct { double v; const char* name; } sc[] = {{lr, "lr"}, {beta1, "beta1"}, {beta2, "beta2"}, {eps, "eps"}, {weight_decay, "weight_decay"},
+                                                         {bc1, "bc1"}, {bc2, "bc2"}, {max_norm, "max_norm"}, {grad_scale, "grad_scale"}};
+    for (const auto& r : sc)
+        if (!(r.v - r.v == 0.0)) return fail(PCAD_ERR_INVALID, "%s: %s must be finite", who, r.name);
+    if (!(bc1 > 0.0 && bc1 <= 1.0)) return fail(PCAD_ERR_INVALID, "%s: bc1 = 1 - beta1^t must be in (0, 1] (bc1=%g)", who, bc1);
+    if (!(bc2 > 0.0 && bc2 <= 1.0)) return fail(PCAD_ERR_INVALID, "%s: bc2 = 1 - beta2^t must be in (0, 1] (bc2=%g)", who, bc2);
+    if (chunks > 0 && (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < optim_scratch_bytes(chunks)))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_adamw_step_scratch_bytes large", who);
+    hipError_t err = launch_adamw_step({.table = table, .map = chunk_map, .chunks = chunks, .state = state, .part = (float*)scratch,
+                                        .max_norm = (float)max_norm, .grad_scale = (float)grad_scale, .decay = (float)(1.0 - lr * weight_decay),
+                                        .b1 = (float)beta1, .omb1 = (float)(1.0 - beta1), .b2 = (float)beta2, .omb2 = (float)(1.0 - beta2),
+                                        .step_size = (float)(lr / bc1), .bc2_sqrt = (float)sqrt(bc2), .eps = (float)eps},
+                                       (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_zero_grads(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, pcad_stream stream) {
+    const char* who = "pcad_zero_grads";
+    if (int rc = optim_table_check(who, table, chunk_map, count, chunks)) return rc;
+    hipError_t err = launch_zero_grads(table, chunk_map, chunks, (hipStream_t)stream);
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
     return PCAD_OK;
 }

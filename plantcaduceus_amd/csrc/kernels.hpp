@@ -431,6 +431,21 @@ struct LossHeadBwdLaunch {
 size_t loss_head_bwd_bytes(int B, int L, int D);
 hipError_t launch_loss_head_bwd(const LossHeadBwdLaunch& a, hipStream_t s);
 
+// optim.hip (libpcad_bwd.so): one AdamW step with global-norm clipping over a table of tensors (pcad_bwd.h pcad_adamw_step) and
+// the zeroing of its gradients (pcad_zero_grads).  table: device array of pcad_optim_tensor; map: device int32 [chunks, 2] = (tensor,
+// chunk within the tensor), as pcad_optim_plan fills it; one block per chunk of OPTIM_CHUNK elements, chunks never straddle two tensors.
+constexpr int OPTIM_CHUNK = 4096;     // elements per chunk = per block of 256 lanes (pcad_bwd.h PCAD_OPTIM_CHUNK)
+struct AdamwLaunch {
+    const void* table;  const int32_t* map;  int64_t chunks;
+    void* state;                      // pcad_optim_state
+    float* part;                      // optim_scratch_bytes(chunks): one sum of squares per chunk
+    float max_norm, grad_scale;
+    float decay, b1, omb1, b2, omb2, step_size, bc2_sqrt, eps;     // 1 - lr wd, beta1, 1 - beta1, beta2, 1 - beta2, lr / bc1, sqrt(bc2), eps
+};
+size_t optim_scratch_bytes(int64_t chunks);
+hipError_t launch_adamw_step(const AdamwLaunch& a, hipStream_t s);
+hipError_t launch_zero_grads(const void* table, const int32_t* map, int64_t chunks, hipStream_t s);
+
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor -> out[(strand * P + q), E]
 struct GatherRowsLaunch {

@@ -1135,3 +1135,156 @@ def mlm_loss_head_fn(h, res, norm_weight, emb, complement, labels, loss_weights=
         return (sums, nll) if return_nll else sums
     sums, nll, _ = loss_head(h, res, norm_weight, emb, complement, labels, loss_weights, ignore_index, eps, B=B, L=L, want_nll=return_nll)
     return (sums, nll) if return_nll else sums
+
+
+# ---- the optimizer step (include/pcad_bwd.h pcad_optim_plan / pcad_adamw_step / pcad_zero_grads) ---------------------
+OPTIM_CHUNK = 4096       # include/pcad_bwd.h PCAD_OPTIM_CHUNK = csrc/kernels.hpp OPTIM_CHUNK: elements per chunk = per block
+OPTIM_DECAY = 1          # include/pcad_bwd.h PCAD_OPTIM_DECAY: flags bit 0
+
+
+def _optim_record_type():
+    import ctypes as C
+
+    class Record(C.Structure):            # include/pcad_bwd.h pcad_optim_tensor
+        _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("master", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                    ("n", C.c_int64), ("param_dtype", C.c_int32), ("grad_dtype", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+    assert C.sizeof(Record) == 64
+    return Record
+
+
+def optim_plan(records):
+    """pcad_optim_plan on host records (param, grad, master, exp_avg, exp_avg_sq, n, param_dtype, grad_dtype, flags): pointers as
+    integers or None, nothing is dereferenced.  -> (the table as bytes, the chunk map as a list of (record, chunk) pairs)"""
+    import ctypes as C
+    lib = load_bwd_library()
+    Record = _optim_record_type()
+    tab = (Record * max(1, len(records)))()
+    for r, rec in zip(tab, records):
+        r.param, r.grad, r.master, r.exp_avg, r.exp_avg_sq, r.n, r.param_dtype, r.grad_dtype, r.flags = rec
+    chunks = C.c_int64(0)
+    _check(lib.pcad_optim_plan(C.addressof(tab), len(records), None, 0, C.byref(chunks)), "pcad_optim_plan")
+    cmap = (C.c_int32 * max(2, 2 * chunks.value))()
+    _check(lib.pcad_optim_plan(C.addressof(tab), len(records), C.addressof(cmap), chunks.value, C.byref(chunks)), "pcad_optim_plan")
+    return bytes(tab)[:64 * len(records)], [(cmap[2 * c], cmap[2 * c + 1]) for c in range(chunks.value)]
+
+
+class OptimTable:
+    """The parameter set of pcad_adamw_step / pcad_zero_grads in device memory: one record per tensor and the chunk map beside it.
+    params[i] / grads[i]: contiguous bf16 or fp32 tensors of equal size; masters[i]: fp32 or None (an fp32 parameter is its own
+    master); exp_avgs[i], exp_avg_sqs[i]: fp32; decay[i]: whether weight decay applies.  Every data pointer must be 16-byte aligned
+    (the plan refuses the table otherwise).  The upload goes on the current stream from pinned memory, without synchronising.
+    state (fp32-sized [4] int32 tensor, include/pcad_bwd.h pcad_optim_state) is the caller's when given, so that it outlives the table."""
+
+    def __init__(self, params, grads, masters, exp_avgs, exp_avg_sqs, decay, state=None):
+        import numpy as np
+        lists = (params, grads, masters, exp_avgs, exp_avg_sqs, decay)
+        if len({len(x) for x in lists}) != 1:
+            raise ValueError("params, grads, masters, exp_avgs, exp_avg_sqs and decay must have one entry per tensor")
+        self.params, self.grads, self.masters = list(params), list(grads), list(masters)
+        self.exp_avgs, self.exp_avg_sqs, self.decay = list(exp_avgs), list(exp_avg_sqs), [bool(d) for d in decay]
+        if not self.params:
+            raise ValueError("an empty parameter set")
+        dev = self.params[0].device
+        records = []
+        for i, (p, g, ms, m, v, d) in enumerate(zip(*lists)):
+            for t, name, want in ((p, "param", None), (g, "grad", None), (ms, "master", torch.float32), (m, "exp_avg", torch.float32),
+                                  (v, "exp_avg_sq", torch.float32)):
+                if t is None and name == "master":
+                    continue
+                _require_gpu(t, f"{name}[{i}]")
+                if t.device != dev or not t.is_contiguous() or t.numel() != p.numel() or (want is not None and t.dtype != want):
+                    raise ValueError(f"{name}[{i}] must be a contiguous {want or 'bf16 / fp32'} tensor of param[{i}]'s size on {dev}")
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+            records.append((ptr(p), ptr(g), ptr(ms), ptr(m), ptr(v), p.numel(), _dt(p), _dt(g), OPTIM_DECAY if d else 0))
+        self.pointers = tuple(r[:5] for r in records)
+        tab, cmap = optim_plan(records)
+        self.count, self.chunks = len(records), len(cmap)
+        host = torch.from_numpy(np.frombuffer(tab, dtype=np.uint8).copy()).pin_memory()
+        hmap = torch.tensor(cmap if cmap else [(0, 0)], dtype=torch.int32).pin_memory()
+        with torch.cuda.device(dev):
+            self._host = (host, hmap)                                 # alive until the copies have run
+            self.table = host.to(dev, non_blocking=True)
+            self.chunk_map = hmap.to(dev, non_blocking=True)
+            self.state = state if state is not None else torch.zeros(4, dtype=torch.int32, device=dev)
+            self.scratch_bytes = load_bwd_library().pcad_adamw_step_scratch_bytes(self.chunks)
+            self.scratch = torch.empty(self.scratch_bytes + 256, dtype=torch.uint8, device=dev)
+        self.device = dev
+
+    def read_state(self):
+        """-> dict(norm, coef, finite, skipped) of the last step.  Synchronises."""
+        raw = self.state.cpu()
+        f = raw.view(torch.float32)
+        return {"norm": float(f[0]), "coef": float(f[1]), "finite": int(raw[2]), "skipped": int(raw[3])}
+
+
+OPTIM_GUARD = 64         # sentinel elements before and after every output of the poison forms (a multiple of 16 bytes in either dtype)
+
+
+def _guarded_copy(t: torch.Tensor):
+    n = t.numel()
+    whole = torch.full((n + 2 * OPTIM_GUARD,), GUARD, dtype=t.dtype, device=t.device)
+    whole[OPTIM_GUARD:OPTIM_GUARD + n] = t.reshape(-1)
+    return whole[OPTIM_GUARD:OPTIM_GUARD + n].view(t.shape), whole
+
+
+def _guarded_copies_intact(pairs) -> bool:
+    return all(bool((w[:OPTIM_GUARD] == GUARD).all()) and bool((w[OPTIM_GUARD + t.numel():] == GUARD).all()) for t, w in pairs)
+
+
+def adamw_step(table: OptimTable, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, max_norm=0.0, grad_scale=1.0,
+               poison=False):
+    """pcad_adamw_step: one AdamW step with global-norm clipping over the table's tensors, in place (torch.optim.AdamW's arithmetic in
+    fp32 after clip_grad_norm_(max_norm) of grad_scale * grad; max_norm <= 0: no clipping; `step` is the 1-based step number of the
+    bias corrections).  Non-finite gradients: nothing changes and the state's `skipped` goes up.  No host synchronisation.
+    poison (tests): the step runs on copies of every output - param, master, exp_avg, exp_avg_sq - that sit between OPTIM_GUARD sentinel
+    elements, with a scratch of 0xFF bytes, and the results are copied back; -> whether all sentinels are intact (else None)."""
+    lib = load_bwd_library()
+    bc1, bc2 = 1.0 - float(beta1) ** int(step), 1.0 - float(beta2) ** int(step)
+    run, pairs, back = table, [], []
+    if poison:
+        cols = []
+        for src in (table.params, table.masters, table.exp_avgs, table.exp_avg_sqs):
+            col = []
+            for t in src:
+                if t is None:
+                    col.append(None)
+                    continue
+                c, whole = _guarded_copy(t)
+                pairs.append((c, whole))
+                back.append((t, c))
+                col.append(c)
+            cols.append(col)
+        run = OptimTable(cols[0], table.grads, cols[1], cols[2], cols[3], table.decay, state=table.state)
+        run.scratch = _nan_bytes(run.scratch_bytes, table.device)
+    with torch.cuda.device(table.device):
+        _check(lib.pcad_adamw_step(run.table.data_ptr(), run.chunk_map.data_ptr(), run.count, run.chunks, run.state.data_ptr(),
+                                   _aligned(run.scratch), run.scratch_bytes, float(lr), float(beta1), float(beta2), float(eps),
+                                   float(weight_decay), bc1, bc2, float(max_norm), float(grad_scale), _stream_ptr()), "pcad_adamw_step")
+    if not poison:
+        return None
+    with torch.no_grad():
+        for t, c in back:
+            t.copy_(c)
+    return _guarded_copies_intact(pairs)
+
+
+def zero_grads(table: OptimTable, poison=False):
+    """pcad_zero_grads: every gradient of the table set to zero in one launch, storage kept.  poison (tests): as adamw_step, on guarded
+    NaN-filled copies of the gradients."""
+    lib = load_bwd_library()
+    run, pairs = table, []
+    if poison:
+        grads = []
+        for g in table.grads:
+            c, whole = _guarded_copy(torch.full_like(g, float("nan")))
+            pairs.append((c, whole))
+            grads.append(c)
+        run = OptimTable(table.params, grads, table.masters, table.exp_avgs, table.exp_avg_sqs, table.decay, state=table.state)
+    with torch.cuda.device(table.device):
+        _check(lib.pcad_zero_grads(run.table.data_ptr(), run.chunk_map.data_ptr(), run.count, run.chunks, _stream_ptr()), "pcad_zero_grads")
+    if not poison:
+        return None
+    with torch.no_grad():
+        for g, (c, _) in zip(table.grads, pairs):
+            g.copy_(c)
+    return _guarded_copies_intact(pairs)

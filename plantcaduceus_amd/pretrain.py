@@ -1,0 +1,366 @@
+"""Masked-LM pretraining: the `--do_train` half of the reference's `src/HF_pre_train.py` (:446-501: `Trainer.train()`, `save_model`,
+`save_metrics("train")`, `save_state`) on this project's kernels - forward and backward of `training.TrainableCaduceusForMaskedLM`,
+the fused AdamW step of `optim.AdamW`.  Single process, one GPU.
+
+    python -m plantcaduceus_amd.pretrain --model_name_or_path <snapshot> | --config_name <config.json> \\
+        --dataset_name <dir or table> --do_train [--do_eval] --output_dir out \\
+        --per_device_train_batch_size 8 --gradient_accumulation_steps 1 --learning_rate 5e-5 --weight_decay 0.0 \\
+        --adam_beta1 0.9 --adam_beta2 0.999 --adam_epsilon 1e-8 --max_grad_norm 1.0 \\
+        --num_train_epochs 3 | --max_steps N  --lr_scheduler_type linear|cosine|constant|constant_with_warmup \\
+        --warmup_steps K | --warmup_ratio R  --mlm_probability 0.15 --soft_masked_loss_weights_train 1.0 \\
+        --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16
+
+Flag names and defaults are `transformers.TrainingArguments`' and `HF_pre_train.py`'s.  `--config_name` alone starts from scratch:
+`checkpoint.synthetic_state_dict(config, seed=--seed, stress=False)`, the Mamba-style initialisation.
+
+Data is `mlm_eval`'s: `load_sequences(..., "train")`, `tokenize_windows` (equal-length windows only), and HF's own
+`DataCollatorForLanguageModeling.torch_mask_tokens` on a CPU generator of its own, seeded with `--seed`: masks are drawn afresh for
+every micro-batch.  The window order of epoch e is `torch.randperm(N)` from a generator seeded by (`--seed`, e).  An optimizer step is
+`--gradient_accumulation_steps` micro-batches of `--per_device_train_batch_size` windows, each `forward(...).loss.backward()`, then
+`optimizer.step(lr=schedule(t))` with `grad_scale = 1 / micro-batches` and `zero_grad()`.  An epoch has
+max(1, ceil(N / batch) // accumulation) steps, as `Trainer` counts them; micro-batches beyond the last whole step of an epoch are not
+used.  The learning rate of the t-th step (t = 0, 1, ...) is `learning_rate * lambda(t)` with `transformers.get_scheduler`'s lambdas
+(so the first step of a warm-up runs at 0, as under `Trainer`).  The loop reads nothing back from the device except at
+`--logging_steps`, `--save_steps` and the end.
+
+Written: `output_dir/` becomes a snapshot (config.json, model.safetensors under the reference's key names, the tokenizer) that
+`CaduceusForMaskedLM.from_pretrained`, `mlm_eval` and `zero_shot` load, with `train_results.json`, `all_results.json` and
+`trainer_state.json`; `output_dir/checkpoint-<step>/` is such a snapshot plus `optimizer.pt` (master weights, moments, step),
+`rng_state.pt` (the mask generator's state; the window order is re-derived from (`--seed`, epoch)) and `trainer_state.json` (step, epoch, log history of loss,
+learning_rate, grad_norm and skipped_steps).  `--resume_from_checkpoint` continues from one, bit for bit.  `--do_eval` runs
+`mlm_eval.evaluate_split` on the saved snapshot.
+
+Departures from the reference, all stated in DESIGN.md §4o: a step whose gradient norm is not finite is skipped and counted instead
+of letting NaNs into the weights; weight decay leaves out `A_log` and `D` beside biases and norm weights; `--dtype bfloat16` means
+bf16 parameters and kernels with fp32 master weights in the optimizer, where the reference's `bf16=True` is autocast around fp32
+parameters.  Not built: DDP / torchrun, LoRA training, activation checkpointing."""
+from __future__ import annotations
+
+import json
+import logging
+import math
+import os
+import time
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+logger = logging.getLogger(__name__)
+
+SCHEDULES = ("linear", "cosine", "constant", "constant_with_warmup")
+
+
+def lr_lambda(kind: str, step: int, warmup: int, total: int) -> float:
+    """`transformers.get_scheduler(kind, ..., num_warmup_steps=warmup, num_training_steps=total)`'s multiplier after `step` scheduler steps"""
+    if kind == "constant":
+        return 1.0
+    if step < warmup:
+        return float(step) / float(max(1, warmup))
+    if kind == "constant_with_warmup":
+        return 1.0
+    if kind == "linear":
+        return max(0.0, float(total - step) / float(max(1, total - warmup)))
+    if kind == "cosine":
+        progress = float(step - warmup) / float(max(1, total - warmup))
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * 0.5 * 2.0 * progress)))
+    raise ValueError(f"unknown --lr_scheduler_type {kind!r} (one of {', '.join(SCHEDULES)})")
+
+
+def warmup_steps_of(warmup_steps: int, warmup_ratio: float, total: int) -> int:
+    """`TrainingArguments.get_warmup_steps`"""
+    return int(warmup_steps) if warmup_steps > 0 else math.ceil(total * warmup_ratio)
+
+
+def steps_per_epoch(n_windows: int, batch: int, accumulation: int) -> int:
+    return max(1, math.ceil(n_windows / batch) // accumulation)
+
+
+class BatchSource:
+    """The micro-batches of every optimizer step, a function of (seed, data, batch, accumulation) and of how many micro-batches were
+    drawn before: window order from a generator seeded by (seed, epoch), masks from the collator on a CPU generator of its own."""
+
+    def __init__(self, ids: np.ndarray, special: np.ndarray, weights: np.ndarray, collator, batch: int, accumulation: int, seed: int):
+        self.ids, self.special, self.weights = ids, special, weights
+        self.collator, self.batch, self.accumulation, self.seed = collator, int(batch), int(accumulation), int(seed)
+        self.n = ids.shape[0]
+        if self.n == 0:
+            raise ValueError("no training windows")
+        self.steps_per_epoch = steps_per_epoch(self.n, self.batch, self.accumulation)
+        self.mask_generator = torch.Generator().manual_seed(self.seed)
+        self.order_generator = torch.Generator()
+        self.collator.generator = self.mask_generator
+        self._epoch, self._order = None, None
+
+    def order(self, epoch: int) -> torch.Tensor:
+        if self._epoch != epoch:
+            self.order_generator.manual_seed(self.seed * 1000003 + epoch)
+            self._epoch, self._order = epoch, torch.randperm(self.n, generator=self.order_generator)
+        return self._order
+
+    def windows(self, step: int) -> List[np.ndarray]:
+        """the window indices of each micro-batch of optimizer step `step` (0-based)"""
+        epoch, s = divmod(step, self.steps_per_epoch)
+        order = self.order(epoch).numpy()
+        out = []
+        for j in range(self.accumulation):
+            lo = (s * self.accumulation + j) * self.batch
+            if lo < self.n:
+                out.append(order[lo:lo + self.batch])
+        return out
+
+    def step_batches(self, step: int):
+        """-> [(masked input_ids int32 [b, L], labels int32 [b, L], loss_weights fp32 [b, L])] CPU tensors; advances the mask generator"""
+        out = []
+        for idx in self.windows(step):
+            x, y = self.collator.torch_mask_tokens(torch.from_numpy(self.ids[idx].copy()), special_tokens_mask=torch.from_numpy(self.special[idx].copy()))
+            out.append((x.to(torch.int32), y.to(torch.int32), torch.from_numpy(self.weights[idx].copy())))
+        return out
+
+    def state(self) -> dict:
+        """what a resume cannot re-derive: the mask generator's state (the order is a function of (seed, epoch))"""
+        return {"mask_generator": self.mask_generator.get_state()}
+
+    def load_state(self, st: dict):
+        self.mask_generator.set_state(st["mask_generator"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def build_parser():
+    import argparse
+    p = argparse.ArgumentParser(prog="pretrain", description="Masked-LM pretraining on the MI355X kernels (src/HF_pre_train.py --do_train)")
+    p.add_argument("--model_name_or_path", default=None)
+    p.add_argument("--config_name", default=None)
+    p.add_argument("--tokenizer_name", default=None)
+    p.add_argument("--dataset_name", required=True)
+    p.add_argument("--dataset_config_name", default=None)
+    p.add_argument("--do_train", action="store_true")
+    p.add_argument("--do_eval", action="store_true")
+    p.add_argument("--output_dir", required=True)
+    p.add_argument("--per_device_train_batch_size", type=int, default=8)
+    p.add_argument("--per_device_eval_batch_size", type=int, default=8)
+    p.add_argument("--gradient_accumulation_steps", type=int, default=1)
+    p.add_argument("--learning_rate", type=float, default=5e-5)
+    p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--adam_beta1", type=float, default=0.9)
+    p.add_argument("--adam_beta2", type=float, default=0.999)
+    p.add_argument("--adam_epsilon", type=float, default=1e-8)
+    p.add_argument("--max_grad_norm", type=float, default=1.0)
+    p.add_argument("--num_train_epochs", type=float, default=3.0)
+    p.add_argument("--max_steps", type=int, default=-1)
+    p.add_argument("--lr_scheduler_type", default="linear", choices=SCHEDULES)
+    p.add_argument("--warmup_steps", type=int, default=0)
+    p.add_argument("--warmup_ratio", type=float, default=0.0)
+    p.add_argument("--mlm_probability", type=float, default=0.15)
+    p.add_argument("--soft_masked_loss_weights_train", type=float, default=1.0)
+    p.add_argument("--soft_masked_loss_weights_evaluation", type=float, default=1.0)
+    p.add_argument("--max_train_samples", type=int, default=None)
+    p.add_argument("--max_eval_samples", type=int, default=None)
+    p.add_argument("--logging_steps", type=int, default=500)
+    p.add_argument("--save_steps", type=int, default=500)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--resume_from_checkpoint", default=None)
+    p.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
+    p.add_argument("--device", default="cuda:0")
+    return p
+
+
+def load_tokenizer(a):
+    from .checkpoint import resolve_snapshot
+    src = a.tokenizer_name or a.model_name_or_path
+    if src:
+        from transformers import AutoTokenizer
+        from . import register
+        register()
+        return AutoTokenizer.from_pretrained(resolve_snapshot(src))
+    from .tokenization_caduceus import CaduceusTokenizer
+    return CaduceusTokenizer()
+
+
+def build_model(a, dtype: torch.dtype, source: Optional[str] = None):
+    """the trainable model from `source` (a checkpoint to resume), else --model_name_or_path, else --config_name from scratch"""
+    from .checkpoint import synthetic_state_dict
+    from .configuration_caduceus import config_from_dict
+    from .training import TrainableCaduceusForMaskedLM
+    path = source or a.model_name_or_path
+    if path:
+        return TrainableCaduceusForMaskedLM.from_pretrained(path, dtype=dtype, device=a.device)
+    if not a.config_name:
+        raise SystemExit("pass --model_name_or_path or --config_name")
+    cfg_path = os.path.join(a.config_name, "config.json") if os.path.isdir(a.config_name) else a.config_name
+    with open(cfg_path) as f:
+        cfg = config_from_dict(json.load(f))
+    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device)
+    model.load_state_dict(synthetic_state_dict(cfg, seed=a.seed, stress=False))
+    return model
+
+
+def save_snapshot(model, tokenizer, path: str):
+    """config.json + model.safetensors (the reference's key names, tied duplicates dropped as in a real snapshot) + the tokenizer"""
+    from .checkpoint import save_checkpoint
+    sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    save_checkpoint(path, model.config, sd, with_tokenizer=False)
+    tokenizer.save_pretrained(path)
+
+
+def _write_json(path: str, obj):
+    with open(path, "w") as f:
+        json.dump(obj, f, indent=2, sort_keys=True)
+
+
+class Trainer:
+    """The loop around model, optimizer and batch source; `micro_step` is the only place the model runs."""
+
+    def __init__(self, model, optimizer, source: BatchSource, tokenizer, a, max_steps: int, warmup: int):
+        self.model, self.opt, self.source, self.tok, self.a = model, optimizer, source, tokenizer, a
+        self.max_steps, self.warmup = max_steps, warmup
+        self.step = 0
+        self.log_history: List[dict] = []
+        dev = a.device
+        self.window_loss = torch.zeros((), dtype=torch.float32, device=dev)     # sum of the step losses since the last log
+        self.total_loss = torch.zeros((), dtype=torch.float32, device=dev)      # ... since the start
+        self.window_steps = 0
+
+    def lr(self, step: int) -> float:
+        return self.a.learning_rate * lr_lambda(self.a.lr_scheduler_type, step, self.warmup, self.max_steps)
+
+    def micro_step(self, ids, labels, weights):
+        dev = self.a.device
+        up = lambda t: t.pin_memory().to(dev, non_blocking=True)
+        out = self.model(up(ids), up(labels), up(weights))
+        out.loss.backward()
+        return out.loss.detach()
+
+    def train_step(self):
+        """optimizer step number self.step (0-based): its micro-batches, the fused step, zero_grad; nothing is read back"""
+        batches = self.source.step_batches(self.step)
+        scale = 1.0 / len(batches)
+        self.opt.grad_scale = scale
+        loss = None
+        for ids, labels, weights in batches:
+            l = self.micro_step(ids, labels, weights).float() * scale
+            loss = l if loss is None else loss + l
+        lr = self.lr(self.step)
+        self.opt.step(lr=lr)
+        self.opt.zero_grad()
+        self.window_loss += loss
+        self.total_loss += loss
+        self.window_steps += 1
+        self.step += 1
+        return lr
+
+    def epoch(self) -> float:
+        return self.step / self.source.steps_per_epoch
+
+    def log(self, lr: float):
+        st = self.opt.state()                                   # synchronises
+        entry = {"step": self.step, "epoch": round(self.epoch(), 4), "loss": float(self.window_loss) / max(1, self.window_steps),
+                 "learning_rate": lr, "grad_norm": st["norm"], "skipped_steps": st["skipped"]}
+        self.window_loss.zero_()
+        self.window_steps = 0
+        self.log_history.append(entry)
+        logger.info(json.dumps(entry))
+        return entry
+
+    def trainer_state(self) -> dict:
+        return {"global_step": self.step, "epoch": self.epoch(), "max_steps": self.max_steps, "log_history": self.log_history,
+                "window_loss": float(self.window_loss), "window_steps": self.window_steps, "total_loss": float(self.total_loss)}
+
+    def save_checkpoint(self):
+        path = os.path.join(self.a.output_dir, f"checkpoint-{self.step}")
+        save_snapshot(self.model, self.tok, path)
+        torch.save(self.opt.state_dict(), os.path.join(path, "optimizer.pt"))
+        torch.save(self.source.state(), os.path.join(path, "rng_state.pt"))
+        _write_json(os.path.join(path, "trainer_state.json"), self.trainer_state())
+        return path
+
+    def resume(self, path: str):
+        self.opt.load_state_dict(torch.load(os.path.join(path, "optimizer.pt"), weights_only=False))
+        self.source.load_state(torch.load(os.path.join(path, "rng_state.pt"), weights_only=False))
+        with open(os.path.join(path, "trainer_state.json")) as f:
+            ts = json.load(f)
+        self.step, self.log_history, self.window_steps = int(ts["global_step"]), list(ts["log_history"]), int(ts["window_steps"])
+        self.window_loss.fill_(ts["window_loss"])               # fp32 values, exact in the JSON's doubles
+        self.total_loss.fill_(ts["total_loss"])
+        if self.opt.step_count != self.step:
+            raise ValueError(f"{path}: optimizer at step {self.opt.step_count}, trainer_state at {self.step}")
+
+    def run(self):
+        a = self.a
+        while self.step < self.max_steps:
+            lr = self.train_step()
+            if a.logging_steps > 0 and (self.step % a.logging_steps == 0 or self.step == self.max_steps):
+                self.log(lr)
+            if a.save_steps > 0 and self.step % a.save_steps == 0:
+                self.save_checkpoint()
+
+
+def train(a) -> Dict[str, float]:
+    from . import mlm_eval
+    from .optim import AdamW
+    dtype = {"float32": torch.float32, "bfloat16": torch.bfloat16}[a.dtype]
+    if a.per_device_train_batch_size < 1 or a.gradient_accumulation_steps < 1:
+        raise SystemExit("--per_device_train_batch_size and --gradient_accumulation_steps must be >= 1")
+    tok = load_tokenizer(a)
+    seqs = mlm_eval.load_sequences(a.dataset_name, "train", a.dataset_config_name)
+    if a.max_train_samples is not None:
+        seqs = seqs[:max(0, a.max_train_samples)]
+    ids, special, weights = mlm_eval.tokenize_windows(tok, seqs, a.soft_masked_loss_weights_train)
+    source = BatchSource(ids, special, weights, mlm_eval.make_collator(tok, a.mlm_probability), a.per_device_train_batch_size,
+                         a.gradient_accumulation_steps, a.seed)
+    max_steps = a.max_steps if a.max_steps > 0 else math.ceil(a.num_train_epochs * source.steps_per_epoch)
+    warmup = warmup_steps_of(a.warmup_steps, a.warmup_ratio, max_steps)
+    model = build_model(a, dtype, a.resume_from_checkpoint)
+    opt = AdamW(model.named_parameters(), lr=a.learning_rate, betas=(a.adam_beta1, a.adam_beta2), eps=a.adam_epsilon,
+                weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm)
+    tr = Trainer(model, opt, source, tok, a, max_steps, warmup)
+    if a.resume_from_checkpoint:
+        tr.resume(a.resume_from_checkpoint)
+    os.makedirs(a.output_dir, exist_ok=True)
+    first = tr.step
+    t0 = time.time()
+    tr.run()
+    torch.cuda.synchronize(a.device)
+    runtime = time.time() - t0
+    save_snapshot(model, tok, a.output_dir)
+    done = tr.step - first
+    windows = done * a.per_device_train_batch_size * a.gradient_accumulation_steps
+    metrics = {"epoch": tr.epoch(), "train_loss": float(tr.total_loss) / max(1, tr.step), "train_runtime": round(runtime, 4),
+               "train_samples": int(source.n), "train_samples_per_second": round(windows / runtime, 3) if runtime > 0 else 0.0,
+               "train_steps_per_second": round(done / runtime, 3) if runtime > 0 else 0.0, "skipped_steps": opt.state()["skipped"]}
+    _write_json(os.path.join(a.output_dir, "train_results.json"), metrics)
+    _write_json(os.path.join(a.output_dir, "trainer_state.json"), tr.trainer_state())
+    return metrics
+
+
+def evaluate(a) -> Dict[str, float]:
+    from . import mlm_eval
+    model, tok = mlm_eval.load_model_and_tokenizer(a.output_dir if a.do_train else (a.model_name_or_path or a.output_dir), a.tokenizer_name,
+                                                   a.device, a.dtype)
+    seqs = mlm_eval.load_sequences(a.dataset_name, "validation", a.dataset_config_name)
+    res = mlm_eval.evaluate_split(model, tok, seqs, "eval", a.soft_masked_loss_weights_evaluation, a.mlm_probability,
+                                  a.per_device_eval_batch_size, a.seed, a.max_eval_samples, a.device)
+    _write_json(os.path.join(a.output_dir, "eval_results.json"), res)
+    return res
+
+
+def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Dict[str, float]]:
+    a = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
+    if not (a.do_train or a.do_eval):
+        raise SystemExit("nothing to do: pass --do_train and / or --do_eval")
+    results = {}
+    if a.do_train:
+        results["train"] = train(a)
+        print(json.dumps(results["train"], sort_keys=True), flush=True)
+    if a.do_eval:
+        os.makedirs(a.output_dir, exist_ok=True)
+        results["eval"] = evaluate(a)
+        print(json.dumps(results["eval"], sort_keys=True), flush=True)
+    merged = {k: v for r in results.values() for k, v in r.items()}
+    _write_json(os.path.join(a.output_dir, "all_results.json"), merged)
+    return results
+
+
+if __name__ == "__main__":
+    main()

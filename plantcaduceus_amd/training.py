@@ -10,8 +10,9 @@
     loss = sums[:, 0].sum() / sums[:, 1].sum()
 
 The module tree is `modeling_caduceus`'s parameter holders, so `state_dict()` has the reference's key names and loads into
-`CaduceusForMaskedLM` (and a snapshot of it loads here); the ties are shared storage.  There is no CPU path, and no optimizer, Trainer
-glue, gradient checkpointing or LoRA wrapping here: autograd keeps, per layer, what the operators save (DESIGN.md §4n lists it)."""
+`CaduceusForMaskedLM` (and a snapshot of it loads here); the ties are shared storage.  There is no CPU path, and no gradient
+checkpointing or LoRA wrapping here: autograd keeps, per layer, what the operators save (DESIGN.md §4n lists it).  The optimizer is
+`plantcaduceus_amd.optim.AdamW`, the training command `plantcaduceus_amd.pretrain`."""
 from __future__ import annotations
 
 import json
