@@ -1,5 +1,5 @@
 /* pcad_bwd.h - C ABI of libpcad_bwd.so: the backward operators of a Caduceus block beyond the selective scan, and of the masked-LM
- * loss head (training support).
+ * loss head and of the pooled sequence-classification head (training support).
  *
  * A third library beside libpcad.so (include/pcad.h: the inference ABI) and libpcad_train.so (include/pcad_train.h: the selective
  * scan's backward), whose exported symbol sets stay as they are.  This one is OPEN: a later backward operator is added here - its
@@ -7,7 +7,7 @@
  * library; what is held is that this header, that table and the library's exports name the same pcad_* symbols.
  * libpcad_bwd.so links libpcad.so (same directory) and shares its conventions: status codes (pcad_status), dtypes (pcad_dtype),
  * pcad_stream, and the calling thread's pcad_last_error() text.  Built by the same Makefile from csrc/bwd_api.hip, csrc/conv_bwd.hip,
- * csrc/norm_bwd.hip, csrc/loss_bwd.hip and csrc/optim.hip (the optimizer step that uses the gradients: the last section below).
+ * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip and csrc/optim.hip (the optimizer step that uses the gradients: the last section below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
@@ -83,6 +83,35 @@ int pcad_loss_head_bwd(const void* h, const void* res, const float* norm_weight,
                        const int32_t* labels, const float* loss_weights, int ignore_index, const float* dsum, const float* dnll,
                        void* dh, void* dres, float* dnorm_weight, float* demb, void* scratch, size_t scratch_bytes,
                        int B, int L, int D, float eps, int dtype, int res_dtype, pcad_stream stream);
+
+/* Backward of pcad_pooled_head on plain rows (no fragment layout of res): norm_f -> per-strand pooling -> score -> (fwd + rc) / 2, the
+ * head of CaduceusForSequenceClassification.  Replaces: the backward of rms_norm_fn + the stack / flip of the two strands + the pooling
+ * + the score Linear + the strand average, and never forms norm_f's output or its gradient as a tensor.  The forward it differentiates
+ * (DESIGN.md section 4f), per row:  v = h + res   rstd = rsqrt(mean(v^2) + eps)   vh = v rstd   o = round(vh w) in dtype;
+ * pooled[b, s] = the mean over the strand's own rows (fp32 sum / L, rounded once), or row 0, or row L-1 - the forward strand's rows are
+ * b L + p, the rc strand's (B + b) L + p, no flip;  logits[b, n] = round(round(round(pooled[b, 0] . W[n]) + round(pooled[b, 1] . W[n])) / 2).
+ * Every rounding of the forward is the identity in the derivative.  Everything in fp32:
+ *   dpooled[b, s, :] = 1/2 sum_n dlogits[b, n] W[n, :]                                    (n in index order; the same for both strands)
+ *   dscore_w[n, :]   = 1/2 sum_b dlogits[b, n] (pooled[b, 0, :] + pooled[b, 1, :])        (b in index order)
+ *   do(row)          = dpooled[b, s] / L   mean: every row of the strand;   first: row 0 only;   last: row L-1 only;   other rows: 0
+ *   dv_i = rstd (w_i do_i - vh_i (1/D) sum_j w_j do_j vh_j)            dh = round(dv) in dtype     dres = round(dv) in res_dtype
+ *   dnorm_weight_i = sum_rows do_i vh_i
+ * The only new roundings are the stores of dh and dres.  With first / last the rows that carry no gradient are written as zeros.
+ * PCAD_POOL_MAX is refused (PCAD_ERR_INVALID naming `pooling`): the gradient of a maximum needs a tie rule among rows that are equal
+ * after rounding to the model dtype, and nothing in the reference pins one.  Inference keeps max pooling.
+ *   h, dh      [2B * L, D] dtype;  res, dres [2B * L, D] res_dtype (BF16 / F32, BF16 / BF16 or F32 / F32);  D % 8 == 0, D <= 2048
+ *   norm_weight, dnorm_weight fp32 [D];  score_w, dscore_w fp32 [num_labels, D] (score_w: the dtype-rounded weight, as the forward takes it);
+ *   1 <= num_labels <= PCAD_MAX_LABELS;  pooled fp32 [B, 2, D]: the forward's pooled_out;  dlogits fp32 [B, num_labels]
+ *   dh, dres, dnorm_weight, dscore_w may each be NULL (not computed), not all of them;  h, res, norm_weight, dh, dres 16-byte aligned
+ *   scratch    pcad_pooled_head_bwd_scratch_bytes(B, L, D, pooling) bytes: the windows' do rows [B, D] (formed once per window by a first
+ *              launch, not per row), then one row of D partials of dnorm_weight per (window, strand, segment of 64 rows) - first / last:
+ *              per (window, strand) - which a second kernel adds in a fixed order; each part rounded up to 256 bytes.  0 for a pooling
+ *              this entry refuses.
+ * B == 0: OK, nothing is done.  L == 0 with B > 0: PCAD_ERR_INVALID. */
+size_t pcad_pooled_head_bwd_scratch_bytes(int B, int L, int D, int pooling);
+int pcad_pooled_head_bwd(const void* h, const void* res, const float* norm_weight, const float* score_w, const float* pooled,
+                         const float* dlogits, void* dh, void* dres, float* dnorm_weight, float* dscore_w, void* scratch, size_t scratch_bytes,
+                         int B, int L, int D, int num_labels, float eps, int pooling, int dtype, int res_dtype, pcad_stream stream);
 
 /* ---- The optimizer step: AdamW with global-norm gradient clipping over a whole parameter set ----------------
  * Replaces: torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step + zero_grad, in three (one) launches however many tensors there are.

@@ -115,6 +115,51 @@ int pcad_loss_head_bwd(const void* h, const void* res, const float* norm_weight,
     return PCAD_OK;
 }
 
+size_t pcad_pooled_head_bwd_scratch_bytes(int B, int L, int D, int pooling) {
+    if (B <= 0 || L <= 0 || D <= 0) return 0;
+    if (pooling != PCAD_POOL_MEAN && pooling != PCAD_POOL_FIRST && pooling != PCAD_POOL_LAST) return 0;
+    return pooled_head_bwd_bytes(B, L, D, pooling);
+}
+
+int pcad_pooled_head_bwd(const void* h, const void* res, const float* norm_weight, const float* score_w, const float* pooled,
+                         const float* dlogits, void* dh, void* dres, float* dnorm_weight, float* dscore_w, void* scratch, size_t scratch_bytes,
+                         int B, int L, int D, int num_labels, float eps, int pooling, int dtype, int res_dtype, pcad_stream stream) {
+    const char* who = "pcad_pooled_head_bwd";
+    const struct { const void* p; const char* name; } req[] = {{h, "h"}, {res, "res"}, {norm_weight, "norm_weight"}, {score_w, "score_w"},
+                                                               {pooled, "pooled"}, {dlogits, "dlogits"}};
+    for (const auto& r : req)
+        if (!r.p) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);
+    if (!dh && !dres && !dnorm_weight && !dscore_w)
+        return fail(PCAD_ERR_INVALID, "%s: no output requested (dh, dres, dnorm_weight and dscore_w are all NULL)", who);
+    if (pooling == PCAD_POOL_MAX)
+        return fail(PCAD_ERR_INVALID, "%s: pooling PCAD_POOL_MAX has no backward (its gradient needs a tie rule among rows that are equal "
+                                      "after rounding to the model dtype)", who);
+    if (pooling != PCAD_POOL_MEAN && pooling != PCAD_POOL_FIRST && pooling != PCAD_POOL_LAST)
+        return fail(PCAD_ERR_INVALID, "%s: bad pooling %d", who, pooling);
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (res_dtype != PCAD_F32 && !(res_dtype == PCAD_BF16 && dtype == PCAD_BF16))
+        return fail(PCAD_ERR_INVALID, "%s: bad res_dtype %d for dtype %d (BF16 / F32, BF16 / BF16 or F32 / F32)", who, res_dtype, dtype);
+    if (B < 0 || L < 0) return fail(PCAD_ERR_INVALID, "%s: B, L must be >= 0 (B=%d, L=%d)", who, B, L);
+    if (D <= 0 || D % 8) return fail(PCAD_ERR_INVALID, "%s: D must be a positive multiple of 8 (D=%d)", who, D);
+    if (D > 2048) return fail(PCAD_ERR_INVALID, "%s: D must be <= 2048 (D=%d)", who, D);
+    if (num_labels < 1 || num_labels > PCAD_MAX_LABELS)
+        return fail(PCAD_ERR_INVALID, "%s: num_labels must be in [1, %d] (num_labels=%d)", who, PCAD_MAX_LABELS, num_labels);
+    const struct { const void* p; const char* name; } al[] = {{h, "h"}, {res, "res"}, {norm_weight, "norm_weight"}, {dh, "dh"}, {dres, "dres"}};
+    for (const auto& r : al)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    if (B == 0) return PCAD_OK;
+    if (L == 0) return fail(PCAD_ERR_INVALID, "%s: L must be >= 1 (a strand without rows has nothing to pool)", who);
+    if (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < pooled_head_bwd_bytes(B, L, D, pooling))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_pooled_head_bwd_scratch_bytes large", who);
+    hipError_t err = launch_pooled_head_bwd({.in = {.h = h, .res = res, .w = norm_weight, .B = B, .L = L, .D = D, .eps = eps, .dt = dtype, .rdt = res_dtype},
+                                             .score_w = score_w, .NL = num_labels, .pooled = pooled, .dlogits = dlogits, .pooling = pooling, .dh = dh,
+                                             .dres = dres, .dnorm_w = dnorm_weight, .dscore_w = dscore_w, .scratch = scratch},
+                                            (hipStream_t)stream);
+    if (err == hipErrorInvalidValue) return fail(PCAD_ERR_INVALID, "%s: 2 B * ceil(L / 64) must fit a 32-bit grid", who);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 int pcad_optim_plan(const pcad_optim_tensor* table, int64_t count, int32_t* chunk_map, int64_t chunk_capacity, int64_t* chunks_out) {
     const char* who = "pcad_optim_plan";
     if (count < 0) return fail(PCAD_ERR_INVALID, "%s: count must be >= 0", who);

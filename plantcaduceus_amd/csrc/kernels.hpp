@@ -431,6 +431,28 @@ struct LossHeadBwdLaunch {
 size_t loss_head_bwd_bytes(int B, int L, int D);
 hipError_t launch_loss_head_bwd(const LossHeadBwdLaunch& a, hipStream_t s);
 
+// pool_bwd.hip (libpcad_bwd.so): backward of launch_pooled_head on plain rows (pcad_bwd.h pcad_pooled_head_bwd), pooling
+// POOL_MEAN / POOL_FIRST / POOL_LAST (POOL_MAX is refused: its gradient needs a tie rule nothing pins).  `in` as the forward takes it
+// (res_frag, ids and status unused).  dh [2B * L, D] dtype dt and dres [2B * L, D] dtype rdt: every row is written, zeros where the
+// pooling did not read the row; dnorm_w fp32 [D]; dscore_w fp32 [NL, D]; each output may be null, not all of them.
+// scratch: pooled_head_bwd_bytes(B, L, D, pooling) bytes, 256-byte aligned - the windows' cotangent rows [B, D], then one partial row of
+// dnorm_w per (window, strand, segment of POOL_BWD_SEG rows that carries a gradient), which launch_sum_partials adds.
+constexpr int POOL_BWD_SEG = 64;      // rows per block = pool.hip's POOL_SEG: the segmentation depends on L only
+struct PooledHeadBwdLaunch {
+    HeadInput in;
+    const float* score_w = nullptr;  int NL = 0;      // score head [NL, D] fp32 (the dtype-rounded weight), 1 <= NL <= 256
+    const float* pooled = nullptr;    // [B, 2, D] fp32: the forward's pooled_out (read for dscore_w only)
+    const float* dlogits = nullptr;   // [B, NL] fp32: the gradient of logits_out
+    int pooling = POOL_MEAN;
+    void* dh = nullptr;
+    void* dres = nullptr;
+    float* dnorm_w = nullptr;
+    float* dscore_w = nullptr;
+    void* scratch = nullptr;
+};
+size_t pooled_head_bwd_bytes(int B, int L, int D, int pooling);
+hipError_t launch_pooled_head_bwd(const PooledHeadBwdLaunch& a, hipStream_t s);
+
 // optim.hip (libpcad_bwd.so): one AdamW step with global-norm clipping over a table of tensors (pcad_bwd.h pcad_adamw_step) and
 // the zeroing of its gradients (pcad_zero_grads).  table: device array of pcad_optim_tensor; map: device int32 [chunks, 2] = (tensor,
 // chunk within the tensor), as pcad_optim_plan fills it; one block per chunk of OPTIM_CHUNK elements, chunks never straddle two tensors.

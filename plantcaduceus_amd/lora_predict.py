@@ -1,8 +1,9 @@
-"""The inference commands of the reference's `src/lora_fine_tune.py` - `tokenize` (:43-170), `evaluate` (:356-413) and
-`predict` (:415-499) - for the released fine-tuned PlantCAD2 models (LoRA adapters over the PlantCAD2 trunks), on the MI355X
+"""The commands of the reference's `src/lora_fine_tune.py` - `tokenize` (:43-170), `train` (:243-353), `evaluate` (:356-413) and
+`predict` (:415-499) - for the fine-tuned PlantCAD2 models (LoRA adapters over the PlantCAD2 trunks), on the MI355X
 engine:
 
     python -m plantcaduceus_amd.lora_predict tokenize --data_dir x.tsv --model_name <base> --sequence_length 8192 --output_path x.parquet
+    python -m plantcaduceus_amd.lora_predict train    --train_dir t.parquet --valid_dir v.parquet --model_name <base> --output_dir out
     python -m plantcaduceus_amd.lora_predict predict  --checkpoint_dir <adapter> --data_dir x.parquet --task_type classification
     python -m plantcaduceus_amd.lora_predict evaluate --checkpoint_dir <adapter> --data_dir x.parquet --task_type multi_label --num_labels 92
 
@@ -11,21 +12,31 @@ reference's dtype - it passes none to from_pretrained - runs with "f32_gemm_spli
 bfloat16), `--pooling` (the head's pooling_strategy, default mean) and `--lora-deltas` (adapters.load_adapter).  `--model_name`
 overrides the adapter's base_model_name_or_path.  Hub ids resolve from local files / the HF cache only.
 
+`train` fine-tunes `training.TrainableCaduceusForSequenceClassification` - frozen trunk, LoRA factors, `score` - with
+`optim.AdamW` and `pretrain`'s schedules, window order and checkpoint form; single process, one GPU.  It takes the reference
+`train()`'s flag names and defaults, except that `--bf16` defaults to false (float32, as `predict` / `evaluate` default) and means
+bf16 trunk and kernels with fp32 factors and score; `save_total_limit` is 5.  Additions: `--device`, `--pooling`, `--train_lora {1,0}`
+(0: the frozen-trunk mode), `--max_grad_norm` (1.0) and `--lora_dropout` (0.0; any other value is refused, as is `--use_wandb`).
+`output_dir/checkpoint-<step>/` is an adapter directory plus `optimizer.pt` and `trainer_state.json`; `output_dir/` ends as the final
+adapter, which `predict --checkpoint_dir <output_dir> --lora-deltas apply` loads (after `--train_lora 0`: the default `auto`).
+
 Under torchrun the windows are sharded over the ranks (plantcad2_eval._sharded_rows); rank 0 writes / prints.  Metrics are
 computed on the host without sklearn (the reference's compute_metrics_* :517-563 restated; pinned against sklearn / scipy in
 tests/test_seqcls.py).
 """
 from __future__ import annotations
 
+import json
 import logging
 import os
+import shutil
 import time
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import sharding
+from . import pretrain, sharding
 from .plantcad2_eval import _midranks, _sharded_rows, auroc, average_precision
 
 logger = logging.getLogger(__name__)
@@ -303,6 +314,206 @@ def evaluate(checkpoint_dir: str, data_dir: str, output_dir: str = "/tmp/pcv2-ft
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# train (reference :243-353)
+class LabelledBatches(pretrain.WindowOrder):
+    """`pretrain.WindowOrder` over labelled windows: the micro-batches of every optimizer step, a function of (seed, data, batch,
+    accumulation); nothing is drawn per batch."""
+
+    def __init__(self, ids: np.ndarray, labels: np.ndarray, batch: int, accumulation: int, seed: int):
+        super().__init__(ids.shape[0], batch, accumulation, seed)
+        self.ids, self.labels = ids, labels
+
+    def step_batches(self, step: int):
+        """-> [(input_ids int32 [b, L], labels [b] or [b, NL], None)] CPU tensors"""
+        return [(torch.from_numpy(self.ids[idx].copy()), torch.from_numpy(self.labels[idx].copy()), None) for idx in self.windows(step)]
+
+
+def _labels_for(labels: np.ndarray, task_type: str) -> np.ndarray:
+    if task_type == "classification":
+        return np.asarray(labels).astype(np.int64).reshape(-1)
+    if task_type == "regression":
+        return np.asarray(labels).astype(np.float32).reshape(-1)
+    return np.asarray(labels).astype(np.float32)
+
+
+def _interval(strategy: str, steps: int, per_epoch: int, flag: str) -> int:
+    if strategy == "no":
+        return 0
+    if strategy == "steps":
+        return max(0, int(steps))
+    if strategy == "epoch":
+        return per_epoch
+    raise SystemExit(f"--{flag} must be one of no, steps, epoch (got {strategy!r})")
+
+
+SAVE_TOTAL_LIMIT = 5          # the reference's TrainingArguments(save_total_limit=5)
+
+
+class FinetuneTrainer(pretrain.Trainer):
+    """`pretrain.Trainer` around the sequence-classification model: its step, schedule, logging, trainer_state and resume; the micro-step,
+    the checkpoint (an adapter directory) and the evaluation are this command's.  a: the command's settings (output_dir, model_name,
+    task_type, device, learning_rate, lr_scheduler_type, warmup_steps, eval_batch_size, eval / save strategy and steps, logging_steps);
+    valid: (ids, labels) of the validation windows, or None."""
+
+    def __init__(self, model, optimizer, source, a, max_steps: int, valid=None):
+        super().__init__(model, optimizer, source, None, a, max_steps, int(a.warmup_steps))
+        self.valid = valid
+
+    def micro_step(self, ids, labels, _weights):
+        dev = self.a.device
+        out = self.model(ids.to(dev), labels.to(dev))
+        out.loss.backward()
+        return out.loss.detach()
+
+    def evaluate(self):
+        ids, labels = self.valid
+        t0 = time.time()
+        logits = predict_logits_trainable(self.model, ids, self.a.device, self.a.eval_batch_size)
+        res = {"eval_loss": eval_loss(self.model, logits, labels, self.a.task_type, self.a.eval_batch_size)}
+        res.update({"eval_" + k: v for k, v in METRICS[self.a.task_type](logits, labels).items()})
+        res["eval_runtime"] = round(time.time() - t0, 4)
+        entry = dict(res, step=self.step, epoch=round(self.epoch(), 4))
+        self.log_history.append(entry)
+        logger.info(json.dumps(entry))
+        return res
+
+    def save_checkpoint(self):
+        path = os.path.join(self.a.output_dir, f"checkpoint-{self.step}")
+        self.model.save_adapter(path, self.a.model_name)
+        torch.save(self.opt.state_dict(), os.path.join(path, "optimizer.pt"))
+        pretrain._write_json(os.path.join(path, "trainer_state.json"), self.trainer_state())
+        kept = sorted((int(d.split("-")[1]), d) for d in os.listdir(self.a.output_dir)
+                      if d.startswith("checkpoint-") and d.split("-")[1].isdigit())
+        for _, d in kept[:-SAVE_TOTAL_LIMIT]:
+            shutil.rmtree(os.path.join(self.a.output_dir, d))
+        return path
+
+    def restore_inputs(self, path: str):
+        """a checkpoint is an adapter directory: the factors and the head (nothing is drawn per batch, so there is no generator state)"""
+        self.model.load_adapter_weights(path)
+
+    def run(self):
+        a = self.a
+        every_eval = _interval(a.eval_strategy, a.eval_steps, self.source.steps_per_epoch, "eval_strategy") if self.valid is not None else 0
+        every_save = _interval(a.save_strategy, a.save_steps, self.source.steps_per_epoch, "save_strategy")
+        while self.step < self.max_steps:
+            lr = self.train_step()
+            if a.logging_steps > 0 and (self.step % a.logging_steps == 0 or self.step == self.max_steps):
+                self.log(lr)
+            if every_eval and self.step % every_eval == 0:
+                self.evaluate()
+            if every_save and self.step % every_save == 0:
+                self.save_checkpoint()
+
+
+def predict_logits_trainable(model, ids: np.ndarray, device: str, batch_size: int) -> np.ndarray:
+    """fp32 logits [N, num_labels] of the trainable model under torch.no_grad()"""
+    t = torch.from_numpy(np.ascontiguousarray(ids))
+    with torch.no_grad():
+        parts = [model(t[b0:b0 + batch_size].to(device)).logits for b0 in range(0, len(ids), batch_size)]
+    return torch.cat(parts, dim=0).float().cpu().numpy() if parts else np.zeros((0, model.num_labels), dtype=np.float32)
+
+
+def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", model_name: Optional[str] = None,
+          task_type: str = "classification", num_labels: Optional[int] = None, train_batch_size: int = 43, eval_batch_size: int = 3,
+          eval_num_samples: Optional[int] = 0, max_steps: int = 500, seed: int = 42, use_wandb: bool = False, learning_rate: float = 1e-3,
+          warmup_steps: int = 50, lr_scheduler_type: str = "linear", gradient_accumulation_steps: int = 64, bf16: bool = False,
+          num_train_epochs: float = 3, weight_decay: float = 0.01, eval_strategy: str = "steps", eval_steps: int = 25,
+          save_strategy: str = "steps", save_steps: int = 100, logging_steps: int = 100, resume_from_checkpoint: Optional[str] = None,
+          device: str = "cuda:0", pooling: str = "mean", train_lora: int = 1, max_grad_norm: float = 1.0, lora_dropout: float = 0.0) -> Dict[str, float]:
+    """Fine-tune a PlantCAD2 trunk with LoRA on tokenized parquet files (the `tokenize` command's).  -> the train metrics."""
+    import math
+    from types import SimpleNamespace
+    from .adapters import TASKS
+    from .optim import AdamW
+    from .training import TrainableCaduceusForSequenceClassification
+    if model_name is None:
+        raise SystemExit("--model_name is required")
+    if task_type not in TASK_TYPES:
+        raise SystemExit(f"--task_type must be one of {TASK_TYPES}")
+    if task_type == "multi_label" and (num_labels is None or num_labels <= 1):
+        raise SystemExit("For multi_label, please provide --num_labels > 1")
+    if use_wandb:
+        raise SystemExit("--use_wandb is not supported: the log history is written to trainer_state.json")
+    if float(lora_dropout) != 0.0:
+        raise SystemExit(f"--lora_dropout {lora_dropout} is not supported: the factors are trained in the merged form, which has no place "
+                         "for a dropout on the LoRA branch alone (DESIGN.md §4p); only 0.0 is accepted")
+    if pooling not in ("mean", "first", "last"):
+        raise SystemExit(f"--pooling {pooling} has no backward (max pooling's gradient needs a tie rule nothing pins): one of mean, first, last")
+    if lr_scheduler_type not in pretrain.SCHEDULES:
+        raise SystemExit(f"--lr_scheduler_type must be one of {', '.join(pretrain.SCHEDULES)}")
+    if train_batch_size < 1 or gradient_accumulation_steps < 1 or eval_batch_size < 1:
+        raise SystemExit("--train_batch_size, --eval_batch_size and --gradient_accumulation_steps must be >= 1")
+    nl, problem_type = TASKS[task_type]
+    nl = int(num_labels) if task_type == "multi_label" else nl
+    ids, labels, _ = read_tokenized(train_dir)
+    if labels is None:
+        raise SystemExit(f"{train_dir} has no label / labels column to train on")
+    source = LabelledBatches(ids, _labels_for(labels, task_type), train_batch_size, gradient_accumulation_steps, seed)
+    valid = None
+    if valid_dir:
+        vids, vlabels, _ = read_tokenized(valid_dir)
+        if vlabels is None:
+            raise SystemExit(f"{valid_dir} has no label / labels column to evaluate against")
+        if eval_num_samples:
+            vids, vlabels = vids[:eval_num_samples], vlabels[:eval_num_samples]
+        valid = (vids, vlabels)
+    total = max_steps if max_steps > 0 else math.ceil(num_train_epochs * source.steps_per_epoch)
+    model = TrainableCaduceusForSequenceClassification.from_pretrained(
+        model_name, nl, problem_type, pooling_strategy=pooling, dtype=torch.bfloat16 if bf16 else torch.float32, device=device,
+        train_lora=bool(int(train_lora)), seed=seed)
+    n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
+    n_all = sum(p.numel() for p in model.parameters())
+    logger.info("Trainable parameters: %d of %d (%.2f%%)", n_train, n_all, 100.0 * n_train / n_all)
+    opt = AdamW(model.named_parameters(), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    a = SimpleNamespace(output_dir=output_dir, model_name=model_name, task_type=task_type, device=device, learning_rate=learning_rate,
+                        lr_scheduler_type=lr_scheduler_type, warmup_steps=warmup_steps, eval_batch_size=eval_batch_size, eval_strategy=eval_strategy,
+                        eval_steps=eval_steps, save_strategy=save_strategy, save_steps=save_steps, logging_steps=logging_steps)
+    tr = FinetuneTrainer(model, opt, source, a, total, valid)
+    if resume_from_checkpoint:
+        logger.info("Resuming training from checkpoint: %s", resume_from_checkpoint)
+        tr.resume(resume_from_checkpoint)
+    os.makedirs(output_dir, exist_ok=True)
+    first, t0 = tr.step, time.time()
+    tr.run()
+    torch.cuda.synchronize(device)
+    runtime = time.time() - t0
+    model.save_adapter(output_dir, model_name)
+    done = tr.step - first
+    windows = done * train_batch_size * gradient_accumulation_steps
+    metrics = {"epoch": tr.epoch(), "train_loss": float(tr.total_loss) / max(1, tr.step), "train_runtime": round(runtime, 4),
+               "train_samples": int(source.n), "train_samples_per_second": round(windows / runtime, 3) if runtime > 0 else 0.0,
+               "train_steps_per_second": round(done / runtime, 3) if runtime > 0 else 0.0, "skipped_steps": opt.state()["skipped"]}
+    pretrain._write_json(os.path.join(output_dir, "train_results.json"), metrics)
+    pretrain._write_json(os.path.join(output_dir, "trainer_state.json"), tr.trainer_state())
+    print(metrics, flush=True)
+    return metrics
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _bool(v) -> bool:
+    if isinstance(v, bool):
+        return v
+    if str(v).lower() in ("1", "true", "yes", "y"):
+        return True
+    if str(v).lower() in ("0", "false", "no", "n"):
+        return False
+    raise ValueError(f"not a boolean: {v!r}")
+
+
+# the reference train()'s flags (name, type, default) as this command takes them; bf16 defaults to False here (module docstring)
+TRAIN_FLAGS = (("train_dir", str, None), ("valid_dir", str, None), ("output_dir", str, "/tmp/pcv2-ft"), ("model_name", str, None),
+               ("task_type", str, "classification"), ("num_labels", int, None), ("train_batch_size", int, 43), ("eval_batch_size", int, 3),
+               ("eval_num_samples", int, 0), ("max_steps", int, 500), ("seed", int, 42), ("use_wandb", _bool, False),
+               ("learning_rate", float, 1e-3), ("warmup_steps", int, 50), ("lr_scheduler_type", str, "linear"),
+               ("gradient_accumulation_steps", int, 64), ("bf16", _bool, False), ("num_train_epochs", float, 3), ("weight_decay", float, 0.01),
+               ("eval_strategy", str, "steps"), ("eval_steps", int, 25), ("save_strategy", str, "steps"), ("save_steps", int, 100),
+               ("logging_steps", int, 100), ("resume_from_checkpoint", str, None),
+               # this project's additions
+               ("device", str, "cuda:0"), ("pooling", str, "mean"), ("train_lora", int, 1), ("max_grad_norm", float, 1.0),
+               ("lora_dropout", float, 0.0))
+
+
 def build_parser():
     import argparse
     p = argparse.ArgumentParser(prog="lora_predict", description="Fine-tuned PlantCAD2 (LoRA adapter) inference on the MI355X engine")
@@ -322,6 +533,10 @@ def build_parser():
     flag(q, "hf_split", default="train")
     flag(q, "seq_column", default="sequence")
     flag(q, "label_column", default="label")
+    q = sub.add_parser("train")
+    for name, ty, default in TRAIN_FLAGS:
+        flag(q, name, type=ty, default=default, required=name in ("train_dir", "valid_dir"),
+             **({"choices": TASK_TYPES} if name == "task_type" else {}))
     for name in ("predict", "evaluate"):
         q = sub.add_parser(name)
         flag(q, "checkpoint_dir", required=True)
@@ -349,6 +564,8 @@ def main(argv: Optional[Sequence[str]] = None):
     kw = {k: v for k, v in vars(a).items() if k != "cmd"}
     if a.cmd == "tokenize":
         return tokenize(**kw)
+    if a.cmd == "train":
+        return train(**kw)
     kw["device"] = sharding.init_from_env(a.device)
     try:
         return predict(**kw) if a.cmd == "predict" else evaluate(**kw)

@@ -15,8 +15,10 @@ All tensors must be ROCm tensors; there is no CPU fallback.
 
 Differentiable (each a torch.autograd.Function on this project's backward kernels as soon as grad mode is on and an input requires
 grad; otherwise the plain call, no graph): selective_scan_fn (include/pcad_train.h), causal_conv1d_fn / causal_conv1d_dir and
-rms_norm_fn (include/pcad_bwd.h), mamba_inner_fn as a composition of those around stock F.linear, and mlm_loss_head_fn - the end of the
-masked LM's forward with labels (include/pcad_bwd.h pcad_loss_head_bwd).  plantcaduceus_amd.training composes the model from them.
+rms_norm_fn (include/pcad_bwd.h), mamba_inner_fn as a composition of those around stock F.linear, mlm_loss_head_fn - the end of the
+masked LM's forward with labels (include/pcad_bwd.h pcad_loss_head_bwd) - and pooled_head_fn, the end of the sequence classifier's
+(include/pcad_bwd.h pcad_pooled_head_bwd); lora_linear_fn is a frozen linear with LoRA factors merged in, differentiated by torch matmuls.
+plantcaduceus_amd.training composes the models from them.
 """
 from __future__ import annotations
 
@@ -1135,6 +1137,174 @@ def mlm_loss_head_fn(h, res, norm_weight, emb, complement, labels, loss_weights=
         return (sums, nll) if return_nll else sums
     sums, nll, _ = loss_head(h, res, norm_weight, emb, complement, labels, loss_weights, ignore_index, eps, B=B, L=L, want_nll=return_nll)
     return (sums, nll) if return_nll else sums
+
+
+# ---- the pooled classification head and its backward (include/pcad.h pcad_pooled_head, include/pcad_bwd.h pcad_pooled_head_bwd) ----
+POOL_BWD_SEG = 64        # csrc/kernels.hpp POOL_BWD_SEG: rows per block of the pooled head's backward (= the forward's segment)
+TRAINABLE_POOLING = ("mean", "first", "last")       # max pooling has a forward only (include/pcad_bwd.h)
+
+
+def _pooled_head_operands(h, res, norm_weight, score_w, pooling, B, L):
+    from .engine import MAX_LABELS, POOLING
+    D = h.shape[-1]
+    if pooling not in POOLING:
+        raise ValueError(f"pooling must be one of {sorted(POOLING)}, got {pooling!r}")
+    if h.numel() != 2 * B * L * D or res.numel() != 2 * B * L * D:
+        raise ValueError(f"h and res must be [2 B L, D] = [{2 * B * L}, {D}], got {tuple(h.shape)} and {tuple(res.shape)}")
+    if res.dtype != torch.float32 and res.dtype != h.dtype:
+        raise ValueError(f"res must be fp32 or h's dtype, got {res.dtype} for {h.dtype}")
+    if score_w.dim() != 2 or score_w.shape[1] != D or not 1 <= score_w.shape[0] <= MAX_LABELS:
+        raise ValueError(f"score_w must be [1..{MAX_LABELS}, {D}], got {tuple(score_w.shape)}")
+    # score_w is rounded to the model dtype here, as the score Linear's weight is stored in it
+    return h.contiguous(), res.contiguous(), norm_weight.float().contiguous(), score_w.to(h.dtype).float().contiguous(), POOLING[pooling]
+
+
+def pooled_head(h, res, norm_weight, score_w, pooling="mean", eps=1e-5, *, B: int, L: int, want_pooled: bool = False):
+    """norm_f + per-strand pooling + score + (fwd + rc) / 2 (include/pcad.h pcad_pooled_head).  h [2B*L, D], res [2B*L, D] (fp32 or
+    h.dtype), score_w [NL, D] (rounded to h.dtype here).  -> logits fp32 [B, NL], or with want_pooled (logits, pooled fp32 [B, 2, D])."""
+    _require_gpu(h, "h")
+    lib = load_library()
+    D, dev = h.shape[-1], h.device
+    hf, rf, w, W, pid = _pooled_head_operands(h, res, norm_weight, score_w, pooling, B, L)
+    NL = W.shape[0]
+    lg = torch.empty((B, NL), dtype=torch.float32, device=dev)
+    pooled = torch.empty((B, 2, D), dtype=torch.float32, device=dev) if want_pooled else None
+    nb = lib.pcad_pooled_head_scratch_bytes(B, L, D, pid)
+    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_pooled_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), W.data_ptr(), NL, pooled.data_ptr() if want_pooled else None,
+                                    lg.data_ptr(), B, L, D, float(eps), pid, None, None, _dt(hf), _DT[rf.dtype], 0, _aligned(scratch), nb,
+                                    _stream_ptr()), "pcad_pooled_head")
+    return (lg, pooled) if want_pooled else lg
+
+
+def pooled_head_bwd(h, res, norm_weight, score_w, pooled, dlogits, pooling="mean", eps=1e-5, *, B: int, L: int,
+                    want=("dh", "dres", "dnorm_weight", "dscore_w"), poison=False):
+    """pcad_pooled_head_bwd on pooled_head's operands: pooled fp32 [B, 2, D] (the forward's) and dlogits fp32 [B, NL].  want: the
+    gradients to compute; the others are passed as NULL and come back as None.
+    -> namespace(dh like h; dres like res; dnorm_weight fp32 (D); dscore_w fp32 (NL, D) - the gradient of the dtype-rounded fp32 weight;
+    guards_ok).  first / last: the rows the pooling did not read are zeros.  poison (tests): as selective_scan_bwd."""
+    from types import SimpleNamespace
+    _require_gpu(h, "h")
+    lib = load_bwd_library()
+    D, dev = h.shape[-1], h.device
+    hf, rf, w, W, pid = _pooled_head_operands(h, res, norm_weight, score_w, pooling, B, L)
+    NL = W.shape[0]
+    unknown = set(want) - {"dh", "dres", "dnorm_weight", "dscore_w"}
+    if unknown or not want:
+        raise ValueError(f"want must name some of dh, dres, dnorm_weight, dscore_w, got {tuple(want)}")
+    pl = pooled.to(dev, torch.float32).contiguous()
+    gl = dlogits.to(dev, torch.float32).contiguous()
+    if pl.numel() != B * 2 * D or gl.numel() != B * NL:
+        raise ValueError(f"pooled must be [B, 2, D] and dlogits [B, NL] = [{B}, {NL}], got {tuple(pooled.shape)} and {tuple(dlogits.shape)}")
+    rows = 2 * B * L
+    spec = {"dh": ((rows, D), hf.dtype), "dres": ((rows, D), rf.dtype), "dnorm_weight": ((D,), torch.float32), "dscore_w": ((NL, D), torch.float32)}
+    outs = {k: _guarded(sh, ty, dev, poison) for k, (sh, ty) in spec.items() if k in want}
+    nb = lib.pcad_pooled_head_bwd_scratch_bytes(B, L, D, pid)
+    scratch = _bwd_scratch(nb, dev, poison)
+    out = lambda k: outs[k][0].data_ptr() if k in outs else None
+    with torch.cuda.device(dev):
+        _check(lib.pcad_pooled_head_bwd(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), W.data_ptr(), pl.data_ptr(), gl.data_ptr(), out("dh"), out("dres"),
+                                        out("dnorm_weight"), out("dscore_w"), _aligned(scratch), nb, B, L, D, NL, float(eps), pid, _dt(hf),
+                                        _DT[rf.dtype], _stream_ptr()), "pcad_pooled_head_bwd")
+    pooled_head_bwd.last_outputs = tuple(k for k in spec if k in outs)
+    get = lambda k, shape: outs[k][0].view(shape) if k in outs else None
+    return SimpleNamespace(dh=get("dh", h.shape), dres=get("dres", res.shape), dnorm_weight=get("dnorm_weight", (D,)),
+                           dscore_w=get("dscore_w", (NL, D)), guards_ok=_sentinels_intact(list(outs.values())))
+
+
+pooled_head_bwd.last_outputs = ()    # the output set of the latest call (tests: a gradient nobody needs is not computed)
+
+
+class _PooledHeadFn(torch.autograd.Function):
+    """pooled_head with a backward: pcad_pooled_head_bwd (include/pcad_bwd.h, libpcad_bwd.so).  norm_weight and score_w arrive in fp32
+    (the casts are torch ops outside).  score_w arrives UNROUNDED: forward and backward round it to the model dtype themselves (the
+    wrappers' operand step), and dscore_w is returned as the kernel wrote it - the rounding is the identity in the derivative, where a
+    torch cast pair outside would round the fp32 gradient to the model dtype on its way back.  Saved: the inputs and the forward's
+    pooled_out."""
+
+    @staticmethod
+    def forward(ctx, h, res, norm_weight, score_w, pooling, eps, B, L):
+        lg, pooled = pooled_head(h, res, norm_weight, score_w, pooling, eps, B=B, L=L, want_pooled=True)
+        ctx.save_for_backward(h, res, norm_weight, score_w, pooled)
+        ctx.args = (pooling, float(eps), int(B), int(L))
+        return lg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        h, res, norm_weight, score_w, pooled = ctx.saved_tensors
+        pooling, eps, B, L = ctx.args
+        want = tuple(k for k, n in zip(("dh", "dres", "dnorm_weight", "dscore_w"), ctx.needs_input_grad[:4]) if n)
+        if not want:
+            return (None,) * 8
+        g = pooled_head_bwd(h, res, norm_weight, score_w, pooled, dlogits, pooling, eps, B=B, L=L, want=want)
+        return (g.dh, g.dres, g.dnorm_weight, g.dscore_w) + (None,) * 4
+
+
+def pooled_head_fn(h, res, norm_weight, score_w, pooling="mean", eps=1e-5, B: Optional[int] = None, L: Optional[int] = None):
+    """The end of CaduceusForSequenceClassification's forward - norm_f, the per-strand pooling, the score head and the strand average -
+    on the 2B-strand rows h, res [2B, L, D] (or [2B*L, D] with B=, L=).  -> logits fp32 [B, NL].
+    With grad mode on and one of h, res, norm_weight, score_w requiring grad the call is differentiable (pcad_pooled_head_bwd): each
+    gradient comes back in its input's shape and dtype (an fp32 score_w's is the kernel's fp32 dscore_w, straight through the rounding
+    of score_w to the model dtype), gradients nobody
+    needs are not computed, and max pooling is refused.  Otherwise it is the plain forward call."""
+    _require_gpu(h, "h")
+    if B is None or L is None:
+        if h.dim() != 3:
+            raise ValueError("h must be [2B, L, D], or [2B*L, D] with B= and L=")
+        B, L = h.shape[0] // 2, h.shape[1]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (h, res, norm_weight, score_w)):
+        if pooling not in TRAINABLE_POOLING:
+            raise NotImplementedError(f"pooling {pooling!r} has no backward (include/pcad_bwd.h): trainable poolings are {TRAINABLE_POOLING}")
+        # the casts to fp32 stay torch ops outside the Function, so that autograd returns each gradient in its input's dtype; the rounding
+        # of score_w to the model dtype happens inside it, so that an fp32 score_w receives the kernel's fp32 dscore_w bit for bit
+        return _PooledHeadFn.apply(h, res, norm_weight.float(), score_w.float(), pooling, float(eps), B, L)
+    return pooled_head(h, res, norm_weight, score_w, pooling, eps, B=B, L=L)
+
+
+def _lora_merged(W, A, B, scale, dtype):
+    """(W + scale B A) formed in fp32 (in float64 where the factors are float64: the CPU checks) and cast once to `dtype`"""
+    acc = torch.promote_types(torch.float32, A.dtype)
+    return (W.to(acc) + float(scale) * (B.to(acc) @ A.to(acc))).to(dtype)
+
+
+class _LoraLinearFn(torch.autograd.Function):
+    """y = x W_eff^T with W_eff = round(W + scale B A) in x's dtype: the merged form (adapters.merge_lora's arithmetic).  The backward
+    never forms dW [N, K]: dx = dy W_eff, dB = scale dy^T (x A^T), dA = scale (dy B)^T x - rank-r GEMMs of stock PyTorch.  The rounding
+    of W_eff is the identity in the derivative; W itself gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, W, A, B, scale):
+        w_eff = _lora_merged(W, A, B, scale, x.dtype)
+        ctx.save_for_backward(x, w_eff, A, B)
+        ctx.scale = float(scale)
+        return F.linear(x, w_eff)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w_eff, A, B = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx = dA = dB = None
+        if need[0]:
+            dx = dy @ w_eff
+        if need[2] or need[3]:
+            x2, g2 = x.reshape(-1, x.shape[-1]).to(A.dtype), dy.reshape(-1, dy.shape[-1]).to(A.dtype)
+            if need[3]:
+                dB = (ctx.scale * (g2.t() @ (x2 @ A.t()))).to(B.dtype)
+            if need[2]:
+                dA = (ctx.scale * ((g2 @ B).t() @ x2)).to(A.dtype)
+        return dx, None, dA, dB, None
+
+
+def lora_linear_fn(x, W, A, B, scale):
+    """F.linear(x, (W.float() + scale * B @ A).to(x.dtype)): a frozen linear W [N, K] with the LoRA factors A [r, K], B [N, r] merged into
+    it - the arithmetic of adapters.merge_lora, and so of inference with lora_deltas="apply".  A and B are fp32 whatever x's dtype.
+    Differentiable in x, A and B through `_LoraLinearFn` (W gets no gradient); tensors on any device."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, A, B)):
+        return _LoraLinearFn.apply(x, W, A, B, float(scale))
+    return F.linear(x, _lora_merged(W, A, B, scale, x.dtype))
 
 
 # ---- the optimizer step (include/pcad_bwd.h pcad_optim_plan / pcad_adamw_step / pcad_zero_grads; DESIGN.md §4o) ---------------------

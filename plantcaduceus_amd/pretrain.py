@@ -76,20 +76,16 @@ def steps_per_epoch(n_windows: int, batch: int, accumulation: int) -> int:
     return max(1, math.ceil(n_windows / batch) // accumulation)
 
 
-class BatchSource:
-    """The micro-batches of every optimizer step, a function of (seed, data, batch, accumulation) and of how many micro-batches were
-    drawn before: window order from a generator seeded by (seed, epoch), masks from the collator on a CPU generator of its own."""
+class WindowOrder:
+    """Which windows make up each micro-batch of every optimizer step, a function of (seed, n, batch, accumulation): the order of
+    epoch e is `torch.randperm(n)` from a generator seeded by (seed, e).  Shared with `lora_predict train`."""
 
-    def __init__(self, ids: np.ndarray, special: np.ndarray, weights: np.ndarray, collator, batch: int, accumulation: int, seed: int):
-        self.ids, self.special, self.weights = ids, special, weights
-        self.collator, self.batch, self.accumulation, self.seed = collator, int(batch), int(accumulation), int(seed)
-        self.n = ids.shape[0]
+    def __init__(self, n: int, batch: int, accumulation: int, seed: int):
+        self.n, self.batch, self.accumulation, self.seed = int(n), int(batch), int(accumulation), int(seed)
         if self.n == 0:
             raise ValueError("no training windows")
         self.steps_per_epoch = steps_per_epoch(self.n, self.batch, self.accumulation)
-        self.mask_generator = torch.Generator().manual_seed(self.seed)
         self.order_generator = torch.Generator()
-        self.collator.generator = self.mask_generator
         self._epoch, self._order = None, None
 
     def order(self, epoch: int) -> torch.Tensor:
@@ -108,6 +104,17 @@ class BatchSource:
             if lo < self.n:
                 out.append(order[lo:lo + self.batch])
         return out
+
+
+class BatchSource(WindowOrder):
+    """The micro-batches of every optimizer step, a function of (seed, data, batch, accumulation) and of how many micro-batches were
+    drawn before: window order from a generator seeded by (seed, epoch), masks from the collator on a CPU generator of its own."""
+
+    def __init__(self, ids: np.ndarray, special: np.ndarray, weights: np.ndarray, collator, batch: int, accumulation: int, seed: int):
+        super().__init__(ids.shape[0], batch, accumulation, seed)
+        self.ids, self.special, self.weights, self.collator = ids, special, weights, collator
+        self.mask_generator = torch.Generator().manual_seed(self.seed)
+        self.collator.generator = self.mask_generator
 
     def step_batches(self, step: int):
         """-> [(masked input_ids int32 [b, L], labels int32 [b, L], loss_weights fp32 [b, L])] CPU tensors; advances the mask generator"""
@@ -274,9 +281,13 @@ class Trainer:
         _write_json(os.path.join(path, "trainer_state.json"), self.trainer_state())
         return path
 
+    def restore_inputs(self, path: str):
+        """what a checkpoint holds beside the optimizer's and the trainer's state: here the mask generator's state"""
+        self.source.load_state(torch.load(os.path.join(path, "rng_state.pt"), weights_only=False))
+
     def resume(self, path: str):
         self.opt.load_state_dict(torch.load(os.path.join(path, "optimizer.pt"), weights_only=False))
-        self.source.load_state(torch.load(os.path.join(path, "rng_state.pt"), weights_only=False))
+        self.restore_inputs(path)
         with open(os.path.join(path, "trainer_state.json")) as f:
             ts = json.load(f)
         self.step, self.log_history, self.window_steps = int(ts["global_step"]), list(ts["log_history"]), int(ts["window_steps"])

@@ -12,7 +12,22 @@
 The module tree is `modeling_caduceus`'s parameter holders, so `state_dict()` has the reference's key names and loads into
 `CaduceusForMaskedLM` (and a snapshot of it loads here); the ties are shared storage.  There is no CPU path, and no gradient
 checkpointing or LoRA wrapping here: autograd keeps, per layer, what the operators save (DESIGN.md §4n lists it).  The optimizer is
-`plantcaduceus_amd.optim.AdamW`, the training command `plantcaduceus_amd.pretrain`."""
+`plantcaduceus_amd.optim.AdamW`, the training command `plantcaduceus_amd.pretrain`.
+
+`TrainableCaduceusForSequenceClassification` is the fine-tuning form: the same trunk frozen, one LoRA factor pair per
+(layer, direction, target module), a trained `score` head, and the pooled head's backward kernel (`ops.pooled_head_fn`).  The
+per-direction in_proj / out_proj factors untie the two directions, so its block is composed here from the single operators:
+
+    per layer   hn, res = ops.rms_norm_fn(h, norm.weight, residual=res, prenorm=True)
+      per direction d   xz  = ops.lora_linear_fn(hn, in_proj_d)            x, z = xz halves
+                        xc  = ops.causal_conv1d_dir(x, conv_d, reverse=d)
+                        xdb = ops.lora_linear_fn(xc, x_proj_d)             delta = F.linear(xdb[:R], dt_proj_d)
+                        y   = ops.selective_scan_fn(xc, delta, A_d, B, C, D_d, z, dt_bias_d, reverse=d)
+                        o_d = ops.lora_linear_fn(y, out_proj_d)
+                h = o_fwd + o_rev
+    logits = ops.pooled_head_fn(h, res, norm_f.weight, score, pooling)     loss: HF's, by problem_type, in torch on the fp32 logits
+
+`save_adapter` writes PEFT's layout (plantcaduceus_amd.adapters); the training command is `plantcaduceus_amd.lora_predict train`."""
 from __future__ import annotations
 
 import json
@@ -28,7 +43,7 @@ from . import ops
 from .checkpoint import load_state_dict, resolve_snapshot
 from .configuration_caduceus import CaduceusConfig, config_from_dict
 from .engine import _DT, _require_gpu
-from .modeling_caduceus import _LMHead, _MixerModel
+from .modeling_caduceus import _LMHead, _MixerModel, _Weight
 
 
 @dataclass
@@ -116,3 +131,177 @@ class TrainableCaduceusForMaskedLM(nn.Module):
         return ops.mamba_inner_fn(xz, m.conv1d.weight, m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.out_proj.weight, None,
                                   -torch.exp(m.A_log.float()), None, None, D=m.D.float(), delta_bias=m.dt_proj.bias.float(),
                                   delta_softplus=True, reverse=reverse)
+
+
+# ---- fine-tuning: frozen trunk + LoRA factors + score -----------------------------------------------------------------
+PROBLEM_TYPES = ("regression", "single_label_classification", "multi_label_classification")
+ADAPTER_PREFIX = "base_model.model."
+
+
+@dataclass
+class SequenceClassificationTrainingOutput:
+    loss: Optional[torch.Tensor]     # scalar (labels given): HF's loss by problem_type on the fp32 logits, differentiable
+    logits: torch.Tensor             # fp32 [B, num_labels]
+
+
+def sequence_classification_loss(logits: torch.Tensor, labels: torch.Tensor, problem_type: str, num_labels: int) -> torch.Tensor:
+    """HF's loss of `*ForSequenceClassification` (CaduceusForSequenceClassification.loss_from_logits with gradients): MSE on the
+    squeezed logits, cross-entropy, or BCE-with-logits"""
+    labels = labels.to(logits.device)
+    if problem_type == "regression":
+        if num_labels == 1:
+            return F.mse_loss(logits.squeeze(), labels.squeeze().to(logits.dtype))
+        return F.mse_loss(logits, labels.to(logits.dtype))
+    if problem_type == "single_label_classification":
+        return F.cross_entropy(logits.view(-1, num_labels), labels.view(-1).long())
+    return F.binary_cross_entropy_with_logits(logits, labels.to(logits.dtype))
+
+
+class TrainableCaduceusForSequenceClassification(nn.Module):
+    """The trunk under the reference's key names, frozen; `lora_A` / `lora_B` fp32 parameters per (layer, direction, target module)
+    under PEFT's names (`...mamba_fwd.in_proj.lora_A.weight`), initialised as PEFT does (A: kaiming_uniform(a=sqrt(5)) = U(+-1/sqrt(in)),
+    B: 0); `score.weight` fp32 [num_labels, d_model], initialised as nn.Linear, handed to the kernel rounded to the model dtype with a
+    straight-through gradient.  The weights the factors merge into are kept in fp32 whatever the model dtype, so that the merged weight
+    is rounded once (adapters.merge_lora).  train_lora=False: the factors exist but do not require grad - the frozen-trunk mode, which
+    is what the reference's pinned fast path trains.  lora_dropout is 0.
+    `forward(input_ids, labels=None)` -> `.loss`, `.logits`."""
+
+    def __init__(self, config: CaduceusConfig, num_labels: int, problem_type: str, pooling_strategy: str = "mean",
+                 dtype: torch.dtype = torch.float32, device="cuda", r: int = 8, lora_alpha: float = 32,
+                 target_modules=("x_proj", "in_proj", "out_proj"), train_lora: bool = True, seed: int = 0):
+        super().__init__()
+        from .adapters import TARGETS
+        if dtype not in _DT:
+            raise ValueError(f"unsupported dtype {dtype}: the kernels compute in bf16 or fp32")
+        config.check_supported()
+        if not getattr(config, "bidirectional_weight_tie", True):
+            raise NotImplementedError("bidirectional_weight_tie=False: the trainable model starts from the tied form only")
+        if pooling_strategy not in ops.TRAINABLE_POOLING:
+            raise NotImplementedError(f"pooling_strategy {pooling_strategy!r} has no backward: trainable poolings are {ops.TRAINABLE_POOLING} "
+                                      "(the gradient of max pooling needs a tie rule nothing pins; inference keeps it)")
+        if problem_type not in PROBLEM_TYPES:
+            raise ValueError(f"problem_type must be one of {PROBLEM_TYPES}, got {problem_type!r}")
+        bad = [t for t in target_modules if t not in TARGETS]
+        if bad or int(r) < 1 or int(num_labels) < 1:
+            raise ValueError(f"target_modules must be among {TARGETS}, r and num_labels >= 1 (got {list(target_modules)}, r={r}, num_labels={num_labels})")
+        self.config, self.num_labels, self.problem_type, self.pooling_strategy = config, int(num_labels), problem_type, pooling_strategy
+        self.dtype, self.r, self.lora_alpha, self.train_lora = dtype, int(r), float(lora_alpha), bool(train_lora)
+        self.target_modules = tuple(sorted(target_modules))
+        self.caduceus = _Backbone(config)
+        self.to(dtype=dtype)
+        g = torch.Generator().manual_seed(int(seed))            # the factors' and the head's initial values
+        for blk in self.caduceus.backbone.layers:
+            for m in (blk.mixer.submodule.mamba_fwd, blk.mixer.submodule.mamba_rev):
+                for mod in TARGETS:
+                    holder = getattr(m, mod)
+                    holder.weight.data = holder.weight.data.float()          # the tied pair is one Parameter: converted once, shared still
+                    if mod in self.target_modules:
+                        out_f, in_f = holder.weight.shape
+                        holder.lora_A = _Weight(self.r, in_f)
+                        holder.lora_B = _Weight(out_f, self.r)
+                        with torch.no_grad():
+                            holder.lora_A.weight.copy_((torch.rand((self.r, in_f), generator=g) * 2 - 1) / in_f ** 0.5)
+                            holder.lora_B.weight.zero_()
+        self.score = _Weight(self.num_labels, config.d_model)
+        with torch.no_grad():                                                # nn.Linear's reset_parameters: U(+-1/sqrt(in))
+            self.score.weight.copy_((torch.rand((self.num_labels, config.d_model), generator=g) * 2 - 1) / config.d_model ** 0.5)
+        self.to(device=device)
+        for name, p in self.named_parameters():
+            p.requires_grad_(name == "score.weight" or (self.train_lora and ".lora_" in name))
+
+    @classmethod
+    def from_pretrained(cls, base_snapshot, num_labels: int, problem_type: str, **kwargs):
+        """The trunk from a base snapshot directory or hub id (config.json + weights under the reference's key names)."""
+        hub_kw = {k: kwargs.pop(k) for k in ("revision", "cache_dir", "local_files_only", "token") if k in kwargs}
+        path = resolve_snapshot(base_snapshot, **hub_kw)
+        with open(os.path.join(path, "config.json")) as f:
+            config = config_from_dict(json.load(f))
+        model = cls(config, num_labels, problem_type, **kwargs)
+        model.load_trunk({k: v for k, v in load_state_dict(path).items() if k.startswith("caduceus.")})
+        return model
+
+    def load_trunk(self, sd):
+        """the frozen trunk's tensors (reference key names); factors and score are left as they are"""
+        missing, unexpected = self.load_state_dict(sd, strict=False)
+        missing = [k for k in missing if ".lora_" not in k and k != "score.weight"]
+        if missing or unexpected:
+            raise ValueError(f"trunk state dict does not fit: missing {missing[:4]}, unexpected {list(unexpected)[:4]}")
+
+    def adapter_state_dict(self):
+        """PEFT's adapter tensors: every factor and the score head under `base_model.model.`, fp32 on the CPU"""
+        return {ADAPTER_PREFIX + k: p.detach().to("cpu", torch.float32).contiguous() for k, p in self.named_parameters()
+                if ".lora_" in k or k == "score.weight"}
+
+    def save_adapter(self, path: str, base_model_name_or_path: Optional[str]):
+        """adapter_config.json + adapter_model.safetensors in the layout adapters.audit_adapter accepts"""
+        from safetensors.torch import save_file
+        from .adapters import ADAPTER_CONFIG
+        os.makedirs(path, exist_ok=True)
+        cfg = {"base_model_name_or_path": base_model_name_or_path, "r": self.r,
+               "lora_alpha": int(self.lora_alpha) if float(self.lora_alpha).is_integer() else self.lora_alpha, "lora_dropout": 0.0,
+               "target_modules": list(self.target_modules), "task_type": "SEQ_CLS", "modules_to_save": ["classifier", "score"],
+               "peft_type": "LORA", "bias": "none", "inference_mode": True}
+        with open(os.path.join(path, ADAPTER_CONFIG), "w") as f:
+            json.dump(cfg, f, indent=2)
+        save_file(self.adapter_state_dict(), os.path.join(path, "adapter_model.safetensors"), metadata={"format": "pt"})
+
+    def load_adapter_weights(self, path: str):
+        """read `save_adapter`'s directory back into the factors and the score head (audited against this model's r and targets)"""
+        from .adapters import audit_adapter, read_adapter_config, read_adapter_weights
+        cfg = read_adapter_config(path)
+        if cfg["r"] != self.r or float(cfg["lora_alpha"]) != self.lora_alpha or tuple(cfg["target_modules"]) != self.target_modules:
+            raise ValueError(f"{path}: r / lora_alpha / target_modules {cfg['r']} / {cfg['lora_alpha']} / {cfg['target_modules']} are not this "
+                             f"model's {self.r} / {self.lora_alpha} / {list(self.target_modules)}")
+        sd = read_adapter_weights(path)
+        audit_adapter(sd, cfg, n_layer=self.config.n_layer, d_model=self.config.d_model)
+        own = dict(self.named_parameters())
+        want = {k for k in own if ".lora_" in k or k == "score.weight"}
+        got = {k[len(ADAPTER_PREFIX):] if k.startswith(ADAPTER_PREFIX) else k: v for k, v in sd.items()}
+        if set(got) != want:
+            raise ValueError(f"{path}: adapter tensors do not match this model's (e.g. {sorted(set(got) ^ want)[:3]})")
+        with torch.no_grad():
+            for k, v in got.items():
+                if tuple(v.shape) != tuple(own[k].shape):
+                    raise ValueError(f"{path}: {k} has shape {tuple(v.shape)}, expected {tuple(own[k].shape)}")
+                own[k].copy_(v)
+
+    def loss_from_logits(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """CaduceusForSequenceClassification.loss_from_logits: the loss without gradient (lora_predict.eval_loss calls it per batch)"""
+        with torch.no_grad():
+            return sequence_classification_loss(logits, labels, self.problem_type, self.num_labels)
+
+    def _linear(self, x, holder):
+        if hasattr(holder, "lora_A"):
+            return ops.lora_linear_fn(x, holder.weight, holder.lora_A.weight, holder.lora_B.weight, self.lora_alpha / self.r)
+        return F.linear(x, holder.weight.to(x.dtype))
+
+    def _direction(self, hn, m, reverse: bool):
+        E, R, dt = self.config.d_inner, self.config.dt_rank, hn.dtype
+        xz = self._linear(hn, m.in_proj)                                                         # (2B, L, 2E)
+        xc = ops.causal_conv1d_dir(xz[..., :E], m.conv1d.weight.reshape(E, -1), m.conv1d.bias, reverse)
+        x_dbl = self._linear(xc, m.x_proj)                                                       # (2B, L, R + 32)
+        delta = F.linear(x_dbl[..., :R], m.dt_proj.weight.to(dt)).transpose(1, 2)                # (2B, E, L)
+        y = ops.selective_scan_fn(xc.transpose(1, 2), delta, -torch.exp(m.A_log.float()), x_dbl[..., R:R + 16].transpose(1, 2),
+                                  x_dbl[..., R + 16:].transpose(1, 2), m.D.float(), z=xz[..., E:].transpose(1, 2),
+                                  delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse)
+        return self._linear(y.transpose(1, 2), m.out_proj)
+
+    def forward(self, input_ids, labels=None) -> SequenceClassificationTrainingOutput:
+        cfg = self.config
+        emb = self.caduceus.backbone.embeddings.word_embeddings.embedding.weight
+        _require_gpu(emb, "the model")
+        _require_gpu(input_ids, "input_ids")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, L], got {tuple(input_ids.shape)}")
+        comp = torch.tensor(cfg.complement_list()[:8], dtype=torch.long, device=emb.device)
+        ids = input_ids.long()
+        strands = torch.cat([ids, comp[ids.flip(1)]], dim=0)                                     # [2B, L]
+        h, res = F.embedding(strands, emb), None
+        eps = cfg.norm_epsilon
+        for blk in self.caduceus.backbone.layers:
+            hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, eps, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
+            bi = blk.mixer.submodule
+            h = self._direction(hn, bi.mamba_fwd, False) + self._direction(hn, bi.mamba_rev, True)
+        logits = ops.pooled_head_fn(h, res, self.caduceus.backbone.norm_f.weight, self.score.weight, self.pooling_strategy, eps)
+        loss = sequence_classification_loss(logits, labels, self.problem_type, self.num_labels) if labels is not None else None
+        return SequenceClassificationTrainingOutput(loss=loss, logits=logits)
