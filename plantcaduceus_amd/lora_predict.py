@@ -19,6 +19,9 @@ bf16 trunk and kernels with fp32 factors and score; `save_total_limit` is 5.  Ad
 (0: the frozen-trunk mode), `--max_grad_norm` (1.0) and `--lora_dropout` (0.0; any other value is refused, as is `--use_wandb`).
 `output_dir/checkpoint-<step>/` is an adapter directory plus `optimizer.pt` and `trainer_state.json`; `output_dir/` ends as the final
 adapter, which `predict --checkpoint_dir <output_dir> --lora-deltas apply` loads (after `--train_lora 0`: the default `auto`).
+Whether the blocks' activations are kept or recomputed in the backward (the same bits either way) is `recompute_policy`'s
+choice, logged at the start: the environment variable PCAD_TRAIN_RECOMPUTE=1 / 0 forces it, unset or `auto` recomputes when the formula's
+stored bytes for a micro-batch exceed half of the device's free memory.  The command has no flag for it: the flag set is the reference's.
 
 Under torchrun the windows are sharded over the ranks (plantcad2_eval._sharded_rows); rank 0 writes / prints.  Metrics are
 computed on the host without sklearn (the reference's compute_metrics_* :517-563 restated; pinned against sklearn / scipy in
@@ -414,6 +417,25 @@ def predict_logits_trainable(model, ids: np.ndarray, device: str, batch_size: in
     return torch.cat(parts, dim=0).float().cpu().numpy() if parts else np.zeros((0, model.num_labels), dtype=np.float32)
 
 
+RECOMPUTE_ENV = "PCAD_TRAIN_RECOMPUTE"
+
+
+def recompute_policy(bytes_per_window: int, batch: int, free_bytes: int, env=None, train_lora: bool = True) -> bool:
+    """Whether `train` recomputes each block in the backward (training's gradient_checkpointing).  `env` is the process
+    environment (a mapping; os.environ when None): PCAD_TRAIN_RECOMPUTE=1 forces it on, =0 off; unset or `auto` turns it on exactly when
+    the factors train and a micro-batch's stored activations, batch * bytes_per_window by the formula
+    (bytes_per_window = 2 L * training.stored_bytes_per_strand_position), exceed half of the device's free bytes.  The half is room for
+    what the formula leaves out (the merged weights, the operators' own copies, the allocator's slack): a stated policy, not a measured
+    threshold.  Gradients are bit-equal either way, so the choice changes no result."""
+    val = env if isinstance(env, str) else (os.environ if env is None else env).get(RECOMPUTE_ENV, "auto")     # a bare value is taken too
+    val = str(val).strip().lower() or "auto"
+    if val not in ("0", "1", "auto"):
+        raise ValueError(f"{RECOMPUTE_ENV} must be 0, 1 or auto, got {val!r}")
+    if val != "auto":
+        return val == "1"
+    return bool(train_lora) and int(batch) * int(bytes_per_window) > int(free_bytes) / 2
+
+
 def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", model_name: Optional[str] = None,
           task_type: str = "classification", num_labels: Optional[int] = None, train_batch_size: int = 43, eval_batch_size: int = 3,
           eval_num_samples: Optional[int] = 0, max_steps: int = 500, seed: int = 42, use_wandb: bool = False, learning_rate: float = 1e-3,
@@ -426,7 +448,7 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     from types import SimpleNamespace
     from .adapters import TASKS
     from .optim import AdamW
-    from .training import TrainableCaduceusForSequenceClassification
+    from .training import TrainableCaduceusForSequenceClassification, stored_bytes_per_strand_position
     if model_name is None:
         raise SystemExit("--model_name is required")
     if task_type not in TASK_TYPES:
@@ -462,6 +484,13 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     model = TrainableCaduceusForSequenceClassification.from_pretrained(
         model_name, nl, problem_type, pooling_strategy=pooling, dtype=torch.bfloat16 if bf16 else torch.float32, device=device,
         train_lora=bool(int(train_lora)), seed=seed)
+    per_window = 2 * ids.shape[1] * stored_bytes_per_strand_position(model.config, model.dtype, lora=True)
+    free_bytes = torch.cuda.mem_get_info(device)[0]
+    if recompute_policy(per_window, train_batch_size, free_bytes, os.environ, model.train_lora):
+        model.gradient_checkpointing_enable()
+    logger.info("Recompute blocks in the backward (%s=%s): %s; stored activations by the formula %d bytes per micro-batch (%d windows), "
+                "%d bytes free on %s", RECOMPUTE_ENV, os.environ.get(RECOMPUTE_ENV, "auto"), "on" if model.is_gradient_checkpointing else "off",
+                train_batch_size * per_window, train_batch_size, free_bytes, device)
     n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
     n_all = sum(p.numel() for p in model.parameters())
     logger.info("Trainable parameters: %d of %d (%.2f%%)", n_train, n_all, 100.0 * n_train / n_all)

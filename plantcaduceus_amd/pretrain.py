@@ -8,7 +8,8 @@ the fused AdamW step of `optim.AdamW`.  Single process, o
         --adam_beta1 0.9 --adam_beta2 0.999 --adam_epsilon 1e-8 --max_grad_norm 1.0 \\
         --num_train_epochs 3 | --max_steps N  --lr_scheduler_type linear|cosine|constant|constant_with_warmup \\
         --warmup_steps K | --warmup_ratio R  --mlm_probability 0.15 --soft_masked_loss_weights_train 1.0 \\
-        --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16
+        --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16 \\
+        [--gradient_checkpointing]
 
 Flag names and defaults are `transformers.TrainingArguments`' and `HF_pre_train.py`'s.  `--config_name` alone starts from scratch:
 `checkpoint.synthetic_state_dict(config, seed=--seed, stress=False)`, the Mamba-style initialisation.
@@ -33,7 +34,8 @@ learning_rate, grad_norm and skipped_steps).  `--resume_from_checkpoint` continu
 Departures from the reference, all stated in DESIGN.md §4o: a step whose gradient norm is not finite is skipped and counted instead
 of letting NaNs into the weights; weight decay leaves out `A_log` and `D` beside biases and norm weights; `--dtype bfloat16` means
 bf16 parameters and kernels with fp32 master weights in the optimizer, where the reference's `bf16=True` is autocast around fp32
-parameters.  Not built: DDP / torchrun, LoRA training, activation checkpointing."""
+parameters.  `--gradient_checkpointing` (`TrainingArguments`' name and default) keeps only each block's inputs and runs the block again in
+the backward: the same bits for about an eighth of the stored activations.  Not built: DDP / torchrun."""
 from __future__ import annotations
 
 import json
@@ -167,6 +169,8 @@ def build_parser():
     p.add_argument("--save_steps", type=int, default=500)
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--resume_from_checkpoint", default=None)
+    p.add_argument("--gradient_checkpointing", action="store_true",
+                   help="keep only each block's inputs and run its forward again in the backward (DESIGN.md §4q): same bits, less memory")
     p.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
     p.add_argument("--device", default="cuda:0")
     return p
@@ -190,14 +194,15 @@ def build_model(a, dtype: torch.dtype, source: Optional[str] = None):
     from .configuration_caduceus import config_from_dict
     from .training import TrainableCaduceusForMaskedLM
     path = source or a.model_name_or_path
+    recompute = bool(getattr(a, "gradient_checkpointing", False))
     if path:
-        return TrainableCaduceusForMaskedLM.from_pretrained(path, dtype=dtype, device=a.device)
+        return TrainableCaduceusForMaskedLM.from_pretrained(path, dtype=dtype, device=a.device, gradient_checkpointing=recompute)
     if not a.config_name:
         raise SystemExit("pass --model_name_or_path or --config_name")
     cfg_path = os.path.join(a.config_name, "config.json") if os.path.isdir(a.config_name) else a.config_name
     with open(cfg_path) as f:
         cfg = config_from_dict(json.load(f))
-    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device)
+    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device, gradient_checkpointing=recompute)
     model.load_state_dict(synthetic_state_dict(cfg, seed=a.seed, stress=False))
     return model
 

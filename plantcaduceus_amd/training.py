@@ -10,9 +10,10 @@
     loss = sums[:, 0].sum() / sums[:, 1].sum()
 
 The module tree is `modeling_caduceus`'s parameter holders, so `state_dict()` has the reference's key names and loads into
-`CaduceusForMaskedLM` (and a snapshot of it loads here); the ties are shared storage.  There is no CPU path, and no gradient
-checkpointing or LoRA wrapping here: autograd keeps, per layer, what the operators save (DESIGN.md §4n lists it).  The optimizer is
-`plantcaduceus_amd.optim.AdamW`, the training command `plantcaduceus_amd.pretrain`.
+`CaduceusForMaskedLM` (and a snapshot of it loads here); the ties are shared storage.  There is no CPU path.  By default autograd
+keeps, per layer, what the operators save (DESIGN.md §4n lists it); with `gradient_checkpointing=True` each block keeps only its
+inputs `h` and `res` and its forward is run again inside the backward, on the same operators and to the same bits.
+The optimizer is `plantcaduceus_amd.optim.AdamW`, the training command `plantcaduceus_amd.pretrain`.
 
 `TrainableCaduceusForSequenceClassification` is the fine-tuning form: the same trunk frozen, one LoRA factor pair per
 (layer, direction, target module), a trained `score` head, and the pooled head's backward kernel (`ops.pooled_head_fn`).  The
@@ -38,6 +39,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.utils.checkpoint import checkpoint
 
 from . import ops
 from .checkpoint import load_state_dict, resolve_snapshot
@@ -59,11 +61,49 @@ class _Backbone(nn.Module):
         self.backbone = _MixerModel(cfg)
 
 
-class TrainableCaduceusForMaskedLM(nn.Module):
-    """`TrainableCaduceusForMaskedLM(config, dtype=torch.float32, device="cuda")`: parameters under the reference's names with
-    requires_grad=True; `forward(input_ids, labels, loss_weights=None)` -> `.loss`, `.sums` (and `.token_nll` with return_token_nll=True)."""
+def stored_bytes_per_strand_position(config, dtype: torch.dtype, *, lora: bool, gradient_checkpointing: bool = False) -> int:
+    """Bytes autograd keeps per strand position for the whole depth, by the formulas of DESIGN.md: per layer
+    ((2D + 8E)e + D r) for the masked LM (§4n), ((2D + 10E + 2(R + 32))e + D r) for the LoRA model (§4p); e is the model dtype's size,
+    r the residual's (4 with residual_in_fp32 or an fp32 model).  With gradient_checkpointing each layer keeps its inputs, D(e + r),
+    and one block at a time is live in the plain form (§4q).  Host arithmetic: a window of length L has 2L strand positions."""
+    if dtype not in _DT:
+        raise ValueError(f"unsupported dtype {dtype}: the kernels compute in bf16 or fp32")
+    D, E, R, n = int(config.d_model), int(config.d_inner), int(config.dt_rank), int(config.n_layer)
+    e = torch.empty((), dtype=dtype).element_size()
+    r = 4 if (config.residual_in_fp32 or dtype == torch.float32) else e
+    plain = ((2 * D + 10 * E + 2 * (R + 32)) * e if lora else (2 * D + 8 * E) * e) + D * r
+    return n * D * (e + r) + plain if gradient_checkpointing else n * plain
 
-    def __init__(self, config: CaduceusConfig, dtype: torch.dtype = torch.float32, device="cuda"):
+
+class _Recompute:
+    """What both trainable models share: the switch, and running a block as one checkpointed unit.  A unit goes through
+    torch.utils.checkpoint's saved-tensor hooks (use_reentrant=False): its forward runs once in grad mode - the composed form of the
+    operators, whose bits the plain model produces - and keeps only the unit's arguments; the first gradient that reaches the unit
+    runs the forward again from them and hands the autograd nodes of the first pass the tensors they saved.  Every Function of `ops`
+    saves through save_for_backward, so nothing escapes the hooks.  With grad mode off, or with nothing in or before the unit requiring
+    grad, no operator saves anything and nothing is run twice."""
+
+    is_gradient_checkpointing = False
+
+    def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
+        if gradient_checkpointing_kwargs:
+            raise NotImplementedError("gradient_checkpointing_kwargs: the units are fixed (one block each, DESIGN.md §4q)")
+        self.is_gradient_checkpointing = True
+
+    def gradient_checkpointing_disable(self):
+        self.is_gradient_checkpointing = False
+
+    def _run_block(self, blk, h, res):
+        if self.is_gradient_checkpointing and torch.is_grad_enabled():
+            return checkpoint(self._block, blk, h, res, use_reentrant=False, preserve_rng_state=False)
+        return self._block(blk, h, res)
+
+
+class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
+    """`TrainableCaduceusForMaskedLM(config, dtype=torch.float32, device="cuda", gradient_checkpointing=False)`: parameters under the
+    reference's names with requires_grad=True; `forward(input_ids, labels, loss_weights=None)` -> `.loss`, `.sums` (and `.token_nll` with return_token_nll=True)."""
+
+    def __init__(self, config: CaduceusConfig, dtype: torch.dtype = torch.float32, device="cuda", gradient_checkpointing: bool = False):
         super().__init__()
         if dtype not in _DT:
             raise ValueError(f"unsupported dtype {dtype}: the kernels compute in bf16 or fp32")
@@ -73,6 +113,7 @@ class TrainableCaduceusForMaskedLM(nn.Module):
         if config.padded_vocab_size != 8:
             raise NotImplementedError(f"padded vocabulary of {config.padded_vocab_size} rows: the loss head evaluates 8")
         self.config = config
+        self.is_gradient_checkpointing = bool(gradient_checkpointing)
         self.caduceus = _Backbone(config)
         self.lm_head = _LMHead(config)
         self.tie_weights()
@@ -85,7 +126,8 @@ class TrainableCaduceusForMaskedLM(nn.Module):
         self.lm_head.lm_head.weight = self.caduceus.backbone.embeddings.word_embeddings.embedding.weight
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, config=None, torch_dtype=None, dtype=None, device="cuda", **kwargs):
+    def from_pretrained(cls, pretrained_model_name_or_path, config=None, torch_dtype=None, dtype=None, device="cuda",
+                        gradient_checkpointing: bool = False, **kwargs):
         """A snapshot directory or hub id, read by the loader of the inference classes (config.json + safetensors / bin with the
         reference's key names; tied keys restored)."""
         hub_kw = {k: kwargs[k] for k in ("revision", "cache_dir", "local_files_only", "token") if k in kwargs}
@@ -96,7 +138,7 @@ class TrainableCaduceusForMaskedLM(nn.Module):
         want = dtype if dtype is not None else torch_dtype
         if isinstance(want, str):
             want = getattr(torch, want) if want != "auto" else None
-        model = cls(config, dtype=want or torch.float32, device=device)
+        model = cls(config, dtype=want or torch.float32, device=device, gradient_checkpointing=gradient_checkpointing)
         model.load_state_dict(load_state_dict(path))
         return model
 
@@ -117,14 +159,19 @@ class TrainableCaduceusForMaskedLM(nn.Module):
         h, res = F.embedding(strands, emb), None
         eps = cfg.norm_epsilon
         for blk in self.caduceus.backbone.layers:
-            hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, eps, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
-            bi = blk.mixer.submodule
-            xz = F.linear(hn, bi.mamba_fwd.in_proj.weight).transpose(1, 2)       # (2B, 2E, L); in_proj is tied
-            h = self._inner(xz, bi.mamba_fwd, False) + self._inner(xz, bi.mamba_rev, True)
+            h, res = self._run_block(blk, h, res)
         sums, nll = ops.mlm_loss_head_fn(h, res, self.caduceus.backbone.norm_f.weight, emb, comp_list, labels, loss_weights, ignore_index, eps,
                                          return_nll=True)
         return MaskedLMTrainingOutput(loss=sums[:, 0].sum() / sums[:, 1].sum(), sums=sums,      # on the device; 0 / 0 = nan
                                       token_nll=nll if return_token_nll else None)
+
+    def _block(self, blk, h, res):
+        """one block, (h, res) -> (h, res): the unit gradient checkpointing keeps the inputs of"""
+        cfg = self.config
+        hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, cfg.norm_epsilon, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
+        bi = blk.mixer.submodule
+        xz = F.linear(hn, bi.mamba_fwd.in_proj.weight).transpose(1, 2)           # (2B, 2E, L); in_proj is tied
+        return self._inner(xz, bi.mamba_fwd, False) + self._inner(xz, bi.mamba_rev, True), res
 
     @staticmethod
     def _inner(xz, m, reverse: bool):
@@ -157,18 +204,20 @@ def sequence_classification_loss(logits: torch.Tensor, labels: torch.Tensor, pro
     return F.binary_cross_entropy_with_logits(logits, labels.to(logits.dtype))
 
 
-class TrainableCaduceusForSequenceClassification(nn.Module):
+class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
     """The trunk under the reference's key names, frozen; `lora_A` / `lora_B` fp32 parameters per (layer, direction, target module)
     under PEFT's names (`...mamba_fwd.in_proj.lora_A.weight`), initialised as PEFT does (A: kaiming_uniform(a=sqrt(5)) = U(+-1/sqrt(in)),
     B: 0); `score.weight` fp32 [num_labels, d_model], initialised as nn.Linear, handed to the kernel rounded to the model dtype with a
     straight-through gradient.  The weights the factors merge into are kept in fp32 whatever the model dtype, so that the merged weight
     is rounded once (adapters.merge_lora).  train_lora=False: the factors exist but do not require grad - the frozen-trunk mode, which
     is what the reference's pinned fast path trains.  lora_dropout is 0.
+    gradient_checkpointing=True: each block keeps only its inputs and is run again in the backward; same bits.
     `forward(input_ids, labels=None)` -> `.loss`, `.logits`."""
 
     def __init__(self, config: CaduceusConfig, num_labels: int, problem_type: str, pooling_strategy: str = "mean",
                  dtype: torch.dtype = torch.float32, device="cuda", r: int = 8, lora_alpha: float = 32,
-                 target_modules=("x_proj", "in_proj", "out_proj"), train_lora: bool = True, seed: int = 0):
+                 target_modules=("x_proj", "in_proj", "out_proj"), train_lora: bool = True, seed: int = 0,
+                 gradient_checkpointing: bool = False):
         super().__init__()
         from .adapters import TARGETS
         if dtype not in _DT:
@@ -187,6 +236,7 @@ class TrainableCaduceusForSequenceClassification(nn.Module):
         self.config, self.num_labels, self.problem_type, self.pooling_strategy = config, int(num_labels), problem_type, pooling_strategy
         self.dtype, self.r, self.lora_alpha, self.train_lora = dtype, int(r), float(lora_alpha), bool(train_lora)
         self.target_modules = tuple(sorted(target_modules))
+        self.is_gradient_checkpointing = bool(gradient_checkpointing)
         self.caduceus = _Backbone(config)
         self.to(dtype=dtype)
         g = torch.Generator().manual_seed(int(seed))            # the factors' and the head's initial values
@@ -286,6 +336,13 @@ class TrainableCaduceusForSequenceClassification(nn.Module):
                                   delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse)
         return self._linear(y.transpose(1, 2), m.out_proj)
 
+    def _block(self, blk, h, res):
+        """one block, (h, res) -> (h, res): the unit gradient checkpointing keeps the inputs of"""
+        cfg = self.config
+        hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, cfg.norm_epsilon, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
+        bi = blk.mixer.submodule
+        return self._direction(hn, bi.mamba_fwd, False) + self._direction(hn, bi.mamba_rev, True), res
+
     def forward(self, input_ids, labels=None) -> SequenceClassificationTrainingOutput:
         cfg = self.config
         emb = self.caduceus.backbone.embeddings.word_embeddings.embedding.weight
@@ -299,9 +356,7 @@ class TrainableCaduceusForSequenceClassification(nn.Module):
         h, res = F.embedding(strands, emb), None
         eps = cfg.norm_epsilon
         for blk in self.caduceus.backbone.layers:
-            hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, eps, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
-            bi = blk.mixer.submodule
-            h = self._direction(hn, bi.mamba_fwd, False) + self._direction(hn, bi.mamba_rev, True)
+            h, res = self._run_block(blk, h, res)
         logits = ops.pooled_head_fn(h, res, self.caduceus.backbone.norm_f.weight, self.score.weight, self.pooling_strategy, eps)
         loss = sequence_classification_loss(logits, labels, self.problem_type, self.num_labels) if labels is not None else None
         return SequenceClassificationTrainingOutput(loss=loss, logits=logits)
