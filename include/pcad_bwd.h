@@ -7,7 +7,8 @@
  * library; what is held is that this header, that table and the library's exports name the same pcad_* symbols.
  * libpcad_bwd.so links libpcad.so (same directory) and shares its conventions: status codes (pcad_status), dtypes (pcad_dtype),
  * pcad_stream, and the calling thread's pcad_last_error() text.  Built by the same Makefile from csrc/bwd_api.hip, csrc/conv_bwd.hip,
- * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip and csrc/optim.hip (the optimizer step that uses the gradients: the last section below).
+ * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip and csrc/optim.hip (the optimizer step that uses the gradients and their gathering
+ * into one buffer for a data-parallel run: the last two sections below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
@@ -175,6 +176,27 @@ int pcad_adamw_step(const void* table, const int32_t* chunk_map, int64_t count, 
 
 /* Sets every gradient of the table to zero (all n elements, nothing beyond them) in one launch. */
 int pcad_zero_grads(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, pcad_stream stream);
+
+/* ---- Every gradient in one fp32 buffer, for one collective over the ranks of a data-parallel run -------------
+ * pcad_grads_flat_plan lays the table's gradients out back to back, each slice padded to a multiple of 4 elements so that it starts
+ * 16-byte aligned (what the table asks of a `grad` pointer: the step then runs on a second table whose grads are the slices):
+ *   offsets_out[i] = sum_{j < i} round_up_4(n_j)  (elements)      *total_out = sum_j round_up_4(n_j)
+ * table: HOST memory, count records; offsets_out: HOST, count int64.  It makes pcad_optim_plan's checks (and refuses what it refuses,
+ * the 2^24 - 1 chunks included), dereferences no pointer of a record and needs no device. */
+int pcad_grads_flat_plan(const pcad_optim_tensor* table, int64_t count, int64_t* offsets_out, int64_t* total_out);
+
+/* One launch over the step's own chunk map (one 256-lane block per chunk): flat[offsets[t] + i] = (float)grad_t[i] for every i < n_t.
+ * bf16 -> fp32 is exact, so the buffer holds the gradients' values; a sum over ranks is then formed in fp32.  16-byte accesses, a full
+ * chunk's loads issued before its stores; a tensor's last n % 4 (fp32 gradients) / n % 8 (bf16) elements are walked one by one by the
+ * lane that owns them: nothing past n is read, the up to 3 padding elements of a slice are never written (the caller zeroes the buffer
+ * once) and the gradients are not modified.
+ *   table, chunk_map, count, chunks: as pcad_adamw_step;  offsets: the DEVICE copy of pcad_grads_flat_plan's, 8-byte aligned
+ *   flat: fp32 [flat_elems >= total], 16-byte aligned.  A chunk whose slice would not lie within [0, flat_elems) or is not 4-aligned
+ *   - offsets that are not this table's - is not written.
+ * PCAD_ERR_INVALID: the table arguments as pcad_adamw_step, flat_elems < 0, NULL or misaligned offsets / flat (chunks > 0).
+ * chunks == 0: OK, nothing is done. */
+int pcad_grads_gather(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, const int64_t* offsets, float* flat,
+                      int64_t flat_elems, pcad_stream stream);
 
 #ifdef __cplusplus
 }

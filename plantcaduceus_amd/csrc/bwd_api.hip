@@ -160,6 +160,29 @@ int pcad_pooled_head_bwd(const void* h, const void* res, const float* norm_weigh
     return PCAD_OK;
 }
 
+// what pcad_optim_plan and pcad_grads_flat_plan refuse in record i; *chunks_out: the record's chunk count (0 for n == 0)
+static int optim_record_check(const char* who, const pcad_optim_tensor& t, int64_t i, int64_t* chunks_out) {
+    *chunks_out = 0;
+    if (t.n < 0) return fail(PCAD_ERR_INVALID, "%s: table[%lld].n must be >= 0 (n=%lld)", who, (long long)i, (long long)t.n);
+    if (t.param_dtype != PCAD_F32 && t.param_dtype != PCAD_BF16)
+        return fail(PCAD_ERR_INVALID, "%s: table[%lld].param_dtype: bad dtype %d", who, (long long)i, t.param_dtype);
+    if (t.grad_dtype != PCAD_F32 && t.grad_dtype != PCAD_BF16)
+        return fail(PCAD_ERR_INVALID, "%s: table[%lld].grad_dtype: bad dtype %d", who, (long long)i, t.grad_dtype);
+    if (t.flags & ~PCAD_OPTIM_DECAY) return fail(PCAD_ERR_INVALID, "%s: table[%lld].flags: unknown bits 0x%x", who, (long long)i, t.flags);
+    if (t.n == 0) return PCAD_OK;
+    const struct { const void* p; const char* name; bool required; } ptr[] = {
+        {t.param, "param", true}, {t.grad, "grad", true}, {t.master, "master", t.param_dtype == PCAD_BF16},
+        {t.exp_avg, "exp_avg", true}, {t.exp_avg_sq, "exp_avg_sq", true}};
+    for (const auto& r : ptr) {
+        if (!r.p && r.required)
+            return fail(PCAD_ERR_INVALID, "%s: table[%lld].%s is null%s", who, (long long)i, r.name,
+                        strcmp(r.name, "master") == 0 ? " (a bf16 param needs an fp32 master)" : "");
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: table[%lld].%s must be 16-byte aligned", who, (long long)i, r.name);
+    }
+    *chunks_out = (t.n - 1) / PCAD_OPTIM_CHUNK + 1;
+    return PCAD_OK;
+}
+
 int pcad_optim_plan(const pcad_optim_tensor* table, int64_t count, int32_t* chunk_map, int64_t chunk_capacity, int64_t* chunks_out) {
     const char* who = "pcad_optim_plan";
     if (count < 0) return fail(PCAD_ERR_INVALID, "%s: count must be >= 0", who);
@@ -168,24 +191,9 @@ int pcad_optim_plan(const pcad_optim_tensor* table, int64_t count, int32_t* chun
     if (chunk_map && chunk_capacity < 0) return fail(PCAD_ERR_INVALID, "%s: chunk_capacity must be >= 0", who);
     int64_t chunks = 0;
     for (int64_t i = 0; i < count; ++i) {
-        const pcad_optim_tensor& t = table[i];
-        if (t.n < 0) return fail(PCAD_ERR_INVALID, "%s: table[%lld].n must be >= 0 (n=%lld)", who, (long long)i, (long long)t.n);
-        if (t.param_dtype != PCAD_F32 && t.param_dtype != PCAD_BF16)
-            return fail(PCAD_ERR_INVALID, "%s: table[%lld].param_dtype: bad dtype %d", who, (long long)i, t.param_dtype);
-        if (t.grad_dtype != PCAD_F32 && t.grad_dtype != PCAD_BF16)
-            return fail(PCAD_ERR_INVALID, "%s: table[%lld].grad_dtype: bad dtype %d", who, (long long)i, t.grad_dtype);
-        if (t.flags & ~PCAD_OPTIM_DECAY) return fail(PCAD_ERR_INVALID, "%s: table[%lld].flags: unknown bits 0x%x", who, (long long)i, t.flags);
-        if (t.n == 0) continue;
-        const struct { const void* p; const char* name; bool required; } ptr[] = {
-            {t.param, "param", true}, {t.grad, "grad", true}, {t.master, "master", t.param_dtype == PCAD_BF16},
-            {t.exp_avg, "exp_avg", true}, {t.exp_avg_sq, "exp_avg_sq", true}};
-        for (const auto& r : ptr) {
-            if (!r.p && r.required)
-                return fail(PCAD_ERR_INVALID, "%s: table[%lld].%s is null%s", who, (long long)i, r.name,
-                            strcmp(r.name, "master") == 0 ? " (a bf16 param needs an fp32 master)" : "");
-            if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: table[%lld].%s must be 16-byte aligned", who, (long long)i, r.name);
-        }
-        const int64_t nc = (t.n - 1) / PCAD_OPTIM_CHUNK + 1;
+        int64_t nc = 0;
+        if (int rc = optim_record_check(who, table[i], i, &nc)) return rc;
+        if (nc == 0) continue;
         if (nc > PCAD_OPTIM_MAX_CHUNKS - chunks) return fail(PCAD_ERR_INVALID, "%s: the table has more than 2^24 - 1 chunks (at table[%lld])", who, (long long)i);
         if (chunk_map) {
             if (chunks + nc > chunk_capacity)
@@ -198,6 +206,25 @@ int pcad_optim_plan(const pcad_optim_tensor* table, int64_t count, int32_t* chun
         chunks += nc;
     }
     *chunks_out = chunks;
+    return PCAD_OK;
+}
+
+int pcad_grads_flat_plan(const pcad_optim_tensor* table, int64_t count, int64_t* offsets_out, int64_t* total_out) {
+    const char* who = "pcad_grads_flat_plan";
+    if (count < 0) return fail(PCAD_ERR_INVALID, "%s: count must be >= 0", who);
+    if (!table && count > 0) return fail(PCAD_ERR_INVALID, "%s: null table", who);
+    if (!offsets_out && count > 0) return fail(PCAD_ERR_INVALID, "%s: null offsets_out", who);
+    if (!total_out) return fail(PCAD_ERR_INVALID, "%s: null total_out", who);
+    int64_t chunks = 0, total = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        int64_t nc = 0;
+        if (int rc = optim_record_check(who, table[i], i, &nc)) return rc;
+        if (nc > PCAD_OPTIM_MAX_CHUNKS - chunks) return fail(PCAD_ERR_INVALID, "%s: the table has more than 2^24 - 1 chunks (at table[%lld])", who, (long long)i);
+        chunks += nc;
+        offsets_out[i] = total;
+        total += (table[i].n + 3) / 4 * 4;              // below 2^24 chunks of 4096: far from 2^63
+    }
+    *total_out = total;
     return PCAD_OK;
 }
 
@@ -244,6 +271,22 @@ int pcad_zero_grads(const void* table, const int32_t* chunk_map, int64_t count, 
     const char* who = "pcad_zero_grads";
     if (int rc = optim_table_check(who, table, chunk_map, count, chunks)) return rc;
     hipError_t err = launch_zero_grads(table, chunk_map, chunks, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_grads_gather(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, const int64_t* offsets, float* flat,
+                      int64_t flat_elems, pcad_stream stream) {
+    const char* who = "pcad_grads_gather";
+    if (int rc = optim_table_check(who, table, chunk_map, count, chunks)) return rc;
+    if (flat_elems < 0) return fail(PCAD_ERR_INVALID, "%s: flat_elems must be >= 0 (flat_elems=%lld)", who, (long long)flat_elems);
+    if (chunks > 0) {
+        if (!offsets) return fail(PCAD_ERR_INVALID, "%s: null offsets", who);
+        if (((uintptr_t)offsets) % 8) return fail(PCAD_ERR_INVALID, "%s: offsets must be 8-byte aligned", who);
+        if (!flat) return fail(PCAD_ERR_INVALID, "%s: null flat", who);
+        if (((uintptr_t)flat) % 16) return fail(PCAD_ERR_INVALID, "%s: flat must be 16-byte aligned", who);
+    }
+    hipError_t err = launch_grads_gather(table, chunk_map, chunks, offsets, flat, flat_elems, (hipStream_t)stream);
     if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
     return PCAD_OK;
 }

@@ -467,6 +467,10 @@ struct AdamwLaunch {
 size_t optim_scratch_bytes(int64_t chunks);
 hipError_t launch_adamw_step(const AdamwLaunch& a, hipStream_t s);
 hipError_t launch_zero_grads(const void* table, const int32_t* map, int64_t chunks, hipStream_t s);
+// flat[offsets[t] + i] = float(grad_t[i]) over the same chunks (pcad_grads_gather); offsets: device int64 [count], multiples of 4;
+// a chunk that would not lie within flat_elems is not written
+hipError_t launch_grads_gather(const void* table, const int32_t* map, int64_t chunks, const int64_t* offsets, float* flat, int64_t flat_elems,
+                               hipStream_t s);
 
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor -> out[(strand * P + q), E]

@@ -1,5 +1,5 @@
-// One AdamW step with global-norm gradient clipping over a whole parameter set, and the zeroing of its gradients (include/pcad_bwd.h
-// pcad_adamw_step / pcad_zero_grads, libpcad_bwd.so).  Replaces torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step
+// One AdamW step with global-norm gradient clipping over a whole parameter set, the zeroing of its gradients, and their gathering into
+// one fp32 buffer for a collective (include/pcad_bwd.h pcad_adamw_step / pcad_zero_grads / pcad_grads_gather, libpcad_bwd.so).  Replaces torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step
 // (and zero_grad) with a fixed number of launches however many tensors the set has.
 //
 // The set is a table of pcad_optim_tensor records in device memory and a chunk map beside it (pcad_optim_plan): chunk c is elements
@@ -234,6 +234,43 @@ __global__ __launch_bounds__(256) void optim_zero_grads_kernel(const pcad_optim_
     else zero_chunk<float>((float*)k.t.grad + k.off, k.cnt);
 }
 
+// pcad_grads_gather: chunk c of tensor t, widened to fp32, into its slice of one flat buffer.  A full chunk's loads are
+// all issued before its stores, as in update_chunk; bf16 -> fp32 is a shift, so the copy is exact.  A slice starts at a multiple of 4
+// elements of a 16-byte aligned buffer and a chunk at a multiple of OPTIM_CHUNK within it, so every vector store is 16-byte aligned.
+template <typename G> __device__ __forceinline__ void gather_chunk(const G* __restrict__ g, float* __restrict__ out, int cnt) {
+    constexpr int V = Vec<G>::N, PER = OPTIM_CHUNK / (256 * V);
+    if (cnt == OPTIM_CHUNK) {
+        float x[PER][V];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) loadv<G, V>(g + (threadIdx.x + 256 * j) * V, x[j]);
+#pragma unroll
+        for (int j = 0; j < PER; ++j) storev<float, V>(out + (threadIdx.x + 256 * j) * V, x[j]);
+        return;
+    }
+#pragma unroll 1
+    for (int j = 0; j < PER; ++j) {
+        const int at = (threadIdx.x + 256 * j) * V;
+        if (at + V <= cnt) {
+            float x[V];
+            loadv<G, V>(g + at, x);
+            storev<float, V>(out + at, x);
+        } else {
+            for (int i = at; i < cnt; ++i) out[i] = Elem<G>::load(g + i);      // the tensor's last n % V elements; the slice's padding stays
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void optim_grads_gather_kernel(const pcad_optim_tensor* __restrict__ tab, const int32_t* __restrict__ map,
+                                                                 const int64_t* __restrict__ offsets, float* __restrict__ flat,
+                                                                 int64_t flat_elems) {
+    const Chunk k = chunk_of(tab, map);
+    const int64_t at = offsets[map[2 * (int64_t)blockIdx.x]] + k.off;
+    if (at < 0 || (at & 3) || at + k.cnt > flat_elems) return;     // offsets that are not pcad_grads_flat_plan's for this buffer: nothing is written
+    float* out = flat + at;
+    if (k.t.grad_dtype == BF16) gather_chunk<bf16_t>((const bf16_t*)k.t.grad + k.off, out, k.cnt);
+    else gather_chunk<float>((const float*)k.t.grad + k.off, out, k.cnt);
+}
+
 }  // namespace
 
 hipError_t launch_adamw_step(const AdamwLaunch& a, hipStream_t s) {
@@ -261,6 +298,16 @@ hipError_t launch_zero_grads(const void* table, const int32_t* map, int64_t chun
     if (chunks == 0) return hipSuccess;
     if (!table || !map) return hipErrorInvalidValue;
     hipLaunchKernelGGL(optim_zero_grads_kernel, dim3((unsigned)chunks), dim3(256), 0, s, (const pcad_optim_tensor*)table, map);
+    return hipGetLastError();
+}
+
+hipError_t launch_grads_gather(const void* table, const int32_t* map, int64_t chunks, const int64_t* offsets, float* flat, int64_t flat_elems,
+                               hipStream_t s) {
+    if (chunks < 0 || chunks > PCAD_OPTIM_MAX_CHUNKS) return hipErrorInvalidValue;
+    if (chunks == 0) return hipSuccess;
+    if (!table || !map || !offsets || !flat) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(optim_grads_gather_kernel, dim3((unsigned)chunks), dim3(256), 0, s, (const pcad_optim_tensor*)table, map, offsets, flat,
+                       flat_elems);
     return hipGetLastError();
 }
 

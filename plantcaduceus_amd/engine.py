@@ -149,6 +149,9 @@ BWD_SIGNATURES = {
     "pcad_adamw_step_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "pcad_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_double] * 9 + [C.c_void_p]),
     "pcad_zero_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    # every gradient into one fp32 buffer for a collective (plantcaduceus_amd.ops.grads_flat_plan / grads_gather)
+    "pcad_grads_flat_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    "pcad_grads_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
 

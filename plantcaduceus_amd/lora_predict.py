@@ -13,7 +13,9 @@ bfloat16), `--pooling` (the head's pooling_strategy, default mean) and `--lora-d
 overrides the adapter's base_model_name_or_path.  Hub ids resolve from local files / the HF cache only.
 
 `train` fine-tunes `training.TrainableCaduceusForSequenceClassification` - frozen trunk, LoRA factors, `score` - with
-`optim.AdamW` and `pretrain`'s schedules, window order and checkpoint form; single process, one GPU.  It takes the reference
+`optim.AdamW` and `pretrain`'s schedules, window order and checkpoint form; one process and one GPU under plain `python`, data-parallel under `torchrun` as `pretrain` is (world x
+`--gradient_accumulation_steps` micro-batches per step, one fused gradient all-reduce; the environment variable PCAD_DDP_BACKEND = nccl,
+the default, or gloo - no flag, as below; every rank evaluates the whole validation set, rank 0 logs and writes).  It takes the reference
 `train()`'s flag names and defaults, except that `--bf16` defaults to false (float32, as `predict` / `evaluate` default) and means
 bf16 trunk and kernels with fp32 factors and score; `save_total_limit` is 5.  Additions: `--device`, `--pooling`, `--train_lora {1,0}`
 (0: the frozen-trunk mode), `--max_grad_norm` (1.0) and `--lora_dropout` (0.0; any other value is refused, as is `--use_wandb`).
@@ -358,8 +360,8 @@ class FinetuneTrainer(pretrain.Trainer):
     task_type, device, learning_rate, lr_scheduler_type, warmup_steps, eval_batch_size, eval / save strategy and steps, logging_steps);
     valid: (ids, labels) of the validation windows, or None."""
 
-    def __init__(self, model, optimizer, source, a, max_steps: int, valid=None):
-        super().__init__(model, optimizer, source, None, a, max_steps, int(a.warmup_steps))
+    def __init__(self, model, optimizer, source, a, max_steps: int, valid=None, rank: int = 0, world: int = 1):
+        super().__init__(model, optimizer, source, None, a, max_steps, int(a.warmup_steps), rank, world)
         self.valid = valid
 
     def micro_step(self, ids, labels, _weights):
@@ -377,7 +379,8 @@ class FinetuneTrainer(pretrain.Trainer):
         res["eval_runtime"] = round(time.time() - t0, 4)
         entry = dict(res, step=self.step, epoch=round(self.epoch(), 4))
         self.log_history.append(entry)
-        logger.info(json.dumps(entry))
+        if self.rank == 0:                                      # every rank evaluates the whole set, with no communication: the same values
+            logger.info(json.dumps(entry))
         return res
 
     def save_checkpoint(self):
@@ -406,7 +409,7 @@ class FinetuneTrainer(pretrain.Trainer):
             if every_eval and self.step % every_eval == 0:
                 self.evaluate()
             if every_save and self.step % every_save == 0:
-                self.save_checkpoint()
+                self.checkpoint()
 
 
 def predict_logits_trainable(model, ids: np.ndarray, device: str, batch_size: int) -> np.ndarray:
@@ -443,9 +446,13 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
           num_train_epochs: float = 3, weight_decay: float = 0.01, eval_strategy: str = "steps", eval_steps: int = 25,
           save_strategy: str = "steps", save_steps: int = 100, logging_steps: int = 100, resume_from_checkpoint: Optional[str] = None,
           device: str = "cuda:0", pooling: str = "mean", train_lora: int = 1, max_grad_norm: float = 1.0, lora_dropout: float = 0.0) -> Dict[str, float]:
-    """Fine-tune a PlantCAD2 trunk with LoRA on tokenized parquet files (the `tokenize` command's).  -> the train metrics."""
+    """Fine-tune a PlantCAD2 trunk with LoRA on tokenized parquet files (the `tokenize` command's).  -> the train metrics.
+    Under `torchrun` the run is data-parallel as `pretrain`'s is: world x gradient_accumulation_steps micro-batches per
+    step, rank r running those with index j = r (mod world); `device` is then the rank's own (PCAD_DDP_BACKEND: nccl, the default, or gloo)."""
     import math
     from types import SimpleNamespace
+    import torch.distributed as dist
+    from . import ddp
     from .adapters import TASKS
     from .optim import AdamW
     from .training import TrainableCaduceusForSequenceClassification, stored_bytes_per_strand_position
@@ -468,10 +475,11 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
         raise SystemExit("--train_batch_size, --eval_batch_size and --gradient_accumulation_steps must be >= 1")
     nl, problem_type = TASKS[task_type]
     nl = int(num_labels) if task_type == "multi_label" else nl
+    device, rank, world = ddp.init_from_env(device, ddp.backend_from())
     ids, labels, _ = read_tokenized(train_dir)
     if labels is None:
         raise SystemExit(f"{train_dir} has no label / labels column to train on")
-    source = LabelledBatches(ids, _labels_for(labels, task_type), train_batch_size, gradient_accumulation_steps, seed)
+    source = LabelledBatches(ids, _labels_for(labels, task_type), train_batch_size, gradient_accumulation_steps * world, seed)
     valid = None
     if valid_dir:
         vids, vlabels, _ = read_tokenized(valid_dir)
@@ -494,28 +502,36 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
     n_all = sum(p.numel() for p in model.parameters())
     logger.info("Trainable parameters: %d of %d (%.2f%%)", n_train, n_all, 100.0 * n_train / n_all)
-    opt = AdamW(model.named_parameters(), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    reducer = ddp.GradReducer(dist.group.WORLD, device) if ddp.active() else None
+    opt = AdamW(model.named_parameters(), lr=learning_rate, weight_decay=weight_decay, max_grad_norm=max_grad_norm, reducer=reducer)
     a = SimpleNamespace(output_dir=output_dir, model_name=model_name, task_type=task_type, device=device, learning_rate=learning_rate,
                         lr_scheduler_type=lr_scheduler_type, warmup_steps=warmup_steps, eval_batch_size=eval_batch_size, eval_strategy=eval_strategy,
                         eval_steps=eval_steps, save_strategy=save_strategy, save_steps=save_steps, logging_steps=logging_steps)
-    tr = FinetuneTrainer(model, opt, source, a, total, valid)
+    tr = FinetuneTrainer(model, opt, source, a, total, valid, rank, world)
     if resume_from_checkpoint:
         logger.info("Resuming training from checkpoint: %s", resume_from_checkpoint)
         tr.resume(resume_from_checkpoint)
-    os.makedirs(output_dir, exist_ok=True)
+    if rank == 0:
+        os.makedirs(output_dir, exist_ok=True)
+    ddp.barrier()
     first, t0 = tr.step, time.time()
     tr.run()
     torch.cuda.synchronize(device)
     runtime = time.time() - t0
-    model.save_adapter(output_dir, model_name)
+    if reducer is not None:
+        ddp.check_in_step(tr.masters(), tr.step)
+    if rank == 0:
+        model.save_adapter(output_dir, model_name)
     done = tr.step - first
-    windows = done * train_batch_size * gradient_accumulation_steps
+    windows = done * train_batch_size * gradient_accumulation_steps * world      # the windows of all ranks
     metrics = {"epoch": tr.epoch(), "train_loss": float(tr.total_loss) / max(1, tr.step), "train_runtime": round(runtime, 4),
                "train_samples": int(source.n), "train_samples_per_second": round(windows / runtime, 3) if runtime > 0 else 0.0,
                "train_steps_per_second": round(done / runtime, 3) if runtime > 0 else 0.0, "skipped_steps": opt.state()["skipped"]}
-    pretrain._write_json(os.path.join(output_dir, "train_results.json"), metrics)
-    pretrain._write_json(os.path.join(output_dir, "trainer_state.json"), tr.trainer_state())
-    print(metrics, flush=True)
+    if rank == 0:
+        pretrain._write_json(os.path.join(output_dir, "train_results.json"), metrics)
+        pretrain._write_json(os.path.join(output_dir, "trainer_state.json"), tr.trainer_state())
+        print(metrics, flush=True)
+    ddp.shutdown()
     return metrics
 
 

@@ -1307,7 +1307,8 @@ def lora_linear_fn(x, W, A, B, scale):
     return F.linear(x, _lora_merged(W, A, B, scale, x.dtype))
 
 
-# ---- the optimizer step (include/pcad_bwd.h pcad_optim_plan / pcad_adamw_step / pcad_zero_grads) ---------------------
+# ---- the optimizer step (include/pcad_bwd.h pcad_optim_plan / pcad_adamw_step / pcad_zero_grads) and the gathering of
+# ---- every gradient into one fp32 buffer for a collective (pcad_grads_flat_plan / pcad_grads_gather) ------------------
 OPTIM_CHUNK = 4096       # include/pcad_bwd.h PCAD_OPTIM_CHUNK = csrc/kernels.hpp OPTIM_CHUNK: elements per chunk = per block
 OPTIM_DECAY = 1          # include/pcad_bwd.h PCAD_OPTIM_DECAY: flags bit 0
 
@@ -1336,6 +1337,21 @@ def optim_plan(records):
     cmap = (C.c_int32 * max(2, 2 * chunks.value))()
     _check(lib.pcad_optim_plan(C.addressof(tab), len(records), C.addressof(cmap), chunks.value, C.byref(chunks)), "pcad_optim_plan")
     return bytes(tab)[:64 * len(records)], [(cmap[2 * c], cmap[2 * c + 1]) for c in range(chunks.value)]
+
+
+def grads_flat_plan(records):
+    """pcad_grads_flat_plan on host records (as optim_plan takes them; needs no device): where each tensor's gradient lies in one fp32
+    buffer, every slice padded to a multiple of 4 elements (16 bytes).  -> (offsets in elements, one per record; total elements)"""
+    import ctypes as C
+    lib = load_bwd_library()
+    Record = _optim_record_type()
+    tab = (Record * max(1, len(records)))()
+    for r, rec in zip(tab, records):
+        r.param, r.grad, r.master, r.exp_avg, r.exp_avg_sq, r.n, r.param_dtype, r.grad_dtype, r.flags = rec
+    offsets = (C.c_int64 * max(1, len(records)))()
+    total = C.c_int64(0)
+    _check(lib.pcad_grads_flat_plan(C.addressof(tab), len(records), C.addressof(offsets), C.byref(total)), "pcad_grads_flat_plan")
+    return [int(offsets[i]) for i in range(len(records))], int(total.value)
 
 
 class OptimTable:
@@ -1367,6 +1383,8 @@ class OptimTable:
             ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
             records.append((ptr(p), ptr(g), ptr(ms), ptr(m), ptr(v), p.numel(), _dt(p), _dt(g), OPTIM_DECAY if d else 0))
         self.pointers = tuple(r[:5] for r in records)
+        self.records = records
+        self._flat_plan, self._flat_offsets = None, None
         tab, cmap = optim_plan(records)
         self.count, self.chunks = len(records), len(cmap)
         host = torch.from_numpy(np.frombuffer(tab, dtype=np.uint8).copy()).pin_memory()
@@ -1379,6 +1397,30 @@ class OptimTable:
             self.scratch_bytes = load_bwd_library().pcad_adamw_step_scratch_bytes(self.chunks)
             self.scratch = torch.empty(self.scratch_bytes + 256, dtype=torch.uint8, device=dev)
         self.device = dev
+
+    def flat_plan(self):
+        """-> (offsets, total) of grads_flat_plan for this table: the layout of its gradients in one fp32 buffer"""
+        if self._flat_plan is None:
+            self._flat_plan = grads_flat_plan(self.records)
+        return self._flat_plan
+
+    def flat_offsets(self) -> torch.Tensor:
+        """the offsets of flat_plan() as a device int64 tensor, uploaded once on the current stream from pinned memory"""
+        if self._flat_offsets is None:
+            host = torch.tensor(self.flat_plan()[0] or [0], dtype=torch.int64).pin_memory()
+            with torch.cuda.device(self.device):
+                self._flat_offsets = (host.to(self.device, non_blocking=True), host)
+        return self._flat_offsets[0]
+
+    def on_flat(self, flat: torch.Tensor) -> "OptimTable":
+        """The second table of a data-parallel step: the same parameters, masters, moments, decay flags and state - no
+        second set of anything - with the gradient of tensor i the fp32 slice flat[offsets[i] : offsets[i] + n_i] that grads_gather fills.
+        flat: a contiguous fp32 tensor of at least flat_plan()'s total elements on this device, 16-byte aligned."""
+        offsets, total = self.flat_plan()
+        if flat.dtype != torch.float32 or flat.dim() != 1 or not flat.is_contiguous() or flat.numel() < total or flat.device != self.device:
+            raise ValueError(f"flat must be a contiguous fp32 vector of at least {total} elements on {self.device}")
+        slices = [flat[o:o + p.numel()].view(p.shape) for o, p in zip(offsets, self.params)]
+        return OptimTable(self.params, slices, self.masters, self.exp_avgs, self.exp_avg_sqs, self.decay, state=self.state)
 
     def read_state(self):
         """-> dict(norm, coef, finite, skipped) of the last step.  Synchronises."""
@@ -1457,4 +1499,33 @@ def zero_grads(table: OptimTable, poison=False):
     with torch.no_grad():
         for g, (c, _) in zip(table.grads, pairs):
             g.copy_(c)
+    return _guarded_copies_intact(pairs)
+
+
+def grads_gather(table: OptimTable, flat: torch.Tensor, offsets: torch.Tensor, poison=False):
+    """pcad_grads_gather: every gradient of the table, widened to fp32 (exact), into its slice of `flat` in one launch over the table's own
+    chunk map: flat[offsets[i] + k] = float(grad_i[k]).  offsets: table.flat_offsets() (device int64, table.flat_plan()'s); flat: a
+    contiguous fp32 vector of at least the plan's total elements, 16-byte aligned.  The padding of a slice (up to 3 elements) and whatever
+    lies beyond the total are not written, the gradients are not modified.  No host synchronisation.
+    poison (tests): the launch runs on a copy of flat between OPTIM_GUARD sentinel elements and the result is copied back; -> whether all
+    sentinels are intact (else None)."""
+    lib = load_bwd_library()
+    _require_gpu(flat, "flat")
+    _require_gpu(offsets, "offsets")
+    total = table.flat_plan()[1]
+    if flat.dtype != torch.float32 or flat.dim() != 1 or not flat.is_contiguous() or flat.numel() < total or flat.device != table.device:
+        raise ValueError(f"flat must be a contiguous fp32 vector of at least {total} elements on {table.device}")
+    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() < table.count or offsets.device != table.device:
+        raise ValueError(f"offsets must be a contiguous int64 tensor of {table.count} elements on {table.device}")
+    run, pairs = flat, []
+    if poison:
+        run, whole = _guarded_copy(flat)
+        pairs.append((run, whole))
+    with torch.cuda.device(table.device):
+        _check(lib.pcad_grads_gather(table.table.data_ptr(), table.chunk_map.data_ptr(), table.count, table.chunks, offsets.data_ptr(),
+                                     run.data_ptr(), run.numel(), _stream_ptr()), "pcad_grads_gather")
+    if not poison:
+        return None
+    with torch.no_grad():
+        flat.copy_(run)
     return _guarded_copies_intact(pairs)

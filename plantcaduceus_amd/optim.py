@@ -36,11 +36,15 @@ class AdamW:
     `applies_weight_decay`; without names weight decay applies to every tensor not marked `_no_weight_decay`.  A Parameter is taken
     once, so tied weights (one Parameter under several names) are one tensor.  Parameters that do not require grad are left out.
     grad_scale multiplies every gradient before the norm is taken (1 / accumulation steps for summed micro-batch gradients);
-    max_grad_norm <= 0: no clipping."""
+    max_grad_norm <= 0: no clipping.
+    reducer: a `ddp.GradReducer` for data-parallel training, or None.  With one, `step()` gathers every gradient into the
+    reducer's fp32 buffer in one launch, sums that buffer over the ranks, and takes the step on a second table of the same parameters,
+    masters and moments whose gradients are the buffer's slices - so the norm, the clipping and the skip rule see the reduced gradients
+    and are the same on every rank.  Without one the class makes exactly the calls it always made."""
 
     def __init__(self, params: Iterable[Union[torch.nn.Parameter, Tuple[str, torch.nn.Parameter]]], lr: float = 5e-5,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 1.0,
-                 grad_scale: float = 1.0):
+                 grad_scale: float = 1.0, reducer=None):
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.max_grad_norm, self.grad_scale = float(max_grad_norm), float(grad_scale)
         self.names: List[str] = []
@@ -68,7 +72,11 @@ class AdamW:
         self._state = torch.zeros(4, dtype=torch.int32, device=self.params[0].device)      # pcad_optim_state: outlives every table
         self._table: Optional[ops.OptimTable] = None
         self._pointers = None
+        self.reducer = reducer
+        self._flat_table: Optional[ops.OptimTable] = None
         self.step_count = 0
+        if reducer is not None:
+            self.table()                                         # the buffer exists from here on: a trainer writes its loss slot before step()
 
     def table(self) -> ops.OptimTable:
         """The device table, rebuilt and uploaded again (on the stream, without synchronising) only when a pointer in it has changed.  A
@@ -88,12 +96,20 @@ class AdamW:
             self._table = ops.OptimTable([p.data for p in self.params], grads, self.master, self.exp_avg, self.exp_avg_sq, self.decay,
                                          state=self._state)
             self._pointers = (tuple(p.data_ptr() for p in self.params), tuple(g.data_ptr() for g in grads))
+            if self.reducer is not None:
+                self.reducer.allocate(self._table.flat_plan()[1])
+                self._flat_table = self._table.on_flat(self.reducer.grads)
         return self._table
 
     def step(self, lr: Optional[float] = None):
-        """One step at learning rate `lr` (default: the constructor's).  No host synchronisation."""
+        """One step at learning rate `lr` (default: the constructor's).  No host synchronisation (a gloo reducer: one, in its collective)."""
         self.step_count += 1
-        ops.adamw_step(self.table(), self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps, self.weight_decay,
+        table = self.table()
+        if self.reducer is not None:
+            ops.grads_gather(table, self.reducer.grads, table.flat_offsets())
+            self.reducer.all_reduce()
+            table = self._flat_table
+        ops.adamw_step(table, self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps, self.weight_decay,
                        self.step_count, self.max_grad_norm, self.grad_scale)
 
     def zero_grad(self):

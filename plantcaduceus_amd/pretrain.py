@@ -1,6 +1,7 @@
 """Masked-LM pretraining: the `--do_train` half of the reference's `src/HF_pre_train.py` (:446-501: `Trainer.train()`, `save_model`,
 `save_metrics("train")`, `save_state`) on this project's kernels - forward and backward of `training.TrainableCaduceusForMaskedLM`,
-the fused AdamW step of `optim.AdamW`.  Single process, one GPU.
+the fused AdamW step of `optim.AdamW`.  One process and one GPU under plain `python`; data-parallel over the GPUs
+of a node under `torchrun` (below).
 
     python -m plantcaduceus_amd.pretrain --model_name_or_path <snapshot> | --config_name <config.json> \\
         --dataset_name <dir or table> --do_train [--do_eval] --output_dir out \\
@@ -9,7 +10,8 @@ the fused AdamW step of `optim.AdamW`.  Single process, o
         --num_train_epochs 3 | --max_steps N  --lr_scheduler_type linear|cosine|constant|constant_with_warmup \\
         --warmup_steps K | --warmup_ratio R  --mlm_probability 0.15 --soft_masked_loss_weights_train 1.0 \\
         --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16 \\
-        [--gradient_checkpointing]
+        [--gradient_checkpointing] [--ddp_backend nccl|gloo]
+    torchrun --nproc-per-node W -m plantcaduceus_amd.pretrain ... (the same flags)
 
 Flag names and defaults are `transformers.TrainingArguments`' and `HF_pre_train.py`'s.  `--config_name` alone starts from scratch:
 `checkpoint.synthetic_state_dict(config, seed=--seed, stress=False)`, the Mamba-style initialisation.
@@ -35,7 +37,18 @@ Departures from the reference, all stated in DESIGN.md §4o: a step whose gradie
 of letting NaNs into the weights; weight decay leaves out `A_log` and `D` beside biases and norm weights; `--dtype bfloat16` means
 bf16 parameters and kernels with fp32 master weights in the optimizer, where the reference's `bf16=True` is autocast around fp32
 parameters.  `--gradient_checkpointing` (`TrainingArguments`' name and default) keeps only each block's inputs and runs the block again in
-the backward: the same bits for about an eighth of the stored activations.  Not built: DDP / torchrun."""
+the backward: the same bits for about an eighth of the stored activations.
+
+Under `torchrun` with world size W an optimizer step consumes the `--gradient_accumulation_steps` x W micro-batches that
+one process with that accumulation would consume, in the same window order and with the same masks: every rank draws all of them (the
+mask generator advances identically everywhere), rank r runs those with index j = r (mod W), one collective sums the gradients of all
+ranks in fp32, and `grad_scale` = 1 / (micro-batches of the step over all ranks) is applied after the sum.  `steps_per_epoch`, the
+schedule and `trainer_state.json` are those of that single process, so a checkpoint written at one world size resumes at another with
+accumulation x world kept equal; at W = 2 and accumulation 1 in fp32 the run equals the single-process run with accumulation 2 bit for
+bit.  `--ddp_backend` (`TrainingArguments`' name; the environment's PCAD_DDP_BACKEND when absent; default nccl): nccl is RCCL, one rank
+per device, no host wait; gloo stages the buffer through pinned host memory with one stream synchronisation per step and lets ranks
+share a device.  Rank 0 alone logs and writes; every checkpoint and the end compare a checksum of the master weights over the ranks.
+`--do_eval` runs on rank 0 after the group is shut down."""
 from __future__ import annotations
 
 import json
@@ -171,6 +184,9 @@ def build_parser():
     p.add_argument("--resume_from_checkpoint", default=None)
     p.add_argument("--gradient_checkpointing", action="store_true",
                    help="keep only each block's inputs and run its forward again in the backward (DESIGN.md §4q): same bits, less memory")
+    p.add_argument("--ddp_backend", default=None, choices=("nccl", "gloo"),
+                   help="under torchrun: nccl (RCCL, one rank per device; the default) or gloo (ranks may share a device; one host "
+                        "synchronisation per step); the environment's PCAD_DDP_BACKEND when absent (DESIGN.md §4r)")
     p.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
     p.add_argument("--device", default="cuda:0")
     return p
@@ -221,11 +237,16 @@ def _write_json(path: str, obj):
 
 
 class Trainer:
-    """The loop around model, optimizer and batch source; `micro_step` is the only place the model runs."""
+    """The loop around model, optimizer and batch source; `micro_step` is the only place the model runs.  rank / world: this process's
+    place in a data-parallel run: `source` hands out the micro-batches of all ranks, this one runs those with index
+    j = rank (mod world), and an optimizer with a `reducer` sums the gradients and the loss over the ranks; rank 0 alone logs and writes."""
 
-    def __init__(self, model, optimizer, source: BatchSource, tokenizer, a, max_steps: int, warmup: int):
+    def __init__(self, model, optimizer, source: BatchSource, tokenizer, a, max_steps: int, warmup: int, rank: int = 0, world: int = 1):
         self.model, self.opt, self.source, self.tok, self.a = model, optimizer, source, tokenizer, a
         self.max_steps, self.warmup = max_steps, warmup
+        self.rank, self.world = int(rank), int(world)
+        if self.world > 1 and getattr(optimizer, "reducer", None) is None:
+            raise ValueError("a world of more than one rank needs an optimizer with a reducer (optim.AdamW(..., reducer=ddp.GradReducer(...)))")
         self.step = 0
         self.log_history: List[dict] = []
         dev = a.device
@@ -244,16 +265,24 @@ class Trainer:
         return out.loss.detach()
 
     def train_step(self):
-        """optimizer step number self.step (0-based): its micro-batches, the fused step, zero_grad; nothing is read back"""
-        batches = self.source.step_batches(self.step)
+        """optimizer step number self.step (0-based): this rank's share of its micro-batches, the fused step, zero_grad; nothing is read
+        back.  With a reducer the rank's sum of loss x scale travels in the reducer's loss slot and comes back as the global loss; a rank
+        whose share is empty contributes zero gradients and a zero loss and still takes part in the collective."""
+        from . import ddp
+        batches = self.source.step_batches(self.step)           # every rank draws all of them
         scale = 1.0 / len(batches)
         self.opt.grad_scale = scale
+        reducer = getattr(self.opt, "reducer", None)
         loss = None
-        for ids, labels, weights in batches:
+        for ids, labels, weights in ddp.share(batches, self.rank, self.world):
             l = self.micro_step(ids, labels, weights).float() * scale
             loss = l if loss is None else loss + l
+        if reducer is not None:
+            reducer.loss.zero_() if loss is None else reducer.loss.copy_(loss.reshape(1))
         lr = self.lr(self.step)
         self.opt.step(lr=lr)
+        if reducer is not None:
+            loss = reducer.loss[0].clone()
         self.opt.zero_grad()
         self.window_loss += loss
         self.total_loss += loss
@@ -271,7 +300,8 @@ class Trainer:
         self.window_loss.zero_()
         self.window_steps = 0
         self.log_history.append(entry)
-        logger.info(json.dumps(entry))
+        if self.rank == 0:
+            logger.info(json.dumps(entry))
         return entry
 
     def trainer_state(self) -> dict:
@@ -284,6 +314,20 @@ class Trainer:
         torch.save(self.opt.state_dict(), os.path.join(path, "optimizer.pt"))
         torch.save(self.source.state(), os.path.join(path, "rng_state.pt"))
         _write_json(os.path.join(path, "trainer_state.json"), self.trainer_state())
+        return path
+
+    def masters(self):
+        """the fp32 weights the optimizer steps on (an fp32 parameter is its own master)"""
+        return [m if m is not None else p.data for m, p in zip(self.opt.master, self.opt.params)]
+
+    def checkpoint(self):
+        """A checkpoint in a data-parallel run: the ranks compare a checksum of their master weights (a mismatch raises on every rank and
+        names the step), rank 0 writes, and a barrier follows so that no rank reads a checkpoint that is still being written."""
+        from . import ddp
+        if ddp.active():
+            ddp.check_in_step(self.masters(), self.step)
+        path = self.save_checkpoint() if self.rank == 0 else os.path.join(self.a.output_dir, f"checkpoint-{self.step}")
+        ddp.barrier()
         return path
 
     def restore_inputs(self, path: str):
@@ -308,11 +352,13 @@ class Trainer:
             if a.logging_steps > 0 and (self.step % a.logging_steps == 0 or self.step == self.max_steps):
                 self.log(lr)
             if a.save_steps > 0 and self.step % a.save_steps == 0:
-                self.save_checkpoint()
+                self.checkpoint()
 
 
-def train(a) -> Dict[str, float]:
-    from . import mlm_eval
+def train(a, rank: int = 0, world: int = 1) -> Dict[str, float]:
+    """rank / world: `ddp.init_from_env`'s, with a.device this rank's device; world > 1 (or a one-rank group): the data-parallel run"""
+    import torch.distributed as dist
+    from . import ddp, mlm_eval
     from .optim import AdamW
     dtype = {"float32": torch.float32, "bfloat16": torch.bfloat16}[a.dtype]
     if a.per_device_train_batch_size < 1 or a.gradient_accumulation_steps < 1:
@@ -323,29 +369,37 @@ def train(a) -> Dict[str, float]:
         seqs = seqs[:max(0, a.max_train_samples)]
     ids, special, weights = mlm_eval.tokenize_windows(tok, seqs, a.soft_masked_loss_weights_train)
     source = BatchSource(ids, special, weights, mlm_eval.make_collator(tok, a.mlm_probability), a.per_device_train_batch_size,
-                         a.gradient_accumulation_steps, a.seed)
+                         a.gradient_accumulation_steps * world, a.seed)     # the single process this run equals
     max_steps = a.max_steps if a.max_steps > 0 else math.ceil(a.num_train_epochs * source.steps_per_epoch)
     warmup = warmup_steps_of(a.warmup_steps, a.warmup_ratio, max_steps)
     model = build_model(a, dtype, a.resume_from_checkpoint)
+    reducer = ddp.GradReducer(dist.group.WORLD, a.device) if ddp.active() else None
     opt = AdamW(model.named_parameters(), lr=a.learning_rate, betas=(a.adam_beta1, a.adam_beta2), eps=a.adam_epsilon,
-                weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm)
-    tr = Trainer(model, opt, source, tok, a, max_steps, warmup)
+                weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm, reducer=reducer)
+    tr = Trainer(model, opt, source, tok, a, max_steps, warmup, rank, world)
     if a.resume_from_checkpoint:
         tr.resume(a.resume_from_checkpoint)
-    os.makedirs(a.output_dir, exist_ok=True)
+    if rank == 0:
+        os.makedirs(a.output_dir, exist_ok=True)
+    ddp.barrier()
     first = tr.step
     t0 = time.time()
     tr.run()
     torch.cuda.synchronize(a.device)
     runtime = time.time() - t0
-    save_snapshot(model, tok, a.output_dir)
+    if reducer is not None:
+        ddp.check_in_step(tr.masters(), tr.step)
+    if rank == 0:
+        save_snapshot(model, tok, a.output_dir)
     done = tr.step - first
-    windows = done * a.per_device_train_batch_size * a.gradient_accumulation_steps
+    windows = done * a.per_device_train_batch_size * a.gradient_accumulation_steps * world      # the windows of all ranks
     metrics = {"epoch": tr.epoch(), "train_loss": float(tr.total_loss) / max(1, tr.step), "train_runtime": round(runtime, 4),
                "train_samples": int(source.n), "train_samples_per_second": round(windows / runtime, 3) if runtime > 0 else 0.0,
                "train_steps_per_second": round(done / runtime, 3) if runtime > 0 else 0.0, "skipped_steps": opt.state()["skipped"]}
-    _write_json(os.path.join(a.output_dir, "train_results.json"), metrics)
-    _write_json(os.path.join(a.output_dir, "trainer_state.json"), tr.trainer_state())
+    if rank == 0:
+        _write_json(os.path.join(a.output_dir, "train_results.json"), metrics)
+        _write_json(os.path.join(a.output_dir, "trainer_state.json"), tr.trainer_state())
+    ddp.barrier()
     return metrics
 
 
@@ -365,9 +419,15 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, Dict[str, float]]:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     if not (a.do_train or a.do_eval):
         raise SystemExit("nothing to do: pass --do_train and / or --do_eval")
+    from . import ddp
+    a.device, rank, world = ddp.init_from_env(a.device, ddp.backend_from(a.ddp_backend))
     results = {}
     if a.do_train:
-        results["train"] = train(a)
+        results["train"] = train(a, rank, world)
+    ddp.shutdown()                                              # after the final barrier: no rank sits in a collective during the evaluation
+    if rank != 0:
+        return results
+    if a.do_train:
         print(json.dumps(results["train"], sort_keys=True), flush=True)
     if a.do_eval:
         os.makedirs(a.output_dir, exist_ok=True)
