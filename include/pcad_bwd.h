@@ -7,12 +7,13 @@
  * library; what is held is that this header, that table and the library's exports name the same pcad_* symbols.
  * libpcad_bwd.so links libpcad.so (same directory) and shares its conventions: status codes (pcad_status), dtypes (pcad_dtype),
  * pcad_stream, and the calling thread's pcad_last_error() text.  Built by the same Makefile from csrc/bwd_api.hip, csrc/conv_bwd.hip,
- * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip and csrc/optim.hip (the optimizer step that uses the gradients and their gathering
- * into one buffer for a data-parallel run: the last two sections below).
+ * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip, csrc/optim.hip (the optimizer step that uses the gradients and their gathering
+ * into one buffer for a data-parallel run) and csrc/wgrad.hip (the weight gradient of a linear layer into an fp32 main gradient: the
+ * last section below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
- * pcad_last_error(); every output is overwritten, never accumulated; no floating-point atomics - every sum has a fixed order, so two
+ * pcad_last_error(); every output is overwritten, never accumulated (the one exception: pcad_linear_wgrad with accumulate != 0); no floating-point atomics - every sum has a fixed order, so two
  * calls give the same bits; all in-tensor offsets are 64-bit; rows outside a strand are never read or written. */
 #ifndef PCAD_BWD_H
 #define PCAD_BWD_H
@@ -197,6 +198,31 @@ int pcad_grads_flat_plan(const pcad_optim_tensor* table, int64_t count, int64_t*
  * chunks == 0: OK, nothing is done. */
 int pcad_grads_gather(const void* table, const int32_t* chunk_map, int64_t count, int64_t chunks, const int64_t* offsets, float* flat,
                       int64_t flat_elems, pcad_stream stream);
+
+/* ---- fp32 main gradients: the weight gradient of a linear layer, accumulated in place ----------------------------
+ * Replaces: the `dy.t() @ x` of F.linear's backward, which can only return the gradient in the parameter's dtype.
+ *   dw[n, k] = (accumulate ? dw[n, k] : 0) + s[n, k]        s[n, k] = sum_m dy[m, n] x[m, k]
+ * This entry is the one stated exception to "every output is overwritten, never accumulated": with accumulate != 0 it ADDS to dw.
+ * Each bf16 x bf16 product is exact in fp32; the sum is fp32 in a fixed order; s is formed completely and then added to the old value
+ * once - every element of dw sees one read (accumulate only) and one write.  The header's other rules hold: no allocation, no
+ * synchronisation, the caller's stream and scratch, no floating-point atomics, 64-bit offsets (M N may pass 2^31).
+ *   dy     bf16 [M, N], row stride lddy elements;  x bf16 [M, K], row stride ldx;  dw fp32 [N, K], row stride lddw
+ *   N % 8 == 0, K % 8 == 0, 8 <= N, K <= 8192;  lddy % 8 == 0, ldx % 8 == 0, lddw % 4 == 0;  lddy >= N, ldx >= K, lddw >= K;  M >= 0
+ *   dy, x, dw non-NULL (dy and x may be NULL when M == 0) and 16-byte aligned.  Anything else: PCAD_ERR_INVALID naming the argument, decided without a device.
+ * The rows are cut into slabs that depend on (M, N, K) alone - never on the device - so the bits are the same on any GPU:
+ *   tiles = ceil(N / 128) ceil(K / 128)     want = min(32, max(1, 256 / tiles))   (integer division)
+ *   rows_per_slab = round_up(ceil(M / want), 256)     slabs = ceil(M / rows_per_slab)
+ * Slab i holds rows [i rows_per_slab, min(M, (i + 1) rows_per_slab)); within a slab the rows are added in 32-row MFMA steps in index
+ * order; with more than one slab each slab's partial goes to scratch and the partials are added in slab order.
+ * pcad_linear_wgrad_slabs returns slabs and stores rows_per_slab (host only, no device; M == 0: 0 and 0; a refused shape: -1 and the
+ * message in pcad_last_error()).
+ *   scratch    pcad_linear_wgrad_scratch_bytes(M, N, K) = slabs > 1 ? round_up(slabs N K 4, 256) : 0 bytes (0 for a refused shape);
+ *              may be NULL when that is 0
+ * M == 0: with accumulate nothing is done, without it dw is written as zeros. */
+int64_t pcad_linear_wgrad_slabs(int64_t M, int N, int K, int64_t* rows_per_slab_out);
+size_t pcad_linear_wgrad_scratch_bytes(int64_t M, int N, int K);
+int pcad_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw,
+                      int64_t M, int N, int K, int accumulate, void* scratch, size_t scratch_bytes, pcad_stream stream);
 
 #ifdef __cplusplus
 }

@@ -291,4 +291,49 @@ int pcad_grads_gather(const void* table, const int32_t* chunk_map, int64_t count
     return PCAD_OK;
 }
 
+// what the three pcad_linear_wgrad* entries refuse in (M, N, K)
+static int wgrad_shape_check(const char* who, int64_t M, int N, int K) {
+    if (M < 0) return fail(PCAD_ERR_INVALID, "%s: M must be >= 0 (M=%lld)", who, (long long)M);
+    if (N < 8 || N > 8192 || N % 8) return fail(PCAD_ERR_INVALID, "%s: N must be a multiple of 8 in [8, 8192] (N=%d)", who, N);
+    if (K < 8 || K > 8192 || K % 8) return fail(PCAD_ERR_INVALID, "%s: K must be a multiple of 8 in [8, 8192] (K=%d)", who, K);
+    return PCAD_OK;
+}
+
+int64_t pcad_linear_wgrad_slabs(int64_t M, int N, int K, int64_t* rows_per_slab_out) {
+    int64_t rows = 0;
+    if (rows_per_slab_out) *rows_per_slab_out = 0;
+    if (wgrad_shape_check("pcad_linear_wgrad_slabs", M, N, K)) return -1;
+    const int64_t slabs = wgrad_slabs(M, N, K, &rows);
+    if (rows_per_slab_out) *rows_per_slab_out = rows;
+    return slabs;
+}
+
+size_t pcad_linear_wgrad_scratch_bytes(int64_t M, int N, int K) {
+    if (M < 0 || N < 8 || N > 8192 || N % 8 || K < 8 || K > 8192 || K % 8) return 0;
+    return wgrad_bytes(M, N, K);
+}
+
+int pcad_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int64_t M, int N, int K,
+                      int accumulate, void* scratch, size_t scratch_bytes, pcad_stream stream) {
+    const char* who = "pcad_linear_wgrad";
+    const struct { const void* p; const char* name; } req[] = {{dy, "dy"}, {x, "x"}, {dw, "dw"}};
+    if (!dw) return fail(PCAD_ERR_INVALID, "%s: null dw", who);
+    for (const auto& r : req)
+        if (!r.p && M != 0) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);      // no rows: dy and x are not read and may be NULL
+    if (int rc = wgrad_shape_check(who, M, N, K)) return rc;
+    if (lddy < N || lddy % 8) return fail(PCAD_ERR_INVALID, "%s: lddy must be a multiple of 8 and >= N (lddy=%lld, N=%d)", who, (long long)lddy, N);
+    if (ldx < K || ldx % 8) return fail(PCAD_ERR_INVALID, "%s: ldx must be a multiple of 8 and >= K (ldx=%lld, K=%d)", who, (long long)ldx, K);
+    if (lddw < K || lddw % 4) return fail(PCAD_ERR_INVALID, "%s: lddw must be a multiple of 4 and >= K (lddw=%lld, K=%d)", who, (long long)lddw, K);
+    for (const auto& r : req)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    const size_t need = wgrad_bytes(M, N, K);
+    if (need > 0 && (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < need))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_linear_wgrad_scratch_bytes large", who);
+    hipError_t err = launch_linear_wgrad({.dy = dy, .lddy = lddy, .x = x, .ldx = ldx, .dw = dw, .lddw = lddw, .M = M, .N = N, .K = K,
+                                          .accumulate = accumulate != 0, .scratch = scratch},
+                                         (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 }  // extern "C"

@@ -472,6 +472,30 @@ hipError_t launch_zero_grads(const void* table, const int32_t* map, int64_t chun
 hipError_t launch_grads_gather(const void* table, const int32_t* map, int64_t chunks, const int64_t* offsets, float* flat, int64_t flat_elems,
                                hipStream_t s);
 
+// wgrad.hip (libpcad_bwd.so): dw[n, k] = (accumulate ? dw[n, k] : 0) + sum_m dy[m, n] x[m, k] with bf16 dy [M, N] / x [M, K]
+// and fp32 dw [N, K] (pcad_bwd.h pcad_linear_wgrad) - the one operator here that ADDS to its output.  N, K multiples of 8.
+// The rows are cut into slabs by (M, N, K) and these constants alone, never by the device:
+//   tiles = ceil(N / WGRAD_BN) ceil(K / WGRAD_BK)     want = clamp(WGRAD_TARGET_BLOCKS / tiles, 1, WGRAD_MAX_SLABS)   (integer division)
+//   rows_per_slab = round_up(ceil(M / want), WGRAD_SLAB_ROWS)     slabs = ceil(M / rows_per_slab)                    (M == 0: 0 and 0)
+// scratch: wgrad_bytes(M, N, K) = slabs > 1 ? round_up(slabs N K 4, 256) : 0 bytes, 256-byte aligned - one partial [N][K] per slab,
+// which a second kernel adds in slab order before the old value is added once.
+constexpr int WGRAD_BN = 128, WGRAD_BK = 128;     // the tile of dw one block owns
+constexpr int WGRAD_TM = 64;                      // rows of dy / x per LDS stage (two 32-row MFMA steps)
+constexpr int WGRAD_TARGET_BLOCKS = 256;          // blocks the split aims for
+constexpr int WGRAD_MAX_SLABS = 32;
+constexpr int WGRAD_SLAB_ROWS = 256;              // rows_per_slab is a multiple of this
+struct LinearWgradLaunch {
+    const void* dy;  int64_t lddy;
+    const void* x;   int64_t ldx;
+    float* dw;       int64_t lddw;
+    int64_t M;  int N, K;
+    bool accumulate = false;
+    void* scratch = nullptr;
+};
+int64_t wgrad_slabs(int64_t M, int N, int K, int64_t* rows_per_slab);
+size_t wgrad_bytes(int64_t M, int N, int K);
+hipError_t launch_linear_wgrad(const LinearWgradLaunch& a, hipStream_t s);
+
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor -> out[(strand * P + q), E]
 struct GatherRowsLaunch {

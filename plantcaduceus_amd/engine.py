@@ -152,6 +152,11 @@ BWD_SIGNATURES = {
     # every gradient into one fp32 buffer for a collective (plantcaduceus_amd.ops.grads_flat_plan / grads_gather)
     "pcad_grads_flat_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     "pcad_grads_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # the weight gradient of a linear layer into an fp32 main gradient (plantcaduceus_amd.ops.linear_wgrad / linear_fn)
+    "pcad_linear_wgrad_slabs": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "pcad_linear_wgrad_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "pcad_linear_wgrad": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
 

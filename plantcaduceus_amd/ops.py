@@ -18,10 +18,12 @@ grad; otherwise the plain call, no graph): selective_scan_fn (include/pcad_train
 rms_norm_fn (include/pcad_bwd.h), mamba_inner_fn as a composition of those around stock F.linear, mlm_loss_head_fn - the end of the
 masked LM's forward with labels (include/pcad_bwd.h pcad_loss_head_bwd) - and pooled_head_fn, the end of the sequence classifier's
 (include/pcad_bwd.h pcad_pooled_head_bwd); lora_linear_fn is a frozen linear with LoRA factors merged in, differentiated by torch matmuls.
-plantcaduceus_amd.training composes the models from them.
+plantcaduceus_amd.training composes the models from them.  linear_fn is F.linear for the masked LM's projections; for a weight that
+carries an fp32 `main_grad` its backward adds dy^T x to that buffer with linear_wgrad (include/pcad_bwd.h pcad_linear_wgrad).
 """
 from __future__ import annotations
 
+import logging
 from typing import Optional
 
 import torch
@@ -664,11 +666,12 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
                                                                                   out_proj_weight, A, D, delta_bias)):
         xc = causal_conv1d_dir(xz[:, :E].transpose(1, 2), w, bias, reverse)                      # (B, L, E)
-        x_dbl = F.linear(xc, x_proj_weight.to(dt))                                               # (B, L, R + 32)
-        delta = F.linear(x_dbl[..., :R], delta_proj_weight.to(dt)).transpose(1, 2)               # (B, E, L)
+        # linear_fn: F.linear(x, weight.to(dt)) itself unless the weight carries an fp32 main_grad
+        x_dbl = linear_fn(xc, x_proj_weight)                                                     # (B, L, R + 32)
+        delta = linear_fn(x_dbl[..., :R], delta_proj_weight).transpose(1, 2)                     # (B, E, L)
         y = selective_scan_fn(xc.transpose(1, 2), delta, A, x_dbl[..., R:R + 16].transpose(1, 2), x_dbl[..., R + 16:].transpose(1, 2), D,
                               z=xz[:, E:], delta_bias=delta_bias, delta_softplus=True, reverse=reverse)
-        return F.linear(y.transpose(1, 2), out_proj_weight.to(dt))
+        return linear_fn(y.transpose(1, 2), out_proj_weight)
     x_tm = xz[:, :E].transpose(1, 2).contiguous()                    # the engine is token-major (test plumbing: it never transposes)
     z_tm = xz[:, E:].transpose(1, 2).contiguous()
     rows = Bsz * L
@@ -1529,3 +1532,135 @@ def grads_gather(table: OptimTable, flat: torch.Tensor, offsets: torch.Tensor, p
     with torch.no_grad():
         flat.copy_(run)
     return _guarded_copies_intact(pairs)
+
+
+# ---- fp32 main gradients: the weight gradient of a linear layer, accumulated in place (include/pcad_bwd.h pcad_linear_wgrad) ----
+WGRAD_MIN, WGRAD_MAX = 8, 8192      # include/pcad_bwd.h: N and K are multiples of 8 inside [8, 8192]
+WGRAD_GUARD = -1234.0               # the sentinel around a poisoned output (rows above and below, 4 columns left and right)
+
+_log = logging.getLogger(__name__)
+
+
+def linear_wgrad_slabs(M: int, N: int, K: int):
+    """pcad_linear_wgrad_slabs (host only): -> (slabs, rows_per_slab) of the split of the M rows; a refused shape raises"""
+    import ctypes as C
+    rows = C.c_int64(0)
+    slabs = load_bwd_library().pcad_linear_wgrad_slabs(int(M), int(N), int(K), C.byref(rows))
+    if slabs < 0:
+        _check(1, "pcad_linear_wgrad_slabs")
+    return int(slabs), int(rows.value)
+
+
+def wgrad_kernel_takes(N: int, K: int) -> bool:
+    """whether [N, K] lies inside pcad_linear_wgrad's limits"""
+    return N % 8 == 0 and K % 8 == 0 and WGRAD_MIN <= N <= WGRAD_MAX and WGRAD_MIN <= K <= WGRAD_MAX
+
+
+def _wgrad_rows(t: torch.Tensor, what: str):
+    """t [..., C] bf16 as M rows of C elements `ld` apart, in place when its layout allows it (unit stride inside a row, the leading
+    dimensions collapsing to one row stride that is a multiple of 8 and >= C, a 16-byte aligned start), else through .contiguous().
+    -> (the tensor that owns the rows, M, ld)"""
+    if t.dtype != torch.bfloat16:
+        raise ValueError(f"{what} must be bf16 (an fp32 model's gradients are fp32 already), got {t.dtype}")
+    C = t.shape[-1]
+    M = t.numel() // C if C else 0
+    lead = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n != 1]
+    ok = t.dim() >= 2 and t.stride(-1) == 1 and all(a[1] == b[0] * b[1] for a, b in zip(lead, lead[1:]))
+    ld = lead[-1][1] if lead else C
+    if not ok or ld % 8 or ld < C or t.data_ptr() % 16:
+        t, ld = t.contiguous(), C
+    return t, M, ld
+
+
+def linear_wgrad(dy, x, out=None, accumulate=False, poison=False):
+    """pcad_linear_wgrad: out[n, k] = (accumulate ? out[n, k] : 0) + sum_m dy[m, n] x[m, k] in fp32, the products exact and the sum in a
+    fixed order.  dy [..., N] and x [..., K] bf16 over the same leading dimensions (M rows); a row-strided view such as x_dbl[..., :R] is
+    read in place when its strides meet the kernel's limits, else copied.  out: fp32 [N, K] with unit stride inside a row (a row stride
+    that is a multiple of 4, a 16-byte aligned start), written in place; None: a new tensor (accumulate then adds to zeros).
+    -> out.  poison (tests): the scratch starts as 0xFF bytes and the call runs on a copy of out inside a larger buffer of sentinels -
+    one row above and below, 4 columns left and right - that is copied back; linear_wgrad.guards_ok tells whether they are intact."""
+    _require_gpu(dy, "dy")
+    _require_gpu(x, "x")
+    lib = load_bwd_library()
+    N, K, dev = dy.shape[-1], x.shape[-1], dy.device
+    if dy.shape[:-1] != x.shape[:-1]:
+        raise ValueError(f"dy and x must share their leading dimensions, got {tuple(dy.shape)} and {tuple(x.shape)}")
+    dyr, M, lddy = _wgrad_rows(dy, "dy")
+    xr, _, ldx = _wgrad_rows(x, "x")
+    if out is None:
+        out = torch.zeros((N, K), dtype=torch.float32, device=dev) if accumulate else torch.empty((N, K), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (N, K) or out.device != dev or (K > 1 and out.stride(1) != 1):
+        raise ValueError(f"out must be an fp32 [{N}, {K}] tensor on {dev} with unit stride inside a row")
+    run, whole = out, None
+    if poison:
+        whole = torch.full((N + 2, K + 8), WGRAD_GUARD, dtype=torch.float32, device=dev)
+        run = whole[1:N + 1, 4:K + 4]
+        run.copy_(out if accumulate else torch.full_like(out, float("nan")))
+    nb = lib.pcad_linear_wgrad_scratch_bytes(M, N, K)
+    scratch = _bwd_scratch(nb, dev, poison)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_linear_wgrad(dyr.data_ptr(), lddy, xr.data_ptr(), ldx, run.data_ptr(), run.stride(0), M, N, K, int(bool(accumulate)), _aligned(scratch), nb, _stream_ptr()), "pcad_linear_wgrad")
+    linear_wgrad.guards_ok = None
+    if poison:
+        with torch.no_grad():
+            out.copy_(run)
+        inner = torch.zeros_like(whole, dtype=torch.bool)
+        inner[1:N + 1, 4:K + 4] = True
+        linear_wgrad.guards_ok = bool((whole[~inner] == WGRAD_GUARD).all())
+    return out
+
+
+linear_wgrad.guards_ok = None       # whether the sentinels of the latest poisoned call are intact (None: it was not poisoned)
+_wgrad_fallback_logged = set()
+
+
+def _main_grad_add(main_grad, dy, x):
+    """main_grad += dy^T x over the rows of dy [..., N] / x [..., K]: pcad_linear_wgrad(accumulate=1) for bf16 device operands and an fp32
+    main_grad inside the kernel's limits; otherwise the same product by torch.addmm on copies in main_grad's dtype (fp32 in training)"""
+    N, K = dy.shape[-1], x.shape[-1]
+    if dy.is_cuda and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and main_grad.dtype == torch.float32 and wgrad_kernel_takes(N, K):
+        linear_wgrad(dy, x, out=main_grad, accumulate=True)
+        return
+    key = (N, K, dy.dtype, str(dy.device.type))
+    if key not in _wgrad_fallback_logged:
+        _wgrad_fallback_logged.add(key)
+        _log.debug("linear_fn: [%d, %d] %s on %s is outside pcad_linear_wgrad's limits; its weight gradient is formed by torch.addmm in %s",
+                   N, K, dy.dtype, dy.device.type, main_grad.dtype)
+    main_grad.addmm_(dy.reshape(-1, N).to(main_grad.dtype).t(), x.reshape(-1, K).to(main_grad.dtype))
+
+
+class _LinearMainGradFn(torch.autograd.Function):
+    """F.linear(x, weight) whose weight gradient goes to weight.main_grad instead of weight.grad: the forward is the stock call,
+    dx = dy W is the stock product, dy^T x is ADDED to main_grad (fp32, never rounded to the weight's dtype) and the weight receives
+    None.  A weight used twice (tied in_proj / out_proj) simply accumulates twice.  Saved: x and weight, through save_for_backward only
+    (gradient checkpointing's hooks see both); main_grad is no activation and rides on ctx."""
+
+    @staticmethod
+    def forward(ctx, x, weight, main_grad):
+        ctx.save_for_backward(x, weight)
+        ctx.main_grad = main_grad
+        return F.linear(x, weight.to(x.dtype))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        # stock F.linear flattens to 2-d, so its backward is this mm on the flattened dy: the same call, the same bits
+        dx = dy.reshape(-1, dy.shape[-1]).mm(weight.to(dy.dtype)).view(x.shape) if ctx.needs_input_grad[0] else None
+        if ctx.needs_input_grad[1]:
+            _main_grad_add(ctx.main_grad, dy, x)
+        return dx, None, None
+
+
+def linear_fn(x, weight):
+    """F.linear(x, weight.to(x.dtype)) for the trainable masked LM's projections.  A weight without a `main_grad` attribute - the
+    default - IS that call: the same autograd node, the gradient in weight.grad.  A weight whose `main_grad` is a tensor of its shape
+    (fp32; optim.AdamW(fp32_grad_accumulation=True) sets it), with grad mode on and the weight requiring grad: the same forward, and
+    the backward adds dy^T x to main_grad - by pcad_linear_wgrad for bf16 operands inside its limits, else by torch.addmm - and leaves
+    weight.grad alone."""
+    mg = getattr(weight, "main_grad", None)
+    if mg is None or not torch.is_grad_enabled() or not weight.requires_grad:
+        return F.linear(x, weight.to(x.dtype))
+    if not isinstance(mg, torch.Tensor) or mg.shape != weight.shape or mg.device != weight.device:
+        raise ValueError(f"main_grad must be a tensor of the weight's shape {tuple(weight.shape)} on {weight.device}")
+    return _LinearMainGradFn.apply(x, weight, mg)

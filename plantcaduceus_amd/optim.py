@@ -40,11 +40,15 @@ class AdamW:
     reducer: a `ddp.GradReducer` for data-parallel training, or None.  With one, `step()` gathers every gradient into the
     reducer's fp32 buffer in one launch, sums that buffer over the ranks, and takes the step on a second table of the same parameters,
     masters and moments whose gradients are the buffer's slices - so the norm, the clipping and the skip rule see the reduced gradients
-    and are the same on every rank.  Without one the class makes exactly the calls it always made."""
+    and are the same on every rank.  Without one the class makes exactly the calls it always made.
+    fp32_grad_accumulation: the gradients live in one fp32 buffer in `ops.grads_flat_plan`'s layout (the reducer's own
+    when there is one), every parameter gets its slice as `p.main_grad`, `ops.linear_fn` adds the projections' weight gradients to the
+    slices unrounded, and a post-accumulate-grad hook adds every other parameter's `.grad` and drops it.  `step()` is the collective (with
+    a reducer) and `adamw_step` on the table of the slices - no gather launch; `zero_grad()` zeroes the slices.  False: nothing changes."""
 
     def __init__(self, params: Iterable[Union[torch.nn.Parameter, Tuple[str, torch.nn.Parameter]]], lr: float = 5e-5,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 1.0,
-                 grad_scale: float = 1.0, reducer=None):
+                 grad_scale: float = 1.0, reducer=None, fp32_grad_accumulation: bool = False):
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.max_grad_norm, self.grad_scale = float(max_grad_norm), float(grad_scale)
         self.names: List[str] = []
@@ -75,13 +79,57 @@ class AdamW:
         self.reducer = reducer
         self._flat_table: Optional[ops.OptimTable] = None
         self.step_count = 0
-        if reducer is not None:
+        self.fp32_grad_accumulation = bool(fp32_grad_accumulation)
+        self.main_grads: Optional[List[torch.Tensor]] = None
+        if self.fp32_grad_accumulation:
+            self._init_main_grads()
+        elif reducer is not None:
             self.table()                                         # the buffer exists from here on: a trainer writes its loss slot before step()
+
+    def _init_main_grads(self):
+        """fp32 main gradients: one flat fp32 buffer in `ops.grads_flat_plan`'s layout - the reducer's own when there is
+        one - whose slices become `p.main_grad`.  `ops.linear_fn` adds the projections' weight gradients to them in the backward; every
+        other parameter's `.grad` is added by a post-accumulate-grad hook and dropped.  The only table is the one on the slices."""
+        dev = self.params[0].device
+        # the plan compares pointers and never reads them: the parameter stands in for a gradient that does not exist
+        records = [(p.data_ptr() or None, p.data_ptr() or None, m.data_ptr() if m is not None and m.numel() else None, a.data_ptr() or None,
+                    v.data_ptr() or None, p.numel(), ops._dt(p), ops._dt(a), ops.OPTIM_DECAY if d else 0)
+                   for p, m, a, v, d in zip(self.params, self.master, self.exp_avg, self.exp_avg_sq, self.decay)]
+        offsets, total = ops.grads_flat_plan(records)
+        if self.reducer is not None:
+            self.reducer.allocate(total)
+            self.flat = self.reducer.grads
+        else:
+            self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.main_grads = [self.flat[o:o + p.numel()].view(p.shape) for o, p in zip(offsets, self.params)]
+
+        def fold(p):
+            if p.grad is None:                                   # a projection routed through ops.linear_fn: autograd was handed None
+                return
+            p.main_grad.add_(p.grad)                             # type promotion: the bf16 gradient is widened, the sum is fp32
+            p.grad = None
+
+        self._hooks = []
+        for p, g in zip(self.params, self.main_grads):
+            p.main_grad = g
+            self._hooks.append(p.register_post_accumulate_grad_hook(fold))
+        self._main_table()
+
+    def _main_table(self) -> ops.OptimTable:
+        now = tuple(p.data_ptr() for p in self.params)
+        if self._table is None or now != self._pointers:
+            self._table = ops.OptimTable([p.data for p in self.params], self.main_grads, self.master, self.exp_avg, self.exp_avg_sq,
+                                         self.decay, state=self._state)
+            self._pointers = now
+        return self._table
 
     def table(self) -> ops.OptimTable:
         """The device table, rebuilt and uploaded again (on the stream, without synchronising) only when a pointer in it has changed.  A
         parameter that has no gradient yet gets a zero one: every tensor of the set takes part in every step.  The per-step check is two
-        data_ptr() calls per tensor and nothing else, so that the host stays ahead of the device."""
+        data_ptr() calls per tensor and nothing else, so that the host stays ahead of the device.  With fp32_grad_accumulation the
+        gradients are the main gradients' slices and no `.grad` is created."""
+        if self.fp32_grad_accumulation:
+            return self._main_table()
         grads = [p.grad for p in self.params]
         now = None
         if not any(g is None for g in grads):
@@ -105,7 +153,11 @@ class AdamW:
         """One step at learning rate `lr` (default: the constructor's).  No host synchronisation (a gloo reducer: one, in its collective)."""
         self.step_count += 1
         table = self.table()
-        if self.reducer is not None:
+        if self.fp32_grad_accumulation:
+            # the main gradients already are the collective's operand: no gather launch, and the table is the one on the slices
+            if self.reducer is not None:
+                self.reducer.all_reduce()
+        elif self.reducer is not None:
             ops.grads_gather(table, self.reducer.grads, table.flat_offsets())
             self.reducer.all_reduce()
             table = self._flat_table
@@ -113,7 +165,9 @@ class AdamW:
                        self.step_count, self.max_grad_norm, self.grad_scale)
 
     def zero_grad(self):
-        """Every gradient set to zero in one launch; the storage stays, so the table stays."""
+        """Every gradient set to zero in one launch; the storage stays, so the table stays.  With fp32_grad_accumulation the gradients
+        are the main gradients' slices: all their elements and nothing beyond them - the padding was zeroed once, the reducer's tail is
+        the trainer's."""
         ops.zero_grads(self.table())
 
     def state(self) -> Dict[str, float]:

@@ -10,7 +10,7 @@ of a node under `torchrun` (below).
         --num_train_epochs 3 | --max_steps N  --lr_scheduler_type linear|cosine|constant|constant_with_warmup \\
         --warmup_steps K | --warmup_ratio R  --mlm_probability 0.15 --soft_masked_loss_weights_train 1.0 \\
         --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16 \\
-        [--gradient_checkpointing] [--ddp_backend nccl|gloo]
+        [--gradient_checkpointing] [--fp32_grad_accumulation] [--ddp_backend nccl|gloo]
     torchrun --nproc-per-node W -m plantcaduceus_amd.pretrain ... (the same flags)
 
 Flag names and defaults are `transformers.TrainingArguments`' and `HF_pre_train.py`'s.  `--config_name` alone starts from scratch:
@@ -37,7 +37,9 @@ Departures from the reference, all stated in DESIGN.md §4o: a step whose gradie
 of letting NaNs into the weights; weight decay leaves out `A_log` and `D` beside biases and norm weights; `--dtype bfloat16` means
 bf16 parameters and kernels with fp32 master weights in the optimizer, where the reference's `bf16=True` is autocast around fp32
 parameters.  `--gradient_checkpointing` (`TrainingArguments`' name and default) keeps only each block's inputs and runs the block again in
-the backward: the same bits for about an eighth of the stored activations.
+the backward: the same bits for about an eighth of the stored activations.  `--fp32_grad_accumulation` (bf16 only) brings
+the gradients back to the reference's fp32: one fp32 buffer holds them, the projections' weight gradients are added to it unrounded by
+`pcad_linear_wgrad`, and micro-batches - and ranks - are summed in fp32.  Checkpoints, resume and logs are unchanged.
 
 Under `torchrun` with world size W an optimizer step consumes the `--gradient_accumulation_steps` x W micro-batches that
 one process with that accumulation would consume, in the same window order and with the same masks: every rank draws all of them (the
@@ -184,6 +186,9 @@ def build_parser():
     p.add_argument("--resume_from_checkpoint", default=None)
     p.add_argument("--gradient_checkpointing", action="store_true",
                    help="keep only each block's inputs and run its forward again in the backward (DESIGN.md §4q): same bits, less memory")
+    p.add_argument("--fp32_grad_accumulation", action="store_true",
+                   help="with --dtype bfloat16: keep the gradients in one fp32 buffer; the projections' weight gradients are added to it "
+                        "unrounded by the weight-gradient MFMA kernel, so micro-batches are summed in fp32 (DESIGN.md §4s)")
     p.add_argument("--ddp_backend", default=None, choices=("nccl", "gloo"),
                    help="under torchrun: nccl (RCCL, one rank per device; the default) or gloo (ranks may share a device; one host "
                         "synchronisation per step); the environment's PCAD_DDP_BACKEND when absent (DESIGN.md §4r)")
@@ -363,6 +368,9 @@ def train(a, rank: int = 0, world: int = 1) -> Dict[str, float]:
     dtype = {"float32": torch.float32, "bfloat16": torch.bfloat16}[a.dtype]
     if a.per_device_train_batch_size < 1 or a.gradient_accumulation_steps < 1:
         raise SystemExit("--per_device_train_batch_size and --gradient_accumulation_steps must be >= 1")
+    main_grads = bool(getattr(a, "fp32_grad_accumulation", False))
+    if main_grads and dtype != torch.bfloat16:
+        raise SystemExit("--fp32_grad_accumulation requires --dtype bfloat16: with float32 parameters the gradients are fp32 already")
     tok = load_tokenizer(a)
     seqs = mlm_eval.load_sequences(a.dataset_name, "train", a.dataset_config_name)
     if a.max_train_samples is not None:
@@ -375,7 +383,7 @@ def train(a, rank: int = 0, world: int = 1) -> Dict[str, float]:
     model = build_model(a, dtype, a.resume_from_checkpoint)
     reducer = ddp.GradReducer(dist.group.WORLD, a.device) if ddp.active() else None
     opt = AdamW(model.named_parameters(), lr=a.learning_rate, betas=(a.adam_beta1, a.adam_beta2), eps=a.adam_epsilon,
-                weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm, reducer=reducer)
+                weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm, reducer=reducer, fp32_grad_accumulation=main_grads)
     tr = Trainer(model, opt, source, tok, a, max_steps, warmup, rank, world)
     if a.resume_from_checkpoint:
         tr.resume(a.resume_from_checkpoint)

@@ -170,7 +170,7 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
         cfg = self.config
         hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, cfg.norm_epsilon, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
         bi = blk.mixer.submodule
-        xz = F.linear(hn, bi.mamba_fwd.in_proj.weight).transpose(1, 2)           # (2B, 2E, L); in_proj is tied
+        xz = ops.linear_fn(hn, bi.mamba_fwd.in_proj.weight).transpose(1, 2)      # (2B, 2E, L); in_proj is tied
         return self._inner(xz, bi.mamba_fwd, False) + self._inner(xz, bi.mamba_rev, True), res
 
     @staticmethod
