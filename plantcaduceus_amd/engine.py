@@ -219,21 +219,28 @@ def build_library(force: bool = False) -> str:
     return LIB_PATH
 
 
+def _bind_library(path: str, signatures, missing_message: str):
+    """CDLL(path) with restype / argtypes set for every symbol of `signatures`; a missing file raises RuntimeError(missing_message),
+    a missing symbol AttributeError"""
+    if not os.path.exists(path):
+        raise RuntimeError(missing_message)
+    lib = C.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load_library():
     """Load libpcad.so; fails loudly if it is missing (no CPU fallback on the product path)."""
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} not found: the MI355X HIP extension is not built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C plantcaduceus_amd/csrc`). "
-            "There is deliberately no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)   # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    lib = _bind_library(LIB_PATH, SIGNATURES,
+                        f"{LIB_PATH} not found: the MI355X HIP extension is not built. Run "
+                        "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C plantcaduceus_amd/csrc`). "
+                        "There is deliberately no CPU fallback.")
     # a binary that was not built from the sources beside it would silently run (and be benchmarked as) other kernels
     if os.path.exists(os.path.join(CSRC, "source_hash.py")) and os.environ.get("PCAD_ALLOW_STALE") != "1":
         built, have = lib.pcad_build_hash().decode(), source_hash()
@@ -245,46 +252,27 @@ def load_library():
     return lib
 
 
-_train_lib = None
+_backward_libs = {}      # path -> the loaded library, once per process
+
+
+def _load_beside(path: str, signatures):
+    """a backward library beside libpcad.so, which it links and which is loaded first"""
+    if path not in _backward_libs:
+        load_library()
+        _backward_libs[path] = _bind_library(path, signatures, f"{path} not found: build it with `make -C plantcaduceus_amd/csrc` / "
+                                                                "`__graft_entry__.build()`")
+    return _backward_libs[path]
 
 
 def load_train_library():
     """Load libpcad_train.so (include/pcad_train.h) beside libpcad.so, which it links and which is loaded first; fails loudly if it
     is missing - a missing backward kernel is an error, there is no fallback to torch."""
-    global _train_lib
-    if _train_lib is not None:
-        return _train_lib
-    load_library()
-    if not os.path.exists(TRAIN_LIB_PATH):
-        raise RuntimeError(f"{TRAIN_LIB_PATH} not found: build it with `make -C plantcaduceus_amd/csrc` / `__graft_entry__.build()`")
-    lib = C.CDLL(TRAIN_LIB_PATH)
-    for name, (res, args) in TRAIN_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _train_lib = lib
-    return lib
-
-
-_bwd_lib = None
+    return _load_beside(TRAIN_LIB_PATH, TRAIN_SIGNATURES)
 
 
 def load_bwd_library():
-    """Load libpcad_bwd.so (include/pcad_bwd.h) beside libpcad.so, which it links and which is loaded first; fails loudly if it is
-    missing - a missing backward kernel is an error, there is no fallback to torch."""
-    global _bwd_lib
-    if _bwd_lib is not None:
-        return _bwd_lib
-    load_library()
-    if not os.path.exists(BWD_LIB_PATH):
-        raise RuntimeError(f"{BWD_LIB_PATH} not found: build it with `make -C plantcaduceus_amd/csrc` / `__graft_entry__.build()`")
-    lib = C.CDLL(BWD_LIB_PATH)
-    for name, (res, args) in BWD_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _bwd_lib = lib
-    return lib
+    """Load libpcad_bwd.so (include/pcad_bwd.h), likewise."""
+    return _load_beside(BWD_LIB_PATH, BWD_SIGNATURES)
 
 
 def _check(code: int, what: str):

@@ -23,20 +23,112 @@ carries an fp32 `main_grad` its backward adds dy^T x to that buffer with linear_
 """
 from __future__ import annotations
 
+import ctypes as C
 import logging
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
 
 import torch.nn.functional as F
 
-from .engine import _DT, _check, _require_gpu, _stream_ptr, load_bwd_library, load_library, load_train_library
+from .engine import (MAX_LABELS, POOLING, _DT, _check, _require_gpu, _stream_ptr, load_bwd_library, load_library,
+                     load_train_library)
 
 
 def _dt(t: torch.Tensor) -> int:
     if t.dtype not in _DT:
         raise ValueError(f"unsupported dtype {t.dtype}")
     return _DT[t.dtype]
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    """an optional operand as the C ABI takes it: its address, or NULL"""
+    return t.data_ptr() if t is not None else None
+
+
+def _round_up(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+def _scratch(nb: int, dev, poison: bool = False):
+    """a scratch of nb bytes -> (the uint8 tensor that keeps the memory alive, the 256-byte aligned address of nb bytes inside it).
+    poison (tests): every byte starts as 0xFF - NaN in fp32 and bf16 -, so that a slot read without having been written shows."""
+    if poison:
+        buf = torch.full((nb + 256,), 0xFF, dtype=torch.uint8, device=dev)
+    else:
+        buf = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+    return buf, _round_up(buf.data_ptr(), 256)
+
+
+# ---- guarded outputs (the poison forms, tests): an output is NaN where the kernel must write it and lies inside a larger buffer of
+# ---- sentinels, so that a row the kernel skipped and a store outside the output both show -------------------------------------------
+GUARD = -1024.0          # the sentinel: exact in bf16 and fp32
+OPTIM_GUARD = 64         # sentinel elements around every output of the optimizer's poison forms (a multiple of 16 bytes in either dtype)
+
+
+def _guard_elems(shape, geometry: str) -> int:
+    """sentinel elements before and after an output of `shape`.  "row": one row of the output, as many elements as its last dimension;
+    "lines": the row rounded up to whole 128-byte lines of bf16, so that a GEMM output keeps its alignment; "optim": OPTIM_GUARD."""
+    return {"row": shape[-1], "lines": _round_up(shape[-1], 64), "optim": OPTIM_GUARD}[geometry]
+
+
+def _guarded(shape, dtype, dev, geometry: str = "row", poison: bool = True):
+    """an output buffer -> (tensor of `shape`, the whole buffer or None).  poison: NaN inside, `_guard_elems` sentinels before and after;
+    else plain torch.empty and no buffer around it."""
+    if not poison:
+        return torch.empty(shape, dtype=dtype, device=dev), None
+    n, g = 1, _guard_elems(shape, geometry)
+    for k in shape:
+        n *= k
+    whole = torch.full((n + 2 * g,), GUARD, dtype=dtype, device=dev)
+    whole[g:g + n] = float("nan")
+    return whole[g:g + n].view(shape), whole
+
+
+def _guarded_copy(t: torch.Tensor, geometry: str = "optim"):
+    """-> (a copy of t between sentinels, the whole buffer)"""
+    c, whole = _guarded(t.shape, t.dtype, t.device, geometry)
+    c.copy_(t.detach())
+    return c, whole
+
+
+def _guards_intact(outs) -> bool:
+    """outs: (tensor, whole buffer or None) pairs: whether every element of a whole buffer outside its tensor still is the sentinel
+    (the tensor any view of the buffer: `_guarded`'s, or linear_wgrad's 2-D frame).  Reads the device; free without buffers."""
+    ok = True
+    for t, whole in outs:
+        if whole is not None:
+            outside = torch.ones_like(whole, dtype=torch.bool)
+            outside.as_strided(t.shape, t.stride(), t.storage_offset()).fill_(False)
+            ok = ok and bool((whole[outside] == GUARD).all())
+    return ok
+
+
+def _guarded_copies(tensors, back, blank: bool = False):
+    """the poison forms of the in-place operators run on copies: -> one copy between OPTIM_GUARD sentinels per tensor (None stays None;
+    blank: NaN instead of the tensor's values); `back` collects the (tensor, copy, whole buffer) triples `_copy_back` takes"""
+    copies = []
+    for t in tensors:
+        c = None
+        if t is not None:
+            c, whole = _guarded(t.shape, t.dtype, t.device, "optim") if blank else _guarded_copy(t)
+            back.append((t, c, whole))
+        copies.append(c)
+    return copies
+
+
+def _copy_back(back) -> bool:
+    """the results of a poisoned run from the copies into the tensors they stand for -> whether all sentinels are intact"""
+    with torch.no_grad():
+        for t, c, _ in back:
+            t.copy_(c)
+    return _guards_intact([(c, whole) for _, c, whole in back])
+
+
+def _residual_dtype(x_dtype, residual_in_fp32):
+    """the dtype of the residual stream: fp32 with residual_in_fp32 or an fp32 x, else x's"""
+    return torch.float32 if (residual_in_fp32 or x_dtype == torch.float32) else x_dtype
 
 
 def rms_norm_fn(x, weight, bias=None, residual=None, eps=1e-6, prenorm=False, residual_in_fp32=False):
@@ -47,7 +139,7 @@ def rms_norm_fn(x, weight, bias=None, residual=None, eps=1e-6, prenorm=False, re
         raise NotImplementedError("RMSNorm bias is not used by Caduceus")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, residual)):
         # the casts stay torch ops outside the Function, so that autograd returns each gradient in its input's dtype
-        rdt = torch.float32 if (residual_in_fp32 or x.dtype == torch.float32) else x.dtype
+        rdt = _residual_dtype(x.dtype, residual_in_fp32)
         y, res_out = _RmsNormFn.apply(x, weight.float(), residual.to(rdt) if residual is not None else None, float(eps),
                                       bool(residual_in_fp32))
         return (y, res_out) if prenorm else y
@@ -59,19 +151,21 @@ def _rms_norm_forward(x, weight, residual, eps, prenorm, residual_in_fp32):
     D = x.shape[-1]
     xf = x.contiguous().view(-1, D)
     rows = xf.shape[0]
-    rdt = torch.float32 if (residual_in_fp32 or x.dtype == torch.float32) else x.dtype
-    res_in = None
-    if residual is not None:
-        res_in = residual.to(rdt).contiguous().view(-1, D)
+    rdt = _residual_dtype(x.dtype, residual_in_fp32)
+    res_in = residual.to(rdt).contiguous().view(-1, D) if residual is not None else None
     y = torch.empty_like(xf)
     res_out = torch.empty((rows, D), dtype=rdt, device=x.device)
     w = weight.float().contiguous()
     with torch.cuda.device(x.device):
-        _check(lib.pcad_add_rmsnorm(xf.data_ptr(), res_in.data_ptr() if res_in is not None else None, w.data_ptr(),
-                                    y.data_ptr(), res_out.data_ptr(), rows, D, float(eps), _dt(xf), _DT[rdt],
-                                    _stream_ptr()), "pcad_add_rmsnorm")
+        _check(lib.pcad_add_rmsnorm(xf.data_ptr(), _ptr(res_in), w.data_ptr(), y.data_ptr(), res_out.data_ptr(), rows, D, float(eps),
+                                    _dt(xf), _DT[rdt], _stream_ptr()), "pcad_add_rmsnorm")
     y = y.view(x.shape)
     return (y, res_out.view(x.shape)) if prenorm else y
+
+
+def _conv_taps(E, w_fwd, b_fwd, w_rev, b_rev):
+    """the conv parameters of both directions as the kernels take them: fp32 (w_fwd [E, 4], b_fwd [E], w_rev [E, 4], b_rev [E])"""
+    return [t.float().contiguous() for t in (w_fwd.reshape(E, -1), b_fwd, w_rev.reshape(E, -1), b_rev)]
 
 
 def causal_conv1d_bidir(x_tm, w_fwd, b_fwd, w_rev, b_rev):
@@ -82,10 +176,9 @@ def causal_conv1d_bidir(x_tm, w_fwd, b_fwd, w_rev, b_rev):
     x_tm = x_tm.contiguous()
     yf = torch.empty_like(x_tm)
     yr = torch.empty_like(x_tm)
-    args = [t.float().contiguous() for t in (w_fwd.reshape(E, -1), b_fwd, w_rev.reshape(E, -1), b_rev)]
+    taps = _conv_taps(E, w_fwd, b_fwd, w_rev, b_rev)
     with torch.cuda.device(x_tm.device):
-        _check(lib.pcad_causal_conv1d_silu(x_tm.data_ptr(), E, args[0].data_ptr(), args[1].data_ptr(),
-                                           args[2].data_ptr(), args[3].data_ptr(), yf.data_ptr(), yr.data_ptr(),
+        _check(lib.pcad_causal_conv1d_silu(x_tm.data_ptr(), E, *[t.data_ptr() for t in taps], yf.data_ptr(), yr.data_ptr(),
                                            S, L, E, _dt(x_tm), _stream_ptr()), "pcad_causal_conv1d_silu")
     return yf, yr
 
@@ -96,7 +189,7 @@ def to_blocked(x_rows: torch.Tensor, pad_value: float = 0.0) -> torch.Tensor:
     per = 128 // x_rows.element_size()
     if E % per:
         raise ValueError("E * elem must be a multiple of 128 bytes")
-    rows8 = (rows + 7) // 8 * 8
+    rows8 = _round_up(rows, 8)
     buf = torch.full((rows8, E), pad_value, dtype=x_rows.dtype, device=x_rows.device)
     buf[:rows] = x_rows
     return buf.view(rows8 // 8, 8, E // per, per).permute(0, 2, 1, 3).contiguous()
@@ -105,6 +198,12 @@ def to_blocked(x_rows: torch.Tensor, pad_value: float = 0.0) -> torch.Tensor:
 def from_blocked(xb: torch.Tensor, rows: int) -> torch.Tensor:
     nb, pieces, _, per = xb.shape
     return xb.permute(0, 2, 1, 3).reshape(nb * 8, pieces * per)[:rows].contiguous()
+
+
+def _split_blocked(xb: torch.Tensor, rows: int):
+    """a blocked buffer -> (its `rows` rows as plain rows, its padding rows)"""
+    full = from_blocked(xb, xb.shape[0] * 8)
+    return full[:rows].contiguous(), full[rows:].contiguous()
 
 
 def causal_conv1d_dir(x_tm, weight, bias, reverse: bool = False, blocked: bool = False):
@@ -127,16 +226,37 @@ def _causal_conv1d_dir_forward(x_tm, weight, bias, reverse, blocked):
     w = weight.reshape(E, -1).float().contiguous()
     b = bias.float().contiguous()
     with torch.cuda.device(x_tm.device):
-        if blocked:
-            xin = to_blocked(x_tm.reshape(S * L, E))
-            # NaN where the kernel must write, so that a row it skipped shows; the padding rows are not its to write
-            yb = torch.full_like(xin, float("nan"))
-        else:
-            xin = x_tm.contiguous()
-            yb = torch.full_like(xin, float("nan"))
+        xin = to_blocked(x_tm.reshape(S * L, E)) if blocked else x_tm.contiguous()
+        # NaN where the kernel must write, so that a row it skipped shows; a blocked buffer's padding rows are not its to write
+        yb = torch.full_like(xin, float("nan"))
         _check(lib.pcad_causal_conv1d_silu_dir(xin.data_ptr(), E, w.data_ptr(), b.data_ptr(), yb.data_ptr(), E, S, L, E, int(bool(reverse)),
                                                int(blocked), int(blocked), _dt(x_tm), _stream_ptr()), "pcad_causal_conv1d_silu_dir")
     return from_blocked(yb, S * L).view(S, L, E) if blocked else yb
+
+
+def padded_dt_rank(R: int) -> int:
+    """csrc/kernels.hpp padded_dt_rank: the columns dt_low and W_dt are zero padded to - 64, beyond that a multiple of 32"""
+    return 64 if R <= 64 else _round_up(R, 32)
+
+
+def pack_x_proj(w, R: int, Rp: int, E: int, dtype, dev):
+    """x_proj's weight [R + 32, E] as the fused kernel takes it, [Rp + 32, E] in `dtype`: the dt rows, zero rows up to Rp, the B | C rows"""
+    p = torch.zeros((Rp + 32, E), dtype=dtype, device=dev)
+    p[:R] = w[:R].to(dtype)
+    p[Rp:] = w[R:].to(dtype)
+    return p
+
+
+def _conv_xproj_operands(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev):
+    """what both forms of the fused conv + x_proj take: -> (x blocked, the conv taps, the packed x_proj weights (fwd, rev), R, Rp)"""
+    S, L, E = x_tm.shape
+    R = x_proj_fwd.shape[0] - 32
+    if not 0 < R <= 96:
+        raise ValueError("dt_rank must be in [1, 96] for the fused kernel")
+    Rp = padded_dt_rank(R)
+    xb = to_blocked(x_tm.reshape(S * L, E))
+    wx = [pack_x_proj(w, R, Rp, E, x_tm.dtype, x_tm.device) for w in (x_proj_fwd, x_proj_rev)]
+    return xb, _conv_taps(E, w_fwd, b_fwd, w_rev, b_rev), wx, R, Rp
 
 
 def _conv_xproj_raw(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev):
@@ -144,29 +264,14 @@ def _conv_xproj_raw(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev):
     _require_gpu(x_tm, "x")
     lib = load_library()
     S, L, E = x_tm.shape
-    dt, dev = x_tm.dtype, x_tm.device
-    R = x_proj_fwd.shape[0] - 32
-    if not 0 < R <= 96:
-        raise ValueError("dt_rank must be in [1, 96] for the fused kernel")
-    Rp = 64 if R <= 64 else 96
-    rows = S * L
-    xb = to_blocked(x_tm.reshape(rows, E))
-
-    def pack_wx(w):
-        p = torch.zeros((Rp + 32, E), dtype=dt, device=dev)
-        p[:R] = w[:R].to(dt)
-        p[Rp:] = w[R:].to(dt)
-        return p
-    wx = [pack_wx(x_proj_fwd), pack_wx(x_proj_rev)]
-    taps = [t.float().contiguous() for t in (w_fwd.reshape(E, -1), b_fwd, w_rev.reshape(E, -1), b_rev)]
-    scratch = torch.empty(lib.pcad_conv_xproj_scratch_bytes(E, _DT[dt]) + 256, dtype=torch.uint8, device=dev)
+    dt, dev, rows = x_tm.dtype, x_tm.device, S * L
+    xb, taps, wx, R, Rp = _conv_xproj_operands(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev)
+    scratch, scratch_ptr = _scratch(lib.pcad_conv_xproj_scratch_bytes(E, _DT[dt]), dev)
     xc = [torch.zeros_like(xb) for _ in range(2)]
     dtl = [torch.empty((rows, Rp), dtype=dt, device=dev) for _ in range(2)]
     bc = [torch.empty((rows, 32), dtype=torch.float32, device=dev) for _ in range(2)]
     with torch.cuda.device(dev):
-        _check(lib.pcad_conv_xproj_bidir(xb.data_ptr(), taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(),
-                                         taps[3].data_ptr(), wx[0].data_ptr(), wx[1].data_ptr(),
-                                         (scratch.data_ptr() + 255) // 256 * 256,
+        _check(lib.pcad_conv_xproj_bidir(xb.data_ptr(), *[t.data_ptr() for t in taps], wx[0].data_ptr(), wx[1].data_ptr(), scratch_ptr,
                                          xc[0].data_ptr(), dtl[0].data_ptr(), bc[0].data_ptr(),
                                          xc[1].data_ptr(), dtl[1].data_ptr(), bc[1].data_ptr(),
                                          S, L, E, Rp, _DT[dt], _stream_ptr()), "pcad_conv_xproj_bidir")
@@ -191,14 +296,6 @@ def conv_xproj_bidir(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev):
 # ---- the engine's launch forms as operators (include/pcad.h pcad_*_engine / pcad_selective_scan_pair) ----------------------------
 # Token-major tensors in and out; the blocked layouts are made and undone here.  Every output buffer starts as NaN where the kernel
 # must write it, so that a row it skipped - or a scratch slot it read without writing - shows.
-def _aligned(t: torch.Tensor) -> int:
-    return (t.data_ptr() + 255) // 256 * 256
-
-
-def _nan_bytes(n: int, dev) -> torch.Tensor:
-    return torch.full((n + 256,), 0xFF, dtype=torch.uint8, device=dev)      # 0xFF bytes: NaN in fp32 and bf16
-
-
 def _y_blocked(y_prior, S, L, E, dt, dev):
     """the blocked y buffer: the caller's prior content (accumulate modes, walk_len), else NaN; padding rows always NaN"""
     if y_prior is None:
@@ -206,10 +303,20 @@ def _y_blocked(y_prior, S, L, E, dt, dev):
     return to_blocked(y_prior.to(dt).reshape(S * L, E), pad_value=float("nan"))
 
 
-def _decode_ysplit(ysb, rows, S, L, E):
-    """bf16 [rows8, 2E] blocked = [hi | lo] -> (hi, lo) [S, L, E] bf16"""
-    flat = from_blocked(ysb, rows)
-    return flat[:, :E].reshape(S, L, E), flat[:, E:].reshape(S, L, E)
+def _ysplit_buffer(rows, E, dev):
+    """the ysplit output, NaN: bf16 [rows8, 2E] blocked = [hi | lo]"""
+    return torch.full((_round_up(rows, 8) // 8, 2 * E * 2 // 128, 8, 64), float("nan"), dtype=torch.bfloat16, device=dev)
+
+
+def _decode_y(yb, ysb, S, L, E):
+    """the scan forms' blocked outputs -> dict(y [S, L, E], pad: the blocked y buffer's padding rows, hi / lo [S, L, E] bf16: the halves
+    of the ysplit buffer, None without one)"""
+    y, pad = _split_blocked(yb, S * L)
+    hi = lo = None
+    if ysb is not None:
+        flat = from_blocked(ysb, S * L)
+        hi, lo = flat[:, :E].reshape(S, L, E), flat[:, E:].reshape(S, L, E)
+    return dict(y=y.view(S, L, E), pad=pad, hi=hi, lo=lo)
 
 
 def selective_scan_engine(u, dt_low, Wdt, Rp, bc, A2, D, delta_bias, z=None, y_prior=None, reverse=False, accumulate=0, a_scale=1.0,
@@ -220,7 +327,6 @@ def selective_scan_engine(u, dt_low, Wdt, Rp, bc, A2, D, delta_bias, z=None, y_p
     segmented: hand over the segment scratch (whether the walk is then cut is the library's policy for the shape, see
     pcad_scan_segment_scratch_bytes).  -> namespace(y [S, L, E], pad: the blocked y buffer's padding rows, hi / lo [S, L, E] bf16 or
     None: the ysplit output, seg_bytes)."""
-    from types import SimpleNamespace
     _require_gpu(u, "u")
     lib = load_library()
     S, L, E = u.shape
@@ -231,26 +337,20 @@ def selective_scan_engine(u, dt_low, Wdt, Rp, bc, A2, D, delta_bias, z=None, y_p
     dl, W = dt_low.contiguous(), Wdt.contiguous()
     f32 = [t.float().contiguous() for t in (bc, A2, D, delta_bias)]
     seg_bytes = lib.pcad_scan_segment_scratch_bytes(S, L, E, policy_S)
-    seg = _nan_bytes(seg_bytes, dev) if segmented else None
-    ysb = None
-    if ysplit:
-        ysb = torch.full(((rows + 7) // 8, 2 * E * 2 // 128, 8, 64), float("nan"), dtype=torch.bfloat16, device=dev)
+    seg, seg_ptr = _scratch(seg_bytes, dev, poison=True) if segmented else (None, None)
+    ysb = _ysplit_buffer(rows, E, dev) if ysplit else None
     with torch.cuda.device(dev):
-        _check(lib.pcad_selective_scan_engine(ub.data_ptr(), dl.data_ptr(), dl.shape[-1], W.data_ptr(), Rp, zb.data_ptr() if zb is not None else None,
+        _check(lib.pcad_selective_scan_engine(ub.data_ptr(), dl.data_ptr(), dl.shape[-1], W.data_ptr(), Rp, _ptr(zb),
                                               f32[0].data_ptr(), f32[1].data_ptr(), float(a_scale), f32[2].data_ptr(), f32[3].data_ptr(),
-                                              yb.data_ptr(), ysb.data_ptr() if ysb is not None else None,
-                                              _aligned(seg) if seg is not None else None, seg_bytes, policy_S, walk_len, int(bool(dt_split)),
+                                              yb.data_ptr(), _ptr(ysb), seg_ptr, seg_bytes, policy_S, walk_len, int(bool(dt_split)),
                                               S, L, E, int(bool(reverse)), accumulate, _dt(u), _stream_ptr()), "pcad_selective_scan_engine")
-    flat = yb.permute(0, 2, 1, 3).reshape(-1, E)
-    hi, lo = _decode_ysplit(ysb, rows, S, L, E) if ysb is not None else (None, None)
-    return SimpleNamespace(y=flat[:rows].reshape(S, L, E).contiguous(), pad=flat[rows:].contiguous(), hi=hi, lo=lo, seg_bytes=seg_bytes)
+    return SimpleNamespace(**_decode_y(yb, ysb, S, L, E), seg_bytes=seg_bytes)
 
 
 def selective_scan_pair(fwd, rev, z, Rp, gate_each=False, phases=(3,), ysplit=False, dt_split=False):
     """pcad_selective_scan_pair: both directions in one launch, half a strand each.  fwd / rev: dicts of one direction's operands
     (u [S, L, E], dt_low, Wdt, bc, A2 - scaled by log2(e) -, D, delta_bias, as selective_scan_engine takes them); z [S, L, E].
     phases: the calls to issue in order, (1, 2) as the engine does or (3,).  -> namespace(y [S, L, E], pad, hi, lo)."""
-    from types import SimpleNamespace
     _require_gpu(z, "z")
     lib = load_library()
     S, L, E = z.shape
@@ -262,19 +362,14 @@ def selective_scan_pair(fwd, rev, z, Rp, gate_each=False, phases=(3,), ysplit=Fa
     zb = to_blocked(z.reshape(rows, E))
     yb = _y_blocked(None, S, L, E, dt, dev)
     ws_bytes = lib.pcad_scan_pair_scratch_bytes(S, E)
-    ws = _nan_bytes(ws_bytes, dev)
-    ysb = None
-    if ysplit:
-        ysb = torch.full(((rows + 7) // 8, 2 * E * 2 // 128, 8, 64), float("nan"), dtype=torch.bfloat16, device=dev)
+    ws, ws_ptr = _scratch(ws_bytes, dev, poison=True)
+    ysb = _ysplit_buffer(rows, E, dev) if ysplit else None
     with torch.cuda.device(dev):
         for ph in phases:
             _check(lib.pcad_selective_scan_pair(*[t.data_ptr() for t in ops], zb.data_ptr(), fwd["dt_low"].shape[-1], Rp, yb.data_ptr(),
-                                                ysb.data_ptr() if ysb is not None else None, _aligned(ws), ws_bytes, S, L, E,
-                                                int(bool(gate_each)), int(ph), int(bool(dt_split)), _DT[dt], _stream_ptr()),
-                   "pcad_selective_scan_pair")
-    flat = yb.permute(0, 2, 1, 3).reshape(-1, E)
-    hi, lo = _decode_ysplit(ysb, rows, S, L, E) if ysb is not None else (None, None)
-    return SimpleNamespace(y=flat[:rows].reshape(S, L, E).contiguous(), pad=flat[rows:].contiguous(), hi=hi, lo=lo)
+                                                _ptr(ysb), ws_ptr, ws_bytes, S, L, E, int(bool(gate_each)), int(ph), int(bool(dt_split)),
+                                                _DT[dt], _stream_ptr()), "pcad_selective_scan_pair")
+    return SimpleNamespace(**_decode_y(yb, ysb, S, L, E))
 
 
 def conv_xproj_bidir_engine(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev, ksplit=True, policy_S=0, split=False):
@@ -282,28 +377,15 @@ def conv_xproj_bidir_engine(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj
     scratch (whether the launch is then split is the library's policy for the shape); split (fp32): dtl_split + w_split.
     -> namespace(xc (fwd, rev) [S, L, E]; dtl (fwd, rev): [S*L, Rp] in x's dtype, or - split - bf16 [S*L, 2 Rp] = [hi | lo];
                  bc (fwd, rev) fp32 [S*L, 32]; R, Rp; part_bytes: the K-split scratch of this shape, 0 = not split)."""
-    from types import SimpleNamespace
     _require_gpu(x_tm, "x")
     lib = load_library()
     S, L, E = x_tm.shape
     dt, dev, rows = x_tm.dtype, x_tm.device, S * L
-    R = x_proj_fwd.shape[0] - 32
-    if not 0 < R <= 96:
-        raise ValueError("dt_rank must be in [1, 96] for the fused kernel")
-    Rp = 64 if R <= 64 else 96
-    xb = to_blocked(x_tm.reshape(rows, E))
-
-    def pack_wx(w):
-        p = torch.zeros((Rp + 32, E), dtype=dt, device=dev)
-        p[:R] = w[:R].to(dt)
-        p[Rp:] = w[R:].to(dt)
-        return p
-    wx = [pack_wx(x_proj_fwd), pack_wx(x_proj_rev)]
-    taps = [t.float().contiguous() for t in (w_fwd.reshape(E, -1), b_fwd, w_rev.reshape(E, -1), b_rev)]
-    sb = (lib.pcad_conv_xproj_scratch_bytes(E, _DT[dt]) + 255) // 256 * 256 + (2 * (Rp + 32) * 2 * E * 2 if split else 0)
-    scratch = torch.empty(sb + 256, dtype=torch.uint8, device=dev)
+    xb, taps, wx, R, Rp = _conv_xproj_operands(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj_rev)
+    sb = _round_up(lib.pcad_conv_xproj_scratch_bytes(E, _DT[dt]), 256) + (2 * (Rp + 32) * 2 * E * 2 if split else 0)
+    scratch, scratch_ptr = _scratch(sb, dev)
     part_bytes = lib.pcad_conv_xproj_split_scratch_bytes(S, L, E, _DT[dt], Rp, policy_S)
-    part = _nan_bytes(part_bytes, dev) if ksplit else None
+    part, part_ptr = _scratch(part_bytes, dev, poison=True) if ksplit else (None, None)
     xc = [torch.full_like(xb, float("nan")) for _ in range(2)]
     if split:
         dtl = [torch.full((rows, 2 * Rp), float("nan"), dtype=torch.bfloat16, device=dev) for _ in range(2)]
@@ -311,10 +393,9 @@ def conv_xproj_bidir_engine(x_tm, w_fwd, b_fwd, w_rev, b_rev, x_proj_fwd, x_proj
         dtl = [torch.full((rows, Rp), float("nan"), dtype=dt, device=dev) for _ in range(2)]
     bc = [torch.full((rows, 32), float("nan"), dtype=torch.float32, device=dev) for _ in range(2)]
     with torch.cuda.device(dev):
-        _check(lib.pcad_conv_xproj_bidir_engine(xb.data_ptr(), taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(), taps[3].data_ptr(),
-                                                wx[0].data_ptr(), wx[1].data_ptr(), _aligned(scratch), sb,
+        _check(lib.pcad_conv_xproj_bidir_engine(xb.data_ptr(), *[t.data_ptr() for t in taps], wx[0].data_ptr(), wx[1].data_ptr(), scratch_ptr, sb,
                                                 xc[0].data_ptr(), dtl[0].data_ptr(), bc[0].data_ptr(), xc[1].data_ptr(), dtl[1].data_ptr(),
-                                                bc[1].data_ptr(), _aligned(part) if part is not None else None, part_bytes, policy_S,
+                                                bc[1].data_ptr(), part_ptr, part_bytes, policy_S,
                                                 int(bool(split)), int(bool(split)), S, L, E, Rp, _DT[dt], _stream_ptr()),
                "pcad_conv_xproj_bidir_engine")
     return SimpleNamespace(xc=tuple(from_blocked(c, rows).view(S, L, E) for c in xc), dtl=tuple(dtl), bc=tuple(bc), R=R, Rp=Rp,
@@ -344,10 +425,15 @@ def _scan_common(u, B, C, A, D, z, delta_bias):
     z_tm = z.to(dt).transpose(1, 2).contiguous() if z is not None else None
     # B_t | C_t rows in fp32 holding the values at the model dtype's precision (what the x_proj epilogue writes)
     bc = torch.cat([B.to(dt).transpose(1, 2), C.to(dt).transpose(1, 2)], dim=-1).float().contiguous()   # [B, L, 32]
+    return (u_tm, z_tm, bc) + _scan_params(A, D, delta_bias, E, u.device)
+
+
+def _scan_params(A, D, delta_bias, E, dev):
+    """A, D and delta_bias as the scan kernels take them: fp32, a missing D or delta_bias as zeros"""
     A32 = A.float().contiguous()
-    Dv = (D.float() if D is not None else torch.zeros(E, device=u.device)).contiguous()
-    db = (delta_bias.float() if delta_bias is not None else torch.zeros(E, device=u.device)).contiguous()
-    return u_tm, z_tm, bc, A32, Dv, db
+    Dv = (D.float() if D is not None else torch.zeros(E, device=dev)).contiguous()
+    db = (delta_bias.float() if delta_bias is not None else torch.zeros(E, device=dev)).contiguous()
+    return A32, Dv, db
 
 
 def _acc_mode(accumulate_into, gate_sum) -> int:
@@ -361,25 +447,11 @@ def _acc_mode(accumulate_into, gate_sum) -> int:
 SCAN_BWD_CHUNK = 8       # csrc/kernels.hpp SCAN_BWD_CHUNK: walk steps between two states the backward stores (and re-runs at once)
 
 
-def _guarded(shape, dtype, dev, guard):
-    """an output buffer; guard: NaN where the kernel must write, between one row of sentinels before and one after.
-    -> (tensor of `shape`, the whole buffer or None)"""
-    if not guard:
-        return torch.empty(shape, dtype=dtype, device=dev), None
-    row, n = shape[-1], 1
-    for k in shape:
-        n *= k
-    whole = torch.full((n + 2 * row,), -1234.0, dtype=dtype, device=dev)
-    whole[row:row + n] = float("nan")
-    return whole[row:row + n].view(shape), whole
-
-
 def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False, poison=False):
     """pcad_selective_scan_bwd on selective_scan_fn's operands (upstream layouts; D, z, delta_bias may be None) and dout (B, E, L).
     -> namespace(du, ddelta, dz (B, E, L) in u's dtype (dz None without z); dB, dC fp32 (B, 16, L); dA fp32 (E, 16); dD, ddelta_bias fp32
     (E); guards_ok).  poison (tests): the scratch starts as 0xFF bytes and every output as NaN inside a larger buffer with one row of
     sentinels before and after it; guards_ok tells whether all sentinels are intact afterwards."""
-    from types import SimpleNamespace
     _require_gpu(u, "u")
     lib = load_train_library()
     Bsz, E, L = u.shape
@@ -388,52 +460,32 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False,
     d_tm = delta.to(dt).transpose(1, 2).contiguous()
     g_tm = dout.to(dt).transpose(1, 2).contiguous()
     f32 = torch.float32
-    outs = [_guarded(sh, ty, dev, poison) for sh, ty in (((Bsz, L, E), dt), ((Bsz, L, E), dt), ((Bsz, L, E), dt), ((Bsz, L, 32), f32),
-                                                         ((E, 16), f32), ((E,), f32), ((E,), f32))]
+    outs = [_guarded(sh, ty, dev, "row", poison) for sh, ty in (((Bsz, L, E), dt), ((Bsz, L, E), dt), ((Bsz, L, E), dt), ((Bsz, L, 32), f32),
+                                                                ((E, 16), f32), ((E,), f32), ((E,), f32))]
     du, dd, dz, dbc, dA, dD, dbias = [o[0] for o in outs]
     if z_tm is None:
         dz = None
     nb = lib.pcad_selective_scan_bwd_scratch_bytes(Bsz, L, E)
-    scratch = _nan_bytes(nb, dev) if poison else torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
-        _check(lib.pcad_selective_scan_bwd(u_tm.data_ptr(), d_tm.data_ptr(), z_tm.data_ptr() if z_tm is not None else None, E,
+        _check(lib.pcad_selective_scan_bwd(u_tm.data_ptr(), d_tm.data_ptr(), _ptr(z_tm), E,
                                            bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), g_tm.data_ptr(),
-                                           du.data_ptr(), dd.data_ptr(), dz.data_ptr() if dz is not None else None, dbc.data_ptr(),
-                                           dA.data_ptr(), dD.data_ptr(), dbias.data_ptr(), _aligned(scratch), nb, Bsz, L, E,
+                                           du.data_ptr(), dd.data_ptr(), _ptr(dz), dbc.data_ptr(),
+                                           dA.data_ptr(), dD.data_ptr(), dbias.data_ptr(), scratch_ptr, nb, Bsz, L, E,
                                            int(bool(reverse)), _dt(u_tm), _stream_ptr()), "pcad_selective_scan_bwd")
-    ok = True
-    for t, whole in outs:
-        if whole is not None:
-            row = t.shape[-1]
-            ok = ok and bool((whole[:row] == -1234.0).all()) and bool((whole[row + t.numel():] == -1234.0).all())
     return SimpleNamespace(du=du.transpose(1, 2), ddelta=dd.transpose(1, 2), dz=dz.transpose(1, 2) if dz is not None else None,
                            dB=dbc[..., :16].transpose(1, 2), dC=dbc[..., 16:].transpose(1, 2), dA=dA, dD=dD, ddelta_bias=dbias,
-                           guards_ok=ok)
+                           guards_ok=_guards_intact(outs))
 
 
 CONV_BWD_SEG = 64        # csrc/kernels.hpp CONV_BWD_SEG: walk steps one lane of the conv backward owns (one row of dw | db partials each)
 NORM_BWD_ROWS = 16       # csrc/kernels.hpp NORM_BWD_ROWS: consecutive rows one wave of the norm backward walks (one dweight partial row each)
 
 
-def _sentinels_intact(outs) -> bool:
-    """outs: (tensor, whole buffer or None) pairs of `_guarded`: one row of sentinels before and after every guarded output untouched"""
-    ok = True
-    for t, whole in outs:
-        if whole is not None:
-            row = t.shape[-1]
-            ok = ok and bool((whole[:row] == -1234.0).all()) and bool((whole[row + t.numel():] == -1234.0).all())
-    return ok
-
-
-def _bwd_scratch(nb: int, dev, poison: bool):
-    return _nan_bytes(nb, dev) if poison else torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-
-
 def causal_conv1d_silu_bwd(x_tm, weight, bias, dout_tm, reverse=False, poison=False):
     """pcad_causal_conv1d_silu_bwd on causal_conv1d_dir's plain operands: x_tm [S, L, E] (a view whose rows are ldx >= E elements apart,
     such as the first half of a token-major xz, is read in place), weight (E, 4) or (E, 1, 4), bias (E), dout_tm [S, L, E].
     -> namespace(dx [S, L, E] in x's dtype; dw fp32 (E, 4); db fp32 (E); guards_ok).  poison (tests): as selective_scan_bwd."""
-    from types import SimpleNamespace
     _require_gpu(x_tm, "x")
     lib = load_bwd_library()
     S, L, E = x_tm.shape
@@ -447,15 +499,15 @@ def causal_conv1d_silu_bwd(x_tm, weight, bias, dout_tm, reverse=False, poison=Fa
     b = bias.float().contiguous()
     g = dout_tm.to(dt).contiguous()
     f32 = torch.float32
-    outs = [_guarded(sh, ty, dev, poison) for sh, ty in (((S, L, E), dt), ((E, 4), f32), ((E,), f32))]
+    outs = [_guarded(sh, ty, dev, "row", poison) for sh, ty in (((S, L, E), dt), ((E, 4), f32), ((E,), f32))]
     dx, dw, db = [o[0] for o in outs]
     nb = lib.pcad_causal_conv1d_silu_bwd_scratch_bytes(S, L, E)
-    scratch = _bwd_scratch(nb, dev, poison)
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
         _check(lib.pcad_causal_conv1d_silu_bwd(x_tm.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), g.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                               db.data_ptr(), _aligned(scratch), nb, S, L, E, int(bool(reverse)), _dt(x_tm), _stream_ptr()),
+                                               db.data_ptr(), scratch_ptr, nb, S, L, E, int(bool(reverse)), _dt(x_tm), _stream_ptr()),
                "pcad_causal_conv1d_silu_bwd")
-    return SimpleNamespace(dx=dx, dw=dw, db=db, guards_ok=_sentinels_intact(outs))
+    return SimpleNamespace(dx=dx, dw=dw, db=db, guards_ok=_guards_intact(outs))
 
 
 def add_rmsnorm_bwd(x, residual, weight, dy, dresidual_out, eps, residual_in_fp32, poison=False):
@@ -463,30 +515,28 @@ def add_rmsnorm_bwd(x, residual, weight, dy, dresidual_out, eps, residual_in_fp3
     of the prenorm output) or None.  The residual tensors are taken in the residual dtype (fp32 with residual_in_fp32 or an fp32 x,
     else x's).  -> namespace(dx like x; dresidual_in like x in the residual dtype, None without residual; dweight fp32 (D); guards_ok).
     poison (tests): as selective_scan_bwd."""
-    from types import SimpleNamespace
     _require_gpu(x, "x")
     lib = load_bwd_library()
     D = x.shape[-1]
     dt, dev = x.dtype, x.device
-    rdt = torch.float32 if (residual_in_fp32 or dt == torch.float32) else dt
+    rdt = _residual_dtype(dt, residual_in_fp32)
     xf = x.contiguous().view(-1, D)
     rows = xf.shape[0]
     res = residual.to(rdt).contiguous().view(-1, D) if residual is not None else None
     g = dy.to(dt).contiguous().view(-1, D)
     gres = dresidual_out.to(rdt).contiguous().view(-1, D) if dresidual_out is not None else None
     w = weight.float().contiguous()
-    outs = [_guarded(sh, ty, dev, poison) for sh, ty in (((rows, D), dt), ((rows, D), rdt), ((D,), torch.float32))]
+    outs = [_guarded(sh, ty, dev, "row", poison) for sh, ty in (((rows, D), dt), ((rows, D), rdt), ((D,), torch.float32))]
     dx, dres, dw = [o[0] for o in outs]
     if res is None:
         dres, outs[1] = None, (outs[1][0], None)
     nb = lib.pcad_add_rmsnorm_bwd_scratch_bytes(rows, D)
-    scratch = _bwd_scratch(nb, dev, poison)
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
-        _check(lib.pcad_add_rmsnorm_bwd(xf.data_ptr(), ptr(res), w.data_ptr(), g.data_ptr(), ptr(gres), dx.data_ptr(), ptr(dres), dw.data_ptr(),
-                                        _aligned(scratch), nb, rows, D, float(eps), _dt(xf), _DT[rdt], _stream_ptr()), "pcad_add_rmsnorm_bwd")
+        _check(lib.pcad_add_rmsnorm_bwd(xf.data_ptr(), _ptr(res), w.data_ptr(), g.data_ptr(), _ptr(gres), dx.data_ptr(), _ptr(dres), dw.data_ptr(),
+                                        scratch_ptr, nb, rows, D, float(eps), _dt(xf), _DT[rdt], _stream_ptr()), "pcad_add_rmsnorm_bwd")
     return SimpleNamespace(dx=dx.view(x.shape), dresidual_in=dres.view(x.shape) if dres is not None else None, dweight=dw,
-                           guards_ok=_sentinels_intact(outs))
+                           guards_ok=_guards_intact(outs))
 
 
 class _CausalConv1dDirFn(torch.autograd.Function):
@@ -586,10 +636,9 @@ def _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumu
     d_tm = delta.to(u.dtype).transpose(1, 2).contiguous()
     y = accumulate_into.transpose(1, 2).contiguous() if accumulate_into is not None else torch.empty_like(u_tm)
     with torch.cuda.device(u.device):
-        _check(lib.pcad_selective_scan(u_tm.data_ptr(), d_tm.data_ptr(), z_tm.data_ptr() if z_tm is not None else None,
-                                       E, bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), y.data_ptr(),
-                                       Bsz, L, E, int(bool(reverse)), _acc_mode(accumulate_into, gate_sum), _dt(u_tm),
-                                       _stream_ptr()), "pcad_selective_scan")
+        _check(lib.pcad_selective_scan(u_tm.data_ptr(), d_tm.data_ptr(), _ptr(z_tm), E, bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(),
+                                       db.data_ptr(), y.data_ptr(), Bsz, L, E, int(bool(reverse)), _acc_mode(accumulate_into, gate_sum),
+                                       _dt(u_tm), _stream_ptr()), "pcad_selective_scan")
     return y.transpose(1, 2)
 
 
@@ -598,23 +647,33 @@ def selective_scan_dtproj_fn(u, dt_low, dt_proj_weight, A, B, C, D=None, z=None,
     """mamba_inner_fn's tail: delta = dt_proj_weight @ dt_low (on MFMA inside the kernel), then selective_scan_fn.
     u, z: (B, E, L); dt_low: (B, L, R); dt_proj_weight: (E, R)."""
     _require_gpu(u, "u")
-    lib = load_library()
     Bsz, E, L = u.shape
-    R = dt_low.shape[-1]
-    Rp = 64 if R <= 64 else (R + 31) // 32 * 32          # kernels.hpp padded_dt_rank
     u_tm, z_tm, bc, A32, Dv, db = _scan_common(u, B, C, A, D, z, delta_bias)
-    dl = torch.zeros((Bsz, L, Rp), dtype=u.dtype, device=u.device)
-    dl[..., :R] = dt_low.to(u.dtype)
-    W = torch.zeros((E, Rp), dtype=u.dtype, device=u.device)
-    W[:, :R] = dt_proj_weight.to(u.dtype)
     y = accumulate_into.transpose(1, 2).contiguous() if accumulate_into is not None else torch.empty_like(u_tm)
-    with torch.cuda.device(u.device):
-        _check(lib.pcad_selective_scan_dtproj(u_tm.data_ptr(), dl.data_ptr(), Rp, W.data_ptr(), Rp,
-                                              z_tm.data_ptr() if z_tm is not None else None, E, bc.data_ptr(),
-                                              A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), y.data_ptr(), Bsz, L, E,
-                                              int(bool(reverse)), _acc_mode(accumulate_into, gate_sum), _dt(u_tm),
-                                              _stream_ptr()), "pcad_selective_scan_dtproj")
+    _scan_dtproj(u_tm, dt_low, dt_low.shape[-1], dt_proj_weight, z_tm, bc, A32, Dv, db, y, Bsz, L, reverse, _acc_mode(accumulate_into, gate_sum))
     return y.transpose(1, 2)
+
+
+def _pad_cols(t, R: int, cols: int, dtype, dev):
+    """t [..., R] -> [..., cols] in `dtype`, zeros behind column R"""
+    p = torch.zeros((*t.shape[:-1], cols), dtype=dtype, device=dev)
+    p[..., :R] = t.to(dtype)
+    return p
+
+
+def _scan_dtproj(u_tm, dt_low, R, dt_proj_weight, z_tm, bc, A32, Dv, db, y, Bsz, L, reverse, acc):
+    """pcad_selective_scan_dtproj into y: u_tm, y [B * L, E] rows (z_tm likewise, or None); dt_low [..., R] and dt_proj_weight (E, R) are
+    zero padded here to padded_dt_rank(R) columns in u's dtype - a dt_low that arrives that wide (the fused conv + x_proj's) is taken as
+    it is; bc, A32, Dv, db as `_scan_common` makes them; acc: `_acc_mode`."""
+    lib = load_library()
+    E, dt, dev = u_tm.shape[-1], u_tm.dtype, u_tm.device
+    Rp = padded_dt_rank(R)
+    dl = dt_low.to(dt).contiguous() if dt_low.shape[-1] == Rp else _pad_cols(dt_low, R, Rp, dt, dev)
+    W = _pad_cols(dt_proj_weight, R, Rp, dt, dev)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_selective_scan_dtproj(u_tm.data_ptr(), dl.data_ptr(), Rp, W.data_ptr(), Rp, _ptr(z_tm), E, bc.data_ptr(),
+                                              A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), y.data_ptr(), Bsz, L, E,
+                                              int(bool(reverse)), acc, _dt(u_tm), _stream_ptr()), "pcad_selective_scan_dtproj")
 
 
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
@@ -650,7 +709,7 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
         raise NotImplementedError("projection biases are not on the Caduceus path (Mamba(bias=False))")
     if not delta_softplus:
         raise NotImplementedError("the Caduceus path always uses delta_softplus=True")
-    lib = load_library()
+    load_library()
     Bsz, E2, L = xz.shape
     E = E2 // 2
     dt, dev = xz.dtype, xz.device
@@ -678,27 +737,16 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
     d = 1 if reverse else 0
     fused = R <= 96 and (E * xz.element_size()) % 128 == 0 and (rows + 16) * E * xz.element_size() < 2 ** 32
     if fused:
-        xc_b, dtl, bc, _, Rp = _conv_xproj_raw(x_tm, w, bias, w, bias, x_proj_weight, x_proj_weight)
+        xc_b, dtl, bc, _, _ = _conv_xproj_raw(x_tm, w, bias, w, bias, x_proj_weight, x_proj_weight)
         xc = from_blocked(xc_b[d], rows)
-        dl, bcd = dtl[d], bc[d]
+        dl, bcd = dtl[d], bc[d]                                      # dt_low already padded_dt_rank(R) wide
     else:
         yf, yr = causal_conv1d_bidir(x_tm, w, bias, w, bias)
         xc = (yr if reverse else yf).reshape(rows, E)
         x_dbl = linear(xc, x_proj_weight)                            # [rows, R + 32] in xz.dtype (rounded like upstream's F.linear)
-        Rp = 64 if R <= 64 else (R + 31) // 32 * 32
-        dl = torch.zeros((rows, Rp), dtype=dt, device=dev)
-        dl[:, :R] = x_dbl[:, :R]
-        bcd = x_dbl[:, R:].float().contiguous()
-    Wdt = torch.zeros((E, Rp), dtype=dt, device=dev)
-    Wdt[:, :R] = delta_proj_weight.to(dt)
-    A32 = A.float().contiguous()
-    Dv = (D.float() if D is not None else torch.zeros(E, device=dev)).contiguous()
-    db = (delta_bias.float() if delta_bias is not None else torch.zeros(E, device=dev)).contiguous()
+        dl, bcd = x_dbl[:, :R], x_dbl[:, R:].float().contiguous()
     y = torch.empty((rows, E), dtype=dt, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.pcad_selective_scan_dtproj(xc.data_ptr(), dl.data_ptr(), Rp, Wdt.data_ptr(), Rp, z_tm.data_ptr(), E,
-                                              bcd.data_ptr(), A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), y.data_ptr(),
-                                              Bsz, L, E, int(bool(reverse)), 0, _dt(xz), _stream_ptr()), "pcad_selective_scan_dtproj")
+    _scan_dtproj(xc, dl, R, delta_proj_weight, z_tm, bcd, *_scan_params(A, D, delta_bias, E, dev), y, Bsz, L, reverse, 0)
     return linear(y.view(Bsz, L, E), out_proj_weight)
 
 
@@ -732,10 +780,10 @@ def linear_split(x, weight):
     M = xf.shape[0]
     out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     nb = lib.pcad_gemm_nt_split_scratch_bytes(M, N, K)
-    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=x.device)
+    scratch, scratch_ptr = _scratch(nb, x.device)
     with torch.cuda.device(x.device):
-        _check(lib.pcad_gemm_nt_split(xf.data_ptr(), K, wf.data_ptr(), K, out.data_ptr(), N, M, N, K,
-                                      (scratch.data_ptr() + 255) // 256 * 256, nb, _stream_ptr()), "pcad_gemm_nt_split")
+        _check(lib.pcad_gemm_nt_split(xf.data_ptr(), K, wf.data_ptr(), K, out.data_ptr(), N, M, N, K, scratch_ptr, nb, _stream_ptr()),
+               "pcad_gemm_nt_split")
     return out.view(*x.shape[:-1], N)
 
 
@@ -782,24 +830,8 @@ def linear_residual(x, weight, residual):
 
 # ---- the engine's GEMM launch forms as operators (include/pcad.h "Engine forms of the GEMMs") ----------------------------------------
 # Layout conversion only (to_blocked / from_blocked, the residual's fragment layout): the operands are taken as the caller built them,
-# split [hi | lo] forms included.  Every output starts as NaN between two guards, as `_guarded` does for the scan's backward.
-GUARD = -1024.0                 # exact in bf16 and fp32
-
-
-def _guarded_rows(rows: int, width: int, dtype, dev):
-    """an output of `rows` rows of `width` elements (plain or blocked - the kernel's business): NaN where the kernel must write, a guard
-    of sentinels before and after (whole 128-byte lines, so the output keeps its alignment).  -> (flat [rows * width], whole buffer, guard)"""
-    g = (width + 63) // 64 * 64
-    n = rows * width
-    whole = torch.full((n + 2 * g,), GUARD, dtype=dtype, device=dev)
-    whole[g:g + n] = float("nan")
-    return whole[g:g + n], whole, g
-
-
-def _guards_intact(outs) -> bool:
-    return all(bool((w[:g] == GUARD).all()) and bool((w[w.numel() - g:] == GUARD).all()) for _, w, g in outs)
-
-
+# split [hi | lo] forms included.  Every output - `rows` rows of `width` elements, plain or blocked: the kernel's business - starts as
+# NaN between two guards of whole lines (`_guarded`, geometry "lines").
 def _gemm_a(a: torch.Tensor, a_blocked: bool, lda_extra: int):
     """A as a launch takes it: blocked (padding rows NaN), or plain rows with lda_extra NaN columns behind each.  -> (tensor, lda)"""
     a = a.contiguous()
@@ -814,19 +846,17 @@ def _gemm_a(a: torch.Tensor, a_blocked: bool, lda_extra: int):
     return a, a.shape[1]
 
 
-def _unblock(flat: torch.Tensor, rows: int, width: int):
-    """a blocked output buffer -> (its `rows` rows as plain rows, its padding rows)"""
-    per = 128 // flat.element_size()
-    rows8 = (rows + 7) // 8 * 8
-    full = from_blocked(flat.view(rows8 // 8, width // per, 8, per), rows8)
-    return full[:rows].contiguous(), full[rows:].contiguous()
+def _unblock(out: torch.Tensor, rows: int):
+    """a blocked output buffer [rows8, width] -> (its `rows` rows as plain rows, its padding rows)"""
+    rows8, width = out.shape
+    per = 128 // out.element_size()
+    return _split_blocked(out.view(rows8 // 8, width // per, 8, per), rows)
 
 
 def gemm_nt_engine(a, w, K: Optional[int] = None, a_blocked: bool = False, ksplit: int = 0, out_dtype: Optional[torch.dtype] = None,
                    lda_extra: int = 0):
     """pcad_gemm_nt_engine (the engine's out_proj launch): a [M, K] - or, ksplit = Ko / 64, bf16 [M, 2 Ko] = [hi | lo] with K = 3 Ko -,
     w [N, K] (or [N, 2 Ko]); a_blocked: A goes through the blocked layout.  -> namespace(c [M, N] out_dtype, guards_ok)."""
-    from types import SimpleNamespace
     _require_gpu(a, "a")
     lib = load_library()
     M, N = a.shape[0], w.shape[0]
@@ -834,28 +864,27 @@ def gemm_nt_engine(a, w, K: Optional[int] = None, a_blocked: bool = False, kspli
     od = out_dtype or a.dtype
     ab, lda = _gemm_a(a, a_blocked, lda_extra)
     wf = w.contiguous()
-    c = _guarded_rows(M, N, od, a.device)
+    c = _guarded((M, N), od, a.device, "lines")
     with torch.cuda.device(a.device):
         _check(lib.pcad_gemm_nt_engine(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c[0].data_ptr(), N, M, N, K, int(bool(a_blocked)),
                                        int(ksplit), _dt(a), _DT[od], _stream_ptr()), "pcad_gemm_nt_engine")
-    return SimpleNamespace(c=c[0].view(M, N), guards_ok=_guards_intact([c]))
+    return SimpleNamespace(c=c[0], guards_ok=_guards_intact([c]))
 
 
 def gemm_nt_xproj(a, w, nsplit: int, a_blocked: bool = False, ksplit: int = 0):
     """pcad_gemm_nt_xproj (the engine's x_proj launch where the fused conv + x_proj kernel is off): a [M, K], w [N, K] ->
     namespace(c [M, nsplit] in a's dtype, c2 fp32 [M, N - nsplit] holding values rounded to a's dtype, guards_ok)."""
-    from types import SimpleNamespace
     _require_gpu(a, "a")
     lib = load_library()
     M, N, K = a.shape[0], w.shape[0], a.shape[1]
     ab, lda = _gemm_a(a, a_blocked, 0)
     wf = w.contiguous()
-    c = _guarded_rows(M, nsplit, a.dtype, a.device)
-    c2 = _guarded_rows(M, N - nsplit, torch.float32, a.device)
+    c = _guarded((M, nsplit), a.dtype, a.device, "lines")
+    c2 = _guarded((M, N - nsplit), torch.float32, a.device, "lines")
     with torch.cuda.device(a.device):
         _check(lib.pcad_gemm_nt_xproj(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c[0].data_ptr(), nsplit, c2[0].data_ptr(), N - nsplit,
                                       nsplit, M, N, K, int(bool(a_blocked)), int(ksplit), _dt(a), _stream_ptr()), "pcad_gemm_nt_xproj")
-    return SimpleNamespace(c=c[0].view(M, nsplit), c2=c2[0].view(M, N - nsplit), guards_ok=_guards_intact([c, c2]))
+    return SimpleNamespace(c=c[0], c2=c2[0], guards_ok=_guards_intact([c, c2]))
 
 
 def gemm_nt_two(a, w, nsplit: int, K: Optional[int] = None, out_blocked: bool = False, rscale=None, ksplit: int = 0,
@@ -864,7 +893,6 @@ def gemm_nt_two(a, w, nsplit: int, K: Optional[int] = None, out_blocked: bool = 
     out_blocked: both outputs go through the blocked layout.  a_blocked is refused by the library (the form has none).
     -> namespace(c1 [M, nsplit], c2 [M, N - nsplit] out_dtype; pad1, pad2: the blocked buffers' padding rows (empty for plain
     outputs); guards_ok)."""
-    from types import SimpleNamespace
     _require_gpu(a, "a")
     lib = load_library()
     M, N = a.shape[0], w.shape[0]
@@ -873,24 +901,22 @@ def gemm_nt_two(a, w, nsplit: int, K: Optional[int] = None, out_blocked: bool = 
     ab, lda = _gemm_a(a, a_blocked, lda_extra)
     wf = w.contiguous()
     rs = rscale.float().contiguous() if rscale is not None else None
-    rows = (M + 7) // 8 * 8 if out_blocked else M
-    c1, c2 = _guarded_rows(rows, nsplit, od, a.device), _guarded_rows(rows, N - nsplit, od, a.device)
+    rows = _round_up(M, 8) if out_blocked else M
+    c1, c2 = _guarded((rows, nsplit), od, a.device, "lines"), _guarded((rows, N - nsplit), od, a.device, "lines")
     with torch.cuda.device(a.device):
         _check(lib.pcad_gemm_nt_two(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c1[0].data_ptr(), c2[0].data_ptr(), nsplit,
-                                    rs.data_ptr() if rs is not None else None, M, N, K, int(bool(a_blocked)), int(bool(out_blocked)),
+                                    _ptr(rs), M, N, K, int(bool(a_blocked)), int(bool(out_blocked)),
                                     int(ksplit), _dt(a), _DT[od], _stream_ptr()), "pcad_gemm_nt_two")
     if out_blocked:
-        (o1, p1), (o2, p2) = _unblock(c1[0], M, nsplit), _unblock(c2[0], M, N - nsplit)
+        (o1, p1), (o2, p2) = _unblock(c1[0], M), _unblock(c2[0], M)
     else:
-        o1, o2 = c1[0].view(M, nsplit), c2[0].view(M, N - nsplit)
-        p1, p2 = o1[M:], o2[M:]
+        (o1, p1), (o2, p2) = (c1[0], c1[0][M:]), (c2[0], c2[0][M:])
     return SimpleNamespace(c1=o1, c2=o2, pad1=p1, pad2=p2, guards_ok=_guards_intact([c1, c2]))
 
 
 def gemm_nt_residual_engine(a, w, residual, a_blocked: bool = False, ksplit: int = 0):
     """pcad_gemm_nt_residual_engine: `linear_residual` with A through the blocked layout (the engine's "norm_fold" out_proj launch).
     -> namespace(res fp32 [M, N], c [M, N] in a's dtype, ssq fp32 [M, N / 128], guards_ok)."""
-    from types import SimpleNamespace
     _require_gpu(a, "a")
     lib = load_library()
     M, K = a.shape
@@ -899,20 +925,18 @@ def gemm_nt_residual_engine(a, w, residual, a_blocked: bool = False, ksplit: int
         raise ValueError("residual must be an fp32 [M, N] tensor")
     ab, lda = _gemm_a(a, a_blocked, 0)
     wf = w.contiguous()
-    res = _guarded_rows(M, N, torch.float32, a.device)
-    res[0].copy_(to_res_fragment(residual))
-    c, ssq = _guarded_rows(M, N, a.dtype, a.device), _guarded_rows(M, N // 128, torch.float32, a.device)
+    res = _guarded((M, N), torch.float32, a.device, "lines")
+    res[0].view(-1).copy_(to_res_fragment(residual))
+    c, ssq = _guarded((M, N), a.dtype, a.device, "lines"), _guarded((M, N // 128), torch.float32, a.device, "lines")
     with torch.cuda.device(a.device):
         _check(lib.pcad_gemm_nt_residual_engine(ab.data_ptr(), lda, wf.data_ptr(), wf.shape[1], c[0].data_ptr(), res[0].data_ptr(),
                                                 ssq[0].data_ptr(), M, N, K, int(bool(a_blocked)), int(ksplit), _dt(a), _stream_ptr()),
                "pcad_gemm_nt_residual_engine")
-    return SimpleNamespace(res=from_res_fragment(res[0], M, N), c=c[0].view(M, N), ssq=ssq[0].view(M, N // 128),
-                           guards_ok=_guards_intact([res, c, ssq]))
+    return SimpleNamespace(res=from_res_fragment(res[0].view(-1), M, N), c=c[0], ssq=ssq[0], guards_ok=_guards_intact([res, c, ssq]))
 
 
 def gather_rows(src, B: int, L: int, positions):
     """src [2B*L, E] -> [2B*P, E]: strand b row p_q, strand B+b row L-1-p_q (include/pcad.h pcad_gather_rows)."""
-    import ctypes as C
     _require_gpu(src, "src")
     lib = load_library()
     E = src.shape[-1]
@@ -931,7 +955,6 @@ def final_head(h, res, norm_weight, emb, complement, B: int, L: int, eps: float,
     """norm_f + RC re-assembly + tied RCPS LM head at the requested positions (include/pcad.h pcad_final_head).
     h [2B*L, D] (or the gathered rows when h_compact), res [2B*L, D] (fp32 or h.dtype), emb [V, D] (rounded to h.dtype here, as the
     tied lm_head weight is).  -> (hidden [B, Q, 2D] | None, logits fp32 [B, Q, V] | None)."""
-    import ctypes as C
     _require_gpu(h, "h")
     lib = load_library()
     D = h.shape[-1]
@@ -948,9 +971,9 @@ def final_head(h, res, norm_weight, emb, complement, B: int, L: int, eps: float,
     pps = pos_per_seq.to(torch.int32).contiguous() if pos_per_seq is not None else None
     with torch.cuda.device(h.device):
         _check(lib.pcad_final_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(),
-                                   hid.data_ptr() if hid is not None else None, lg.data_ptr() if lg is not None else None,
-                                   B, L, D, float(eps), arr, P, pps.data_ptr() if pps is not None else None, int(bool(h_compact)),
-                                   ids.data_ptr() if ids is not None else None, status.data_ptr() if status is not None else None,
+                                   _ptr(hid), _ptr(lg),
+                                   B, L, D, float(eps), arr, P, _ptr(pps), int(bool(h_compact)),
+                                   _ptr(ids), _ptr(status),
                                    _dt(hf), _DT[rf.dtype], int(bool(res_fragment)), _stream_ptr()), "pcad_final_head")
     return hid, lg
 
@@ -962,7 +985,6 @@ def probs_head(h, res, norm_weight, emb, complement, cols, B: int, L: int, eps: 
     (include/pcad.h pcad_probs_head).  h / res / emb / ids / status as in `final_head`; positions: None (all L) or a shared list;
     positions_per_window: integer tensor [B, P] on h's device (exclusive with positions).
     -> (probs fp32 [B, Q, 4] | None, logits fp32 [B, Q, V] | None)."""
-    import ctypes as C
     _require_gpu(h, "h")
     lib = load_library()
     D = h.shape[-1]
@@ -979,10 +1001,10 @@ def probs_head(h, res, norm_weight, emb, complement, cols, B: int, L: int, eps: 
     arr = (C.c_int32 * P)(*[int(p) for p in positions]) if positions is not None and len(positions) else None
     with torch.cuda.device(h.device):
         _check(lib.pcad_probs_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(),
-                                   (C.c_int32 * 4)(*[int(c) for c in cols]), pr.data_ptr() if pr is not None else None,
-                                   lg.data_ptr() if lg is not None else None, B, L, D, float(eps), arr, P,
-                                   ppw.data_ptr() if ppw is not None else None, int(bool(h_compact)),
-                                   ids.data_ptr() if ids is not None else None, status.data_ptr() if status is not None else None,
+                                   (C.c_int32 * 4)(*[int(c) for c in cols]), _ptr(pr),
+                                   _ptr(lg), B, L, D, float(eps), arr, P,
+                                   _ptr(ppw), int(bool(h_compact)),
+                                   _ptr(ids), _ptr(status),
                                    _dt(hf), _DT[rf.dtype], int(bool(res_fragment)), _stream_ptr()), "pcad_probs_head")
     return pr, lg
 
@@ -993,7 +1015,6 @@ def layer_rows(src, B: int, L: int, positions=None, positions_per_window=None, a
     output / the RCPS embedding), or - assembled - [B, P, 2D] rows already in hidden_states' layout; positions: a shared list, or
     positions_per_window: integer tensor [B, P] on src's device (exactly one).  -> [B, P, 2D] in src's dtype, or - average - the
     strand-averaged fp32 [B, P, D]."""
-    import ctypes as C
     _require_gpu(src, "src")
     lib = load_library()
     D = src.shape[-1] // 2 if assembled else src.shape[-1]
@@ -1003,8 +1024,8 @@ def layer_rows(src, B: int, L: int, positions=None, positions_per_window=None, a
     out = torch.empty((B, P, D if average else 2 * D), dtype=torch.float32 if average else src.dtype, device=src.device)
     arr = (C.c_int32 * max(P, 1))(*[int(p) for p in positions]) if positions is not None else None
     with torch.cuda.device(src.device):
-        _check(lib.pcad_layer_rows(srcf.data_ptr(), out.data_ptr(), B, L, D, arr, P, ppw.data_ptr() if ppw is not None else None,
-                                   int(bool(assembled)), int(bool(average)), status.data_ptr() if status is not None else None,
+        _check(lib.pcad_layer_rows(srcf.data_ptr(), out.data_ptr(), B, L, D, arr, P, _ptr(ppw),
+                                   int(bool(assembled)), int(bool(average)), _ptr(status),
                                    _dt(srcf), _stream_ptr()), "pcad_layer_rows")
     return out
 
@@ -1013,14 +1034,49 @@ def layer_rows(src, B: int, L: int, positions=None, positions_per_window=None, a
 LOSS_SEG = 64            # csrc/kernels.hpp LOSS_SEG: positions per block of the loss head and of its backward (one row of partials each)
 
 
-def _loss_head_operands(h, res, norm_weight, emb, complement, labels, loss_weights, B, L):
+def _head_rows(h, res, B, L) -> int:
+    """the checks both heads make on their 2B-strand rows h, res [2 B L, D] -> D"""
     D = h.shape[-1]
-    if emb.shape[0] != 8:
-        raise ValueError(f"emb must hold the 8 rows of the padded vocabulary, got {tuple(emb.shape)}")
     if h.numel() != 2 * B * L * D or res.numel() != 2 * B * L * D:
         raise ValueError(f"h and res must be [2 B L, D] = [{2 * B * L}, {D}], got {tuple(h.shape)} and {tuple(res.shape)}")
     if res.dtype != torch.float32 and res.dtype != h.dtype:
         raise ValueError(f"res must be fp32 or h's dtype, got {res.dtype} for {h.dtype}")
+    return D
+
+
+def _head_batch(h, B, L):
+    """B, L of a head's `*_fn` form: as given, else read from h [2B, L, D]"""
+    if B is None or L is None:
+        if h.dim() != 3:
+            raise ValueError("h must be [2B, L, D], or [2B*L, D] with B= and L=")
+        B, L = h.shape[0] // 2, h.shape[1]
+    return B, L
+
+
+class _WantedGrads:
+    """The `want` of the two head backward wrappers.  spec: name -> (shape the kernel writes, dtype, shape handed back) of every gradient
+    the kernel can form; the wanted ones get a `_guarded` output, the others are passed as NULL and come back as None."""
+
+    def __init__(self, want, spec, dev, poison):
+        if set(want) - set(spec) or not want:
+            raise ValueError(f"want must name some of {', '.join(spec)}, got {tuple(want)}")
+        self.spec = spec
+        self.outs = {k: _guarded(sh, ty, dev, "row", poison) for k, (sh, ty, _) in spec.items() if k in want}
+
+    def ptr(self, k):
+        return self.outs[k][0].data_ptr() if k in self.outs else None
+
+    def result(self, wrapper):
+        """-> namespace(one field per name of the spec, guards_ok); wrapper.last_outputs: the names that were computed"""
+        wrapper.last_outputs = tuple(k for k in self.spec if k in self.outs)
+        fields = {k: self.outs[k][0].view(back) if k in self.outs else None for k, (_, _, back) in self.spec.items()}
+        return SimpleNamespace(**fields, guards_ok=_guards_intact(self.outs.values()))
+
+
+def _loss_head_operands(h, res, norm_weight, emb, complement, labels, loss_weights, B, L):
+    if emb.shape[0] != 8:
+        raise ValueError(f"emb must hold the 8 rows of the padded vocabulary, got {tuple(emb.shape)}")
+    _head_rows(h, res, B, L)
     dev = h.device
     comp = torch.as_tensor(list(complement), dtype=torch.int32, device=dev) if not torch.is_tensor(complement) else complement.to(dev, torch.int32)
     return (h.contiguous(), res.contiguous(), norm_weight.float().contiguous(), emb.to(h.dtype).float().contiguous(), comp.contiguous(),
@@ -1041,12 +1097,11 @@ def loss_head(h, res, norm_weight, emb, complement, labels, loss_weights=None, i
     nll = torch.empty((B, L), dtype=torch.float32, device=dev) if want_nll else None
     lg = torch.empty((B, L, 8), dtype=torch.float32, device=dev) if want_logits else None
     nb = lib.pcad_loss_head_scratch_bytes(B, L)
-    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    scratch, scratch_ptr = _scratch(nb, dev)
     with torch.cuda.device(dev):
-        _check(lib.pcad_loss_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(), lab.data_ptr(), ptr(wt),
-                                  int(ignore_index), sums.data_ptr(), ptr(nll), ptr(lg), B, L, D, float(eps), None, None, _dt(hf),
-                                  _DT[rf.dtype], 0, _aligned(scratch), nb, _stream_ptr()), "pcad_loss_head")
+        _check(lib.pcad_loss_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(), lab.data_ptr(), _ptr(wt),
+                                  int(ignore_index), sums.data_ptr(), _ptr(nll), _ptr(lg), B, L, D, float(eps), None, None, _dt(hf),
+                                  _DT[rf.dtype], 0, scratch_ptr, nb, _stream_ptr()), "pcad_loss_head")
     return sums, nll, lg
 
 
@@ -1056,33 +1111,23 @@ def loss_head_bwd(h, res, norm_weight, emb, complement, labels, loss_weights=Non
     gradient of nll).  want: the gradients to compute; the others are passed as NULL and come back as None.
     -> namespace(dh like h; dres like res; dnorm_weight fp32 (D); demb fp32 (8, D) - the gradient of the dtype-rounded fp32 table;
     guards_ok).  Rows of dh / dres at unlabelled positions are zeros.  poison (tests): as selective_scan_bwd."""
-    from types import SimpleNamespace
     _require_gpu(h, "h")
     lib = load_bwd_library()
-    D, dev = h.shape[-1], h.device
+    D, dev, rows = h.shape[-1], h.device, 2 * B * L
     hf, rf, w, e32, comp, lab, wt = _loss_head_operands(h, res, norm_weight, emb, complement, labels, loss_weights, B, L)
-    unknown = set(want) - {"dh", "dres", "dnorm_weight", "demb"}
-    if unknown or not want:
-        raise ValueError(f"want must name some of dh, dres, dnorm_weight, demb, got {tuple(want)}")
+    g = _WantedGrads(want, {"dh": ((rows, D), hf.dtype, h.shape), "dres": ((rows, D), rf.dtype, res.shape),
+                            "dnorm_weight": ((D,), torch.float32, (D,)), "demb": ((8, D), torch.float32, (8, D))}, dev, poison)
     gs = dsum.to(dev, torch.float32).contiguous()
     gn = dnll.to(dev, torch.float32).contiguous() if dnll is not None else None
     if gs.numel() != B or (gn is not None and gn.numel() != B * L):
         raise ValueError("dsum must be [B] and dnll [B, L]")
-    rows = 2 * B * L
-    spec = {"dh": ((rows, D), hf.dtype), "dres": ((rows, D), rf.dtype), "dnorm_weight": ((D,), torch.float32), "demb": ((8, D), torch.float32)}
-    outs = {k: _guarded(sh, ty, dev, poison) for k, (sh, ty) in spec.items() if k in want}
     nb = lib.pcad_loss_head_bwd_scratch_bytes(B, L, D)
-    scratch = _bwd_scratch(nb, dev, poison)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    out = lambda k: outs[k][0].data_ptr() if k in outs else None
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
-        _check(lib.pcad_loss_head_bwd(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(), lab.data_ptr(), ptr(wt),
-                                      int(ignore_index), gs.data_ptr(), ptr(gn), out("dh"), out("dres"), out("dnorm_weight"), out("demb"),
-                                      _aligned(scratch), nb, B, L, D, float(eps), _dt(hf), _DT[rf.dtype], _stream_ptr()), "pcad_loss_head_bwd")
-    loss_head_bwd.last_outputs = tuple(k for k in spec if k in outs)
-    get = lambda k, shape: outs[k][0].view(shape) if k in outs else None
-    return SimpleNamespace(dh=get("dh", h.shape), dres=get("dres", res.shape), dnorm_weight=get("dnorm_weight", (D,)), demb=get("demb", (8, D)),
-                           guards_ok=_sentinels_intact(list(outs.values())))
+        _check(lib.pcad_loss_head_bwd(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), e32.data_ptr(), comp.data_ptr(), lab.data_ptr(), _ptr(wt),
+                                      int(ignore_index), gs.data_ptr(), _ptr(gn), g.ptr("dh"), g.ptr("dres"), g.ptr("dnorm_weight"), g.ptr("demb"),
+                                      scratch_ptr, nb, B, L, D, float(eps), _dt(hf), _DT[rf.dtype], _stream_ptr()), "pcad_loss_head_bwd")
+    return g.result(loss_head_bwd)
 
 
 loss_head_bwd.last_outputs = ()      # the output set of the latest call (tests: a gradient nobody needs is not computed)
@@ -1127,10 +1172,7 @@ def mlm_loss_head_fn(h, res, norm_weight, emb, complement, labels, loss_weights=
     gradient comes back in its input's shape and dtype, gradients nobody needs are not computed, and only sums[:, 0] and nll carry a
     graph.  Otherwise it is the plain forward call."""
     _require_gpu(h, "h")
-    if B is None or L is None:
-        if h.dim() != 3:
-            raise ValueError("h must be [2B, L, D], or [2B*L, D] with B= and L=")
-        B, L = h.shape[0] // 2, h.shape[1]
+    B, L = _head_batch(h, B, L)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (h, res, norm_weight, emb)):
         comp = torch.as_tensor(list(complement), dtype=torch.int32, device=h.device) if not torch.is_tensor(complement) else complement
         # the casts stay torch ops outside the Function, so that autograd returns each gradient in its input's dtype
@@ -1148,14 +1190,9 @@ TRAINABLE_POOLING = ("mean", "first", "last")       # max pooling has a forward 
 
 
 def _pooled_head_operands(h, res, norm_weight, score_w, pooling, B, L):
-    from .engine import MAX_LABELS, POOLING
-    D = h.shape[-1]
     if pooling not in POOLING:
         raise ValueError(f"pooling must be one of {sorted(POOLING)}, got {pooling!r}")
-    if h.numel() != 2 * B * L * D or res.numel() != 2 * B * L * D:
-        raise ValueError(f"h and res must be [2 B L, D] = [{2 * B * L}, {D}], got {tuple(h.shape)} and {tuple(res.shape)}")
-    if res.dtype != torch.float32 and res.dtype != h.dtype:
-        raise ValueError(f"res must be fp32 or h's dtype, got {res.dtype} for {h.dtype}")
+    D = _head_rows(h, res, B, L)
     if score_w.dim() != 2 or score_w.shape[1] != D or not 1 <= score_w.shape[0] <= MAX_LABELS:
         raise ValueError(f"score_w must be [1..{MAX_LABELS}, {D}], got {tuple(score_w.shape)}")
     # score_w is rounded to the model dtype here, as the score Linear's weight is stored in it
@@ -1173,11 +1210,10 @@ def pooled_head(h, res, norm_weight, score_w, pooling="mean", eps=1e-5, *, B: in
     lg = torch.empty((B, NL), dtype=torch.float32, device=dev)
     pooled = torch.empty((B, 2, D), dtype=torch.float32, device=dev) if want_pooled else None
     nb = lib.pcad_pooled_head_scratch_bytes(B, L, D, pid)
-    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+    scratch, scratch_ptr = _scratch(nb, dev)
     with torch.cuda.device(dev):
-        _check(lib.pcad_pooled_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), W.data_ptr(), NL, pooled.data_ptr() if want_pooled else None,
-                                    lg.data_ptr(), B, L, D, float(eps), pid, None, None, _dt(hf), _DT[rf.dtype], 0, _aligned(scratch), nb,
-                                    _stream_ptr()), "pcad_pooled_head")
+        _check(lib.pcad_pooled_head(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), W.data_ptr(), NL, _ptr(pooled), lg.data_ptr(), B, L, D,
+                                    float(eps), pid, None, None, _dt(hf), _DT[rf.dtype], 0, scratch_ptr, nb, _stream_ptr()), "pcad_pooled_head")
     return (lg, pooled) if want_pooled else lg
 
 
@@ -1187,33 +1223,24 @@ def pooled_head_bwd(h, res, norm_weight, score_w, pooled, dlogits, pooling="mean
     gradients to compute; the others are passed as NULL and come back as None.
     -> namespace(dh like h; dres like res; dnorm_weight fp32 (D); dscore_w fp32 (NL, D) - the gradient of the dtype-rounded fp32 weight;
     guards_ok).  first / last: the rows the pooling did not read are zeros.  poison (tests): as selective_scan_bwd."""
-    from types import SimpleNamespace
     _require_gpu(h, "h")
     lib = load_bwd_library()
-    D, dev = h.shape[-1], h.device
+    D, dev, rows = h.shape[-1], h.device, 2 * B * L
     hf, rf, w, W, pid = _pooled_head_operands(h, res, norm_weight, score_w, pooling, B, L)
     NL = W.shape[0]
-    unknown = set(want) - {"dh", "dres", "dnorm_weight", "dscore_w"}
-    if unknown or not want:
-        raise ValueError(f"want must name some of dh, dres, dnorm_weight, dscore_w, got {tuple(want)}")
+    g = _WantedGrads(want, {"dh": ((rows, D), hf.dtype, h.shape), "dres": ((rows, D), rf.dtype, res.shape),
+                            "dnorm_weight": ((D,), torch.float32, (D,)), "dscore_w": ((NL, D), torch.float32, (NL, D))}, dev, poison)
     pl = pooled.to(dev, torch.float32).contiguous()
     gl = dlogits.to(dev, torch.float32).contiguous()
     if pl.numel() != B * 2 * D or gl.numel() != B * NL:
         raise ValueError(f"pooled must be [B, 2, D] and dlogits [B, NL] = [{B}, {NL}], got {tuple(pooled.shape)} and {tuple(dlogits.shape)}")
-    rows = 2 * B * L
-    spec = {"dh": ((rows, D), hf.dtype), "dres": ((rows, D), rf.dtype), "dnorm_weight": ((D,), torch.float32), "dscore_w": ((NL, D), torch.float32)}
-    outs = {k: _guarded(sh, ty, dev, poison) for k, (sh, ty) in spec.items() if k in want}
     nb = lib.pcad_pooled_head_bwd_scratch_bytes(B, L, D, pid)
-    scratch = _bwd_scratch(nb, dev, poison)
-    out = lambda k: outs[k][0].data_ptr() if k in outs else None
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
-        _check(lib.pcad_pooled_head_bwd(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), W.data_ptr(), pl.data_ptr(), gl.data_ptr(), out("dh"), out("dres"),
-                                        out("dnorm_weight"), out("dscore_w"), _aligned(scratch), nb, B, L, D, NL, float(eps), pid, _dt(hf),
-                                        _DT[rf.dtype], _stream_ptr()), "pcad_pooled_head_bwd")
-    pooled_head_bwd.last_outputs = tuple(k for k in spec if k in outs)
-    get = lambda k, shape: outs[k][0].view(shape) if k in outs else None
-    return SimpleNamespace(dh=get("dh", h.shape), dres=get("dres", res.shape), dnorm_weight=get("dnorm_weight", (D,)),
-                           dscore_w=get("dscore_w", (NL, D)), guards_ok=_sentinels_intact(list(outs.values())))
+        _check(lib.pcad_pooled_head_bwd(hf.data_ptr(), rf.data_ptr(), w.data_ptr(), W.data_ptr(), pl.data_ptr(), gl.data_ptr(), g.ptr("dh"),
+                                        g.ptr("dres"), g.ptr("dnorm_weight"), g.ptr("dscore_w"), scratch_ptr, nb, B, L, D, NL, float(eps), pid,
+                                        _dt(hf), _DT[rf.dtype], _stream_ptr()), "pcad_pooled_head_bwd")
+    return g.result(pooled_head_bwd)
 
 
 pooled_head_bwd.last_outputs = ()    # the output set of the latest call (tests: a gradient nobody needs is not computed)
@@ -1253,10 +1280,7 @@ def pooled_head_fn(h, res, norm_weight, score_w, pooling="mean", eps=1e-5, B: Op
     of score_w to the model dtype), gradients nobody
     needs are not computed, and max pooling is refused.  Otherwise it is the plain forward call."""
     _require_gpu(h, "h")
-    if B is None or L is None:
-        if h.dim() != 3:
-            raise ValueError("h must be [2B, L, D], or [2B*L, D] with B= and L=")
-        B, L = h.shape[0] // 2, h.shape[1]
+    B, L = _head_batch(h, B, L)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (h, res, norm_weight, score_w)):
         if pooling not in TRAINABLE_POOLING:
             raise NotImplementedError(f"pooling {pooling!r} has no backward (include/pcad_bwd.h): trainable poolings are {TRAINABLE_POOLING}")
@@ -1317,7 +1341,6 @@ OPTIM_DECAY = 1          # include/pcad_bwd.h PCAD_OPTIM_DECAY: flags bit 0
 
 
 def _optim_record_type():
-    import ctypes as C
 
     class Record(C.Structure):            # include/pcad_bwd.h pcad_optim_tensor
         _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("master", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
@@ -1326,15 +1349,19 @@ def _optim_record_type():
     return Record
 
 
+def _record_table(records):
+    """host records (param, grad, master, exp_avg, exp_avg_sq, n, param_dtype, grad_dtype, flags) -> a ctypes array of pcad_optim_tensor"""
+    tab = (_optim_record_type() * max(1, len(records)))()
+    for r, rec in zip(tab, records):
+        r.param, r.grad, r.master, r.exp_avg, r.exp_avg_sq, r.n, r.param_dtype, r.grad_dtype, r.flags = rec
+    return tab
+
+
 def optim_plan(records):
     """pcad_optim_plan on host records (param, grad, master, exp_avg, exp_avg_sq, n, param_dtype, grad_dtype, flags): pointers as
     integers or None, nothing is dereferenced.  -> (the table as bytes, the chunk map as a list of (record, chunk) pairs)"""
-    import ctypes as C
     lib = load_bwd_library()
-    Record = _optim_record_type()
-    tab = (Record * max(1, len(records)))()
-    for r, rec in zip(tab, records):
-        r.param, r.grad, r.master, r.exp_avg, r.exp_avg_sq, r.n, r.param_dtype, r.grad_dtype, r.flags = rec
+    tab = _record_table(records)
     chunks = C.c_int64(0)
     _check(lib.pcad_optim_plan(C.addressof(tab), len(records), None, 0, C.byref(chunks)), "pcad_optim_plan")
     cmap = (C.c_int32 * max(2, 2 * chunks.value))()
@@ -1345,16 +1372,18 @@ def optim_plan(records):
 def grads_flat_plan(records):
     """pcad_grads_flat_plan on host records (as optim_plan takes them; needs no device): where each tensor's gradient lies in one fp32
     buffer, every slice padded to a multiple of 4 elements (16 bytes).  -> (offsets in elements, one per record; total elements)"""
-    import ctypes as C
     lib = load_bwd_library()
-    Record = _optim_record_type()
-    tab = (Record * max(1, len(records)))()
-    for r, rec in zip(tab, records):
-        r.param, r.grad, r.master, r.exp_avg, r.exp_avg_sq, r.n, r.param_dtype, r.grad_dtype, r.flags = rec
+    tab = _record_table(records)
     offsets = (C.c_int64 * max(1, len(records)))()
     total = C.c_int64(0)
     _check(lib.pcad_grads_flat_plan(C.addressof(tab), len(records), C.addressof(offsets), C.byref(total)), "pcad_grads_flat_plan")
     return [int(offsets[i]) for i in range(len(records))], int(total.value)
+
+
+def _check_flat(flat, total: int, dev):
+    """the one gradient buffer of a data-parallel step: a contiguous fp32 vector of at least the flat plan's total elements on `dev`"""
+    if flat.dtype != torch.float32 or flat.dim() != 1 or not flat.is_contiguous() or flat.numel() < total or flat.device != dev:
+        raise ValueError(f"flat must be a contiguous fp32 vector of at least {total} elements on {dev}")
 
 
 class OptimTable:
@@ -1383,8 +1412,8 @@ class OptimTable:
                 _require_gpu(t, f"{name}[{i}]")
                 if t.device != dev or not t.is_contiguous() or t.numel() != p.numel() or (want is not None and t.dtype != want):
                     raise ValueError(f"{name}[{i}] must be a contiguous {want or 'bf16 / fp32'} tensor of param[{i}]'s size on {dev}")
-            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-            records.append((ptr(p), ptr(g), ptr(ms), ptr(m), ptr(v), p.numel(), _dt(p), _dt(g), OPTIM_DECAY if d else 0))
+            ptrs = [_ptr(t) if p.numel() else None for t in (p, g, ms, m, v)]            # an empty tensor has no address to hand over
+            records.append((*ptrs, p.numel(), _dt(p), _dt(g), OPTIM_DECAY if d else 0))
         self.pointers = tuple(r[:5] for r in records)
         self.records = records
         self._flat_plan, self._flat_offsets = None, None
@@ -1398,7 +1427,7 @@ class OptimTable:
             self.chunk_map = hmap.to(dev, non_blocking=True)
             self.state = state if state is not None else torch.zeros(4, dtype=torch.int32, device=dev)
             self.scratch_bytes = load_bwd_library().pcad_adamw_step_scratch_bytes(self.chunks)
-            self.scratch = torch.empty(self.scratch_bytes + 256, dtype=torch.uint8, device=dev)
+            self.scratch, self.scratch_ptr = _scratch(self.scratch_bytes, dev)
         self.device = dev
 
     def flat_plan(self):
@@ -1420,8 +1449,7 @@ class OptimTable:
         second set of anything - with the gradient of tensor i the fp32 slice flat[offsets[i] : offsets[i] + n_i] that grads_gather fills.
         flat: a contiguous fp32 tensor of at least flat_plan()'s total elements on this device, 16-byte aligned."""
         offsets, total = self.flat_plan()
-        if flat.dtype != torch.float32 or flat.dim() != 1 or not flat.is_contiguous() or flat.numel() < total or flat.device != self.device:
-            raise ValueError(f"flat must be a contiguous fp32 vector of at least {total} elements on {self.device}")
+        _check_flat(flat, total, self.device)
         slices = [flat[o:o + p.numel()].view(p.shape) for o, p in zip(offsets, self.params)]
         return OptimTable(self.params, slices, self.masters, self.exp_avgs, self.exp_avg_sqs, self.decay, state=self.state)
 
@@ -1430,20 +1458,6 @@ class OptimTable:
         raw = self.state.cpu()
         f = raw.view(torch.float32)
         return {"norm": float(f[0]), "coef": float(f[1]), "finite": int(raw[2]), "skipped": int(raw[3])}
-
-
-OPTIM_GUARD = 64         # sentinel elements before and after every output of the poison forms (a multiple of 16 bytes in either dtype)
-
-
-def _guarded_copy(t: torch.Tensor):
-    n = t.numel()
-    whole = torch.full((n + 2 * OPTIM_GUARD,), GUARD, dtype=t.dtype, device=t.device)
-    whole[OPTIM_GUARD:OPTIM_GUARD + n] = t.reshape(-1)
-    return whole[OPTIM_GUARD:OPTIM_GUARD + n].view(t.shape), whole
-
-
-def _guarded_copies_intact(pairs) -> bool:
-    return all(bool((w[:OPTIM_GUARD] == GUARD).all()) and bool((w[OPTIM_GUARD + t.numel():] == GUARD).all()) for t, w in pairs)
 
 
 def adamw_step(table: OptimTable, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, max_norm=0.0, grad_scale=1.0,
@@ -1455,54 +1469,29 @@ def adamw_step(table: OptimTable, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_d
     elements, with a scratch of 0xFF bytes, and the results are copied back; -> whether all sentinels are intact (else None)."""
     lib = load_bwd_library()
     bc1, bc2 = 1.0 - float(beta1) ** int(step), 1.0 - float(beta2) ** int(step)
-    run, pairs, back = table, [], []
+    run, back = table, []
     if poison:
-        cols = []
-        for src in (table.params, table.masters, table.exp_avgs, table.exp_avg_sqs):
-            col = []
-            for t in src:
-                if t is None:
-                    col.append(None)
-                    continue
-                c, whole = _guarded_copy(t)
-                pairs.append((c, whole))
-                back.append((t, c))
-                col.append(c)
-            cols.append(col)
+        cols = [_guarded_copies(src, back) for src in (table.params, table.masters, table.exp_avgs, table.exp_avg_sqs)]
         run = OptimTable(cols[0], table.grads, cols[1], cols[2], cols[3], table.decay, state=table.state)
-        run.scratch = _nan_bytes(run.scratch_bytes, table.device)
+        run.scratch, run.scratch_ptr = _scratch(run.scratch_bytes, table.device, poison=True)
     with torch.cuda.device(table.device):
         _check(lib.pcad_adamw_step(run.table.data_ptr(), run.chunk_map.data_ptr(), run.count, run.chunks, run.state.data_ptr(),
-                                   _aligned(run.scratch), run.scratch_bytes, float(lr), float(beta1), float(beta2), float(eps),
+                                   run.scratch_ptr, run.scratch_bytes, float(lr), float(beta1), float(beta2), float(eps),
                                    float(weight_decay), bc1, bc2, float(max_norm), float(grad_scale), _stream_ptr()), "pcad_adamw_step")
-    if not poison:
-        return None
-    with torch.no_grad():
-        for t, c in back:
-            t.copy_(c)
-    return _guarded_copies_intact(pairs)
+    return _copy_back(back) if poison else None
 
 
 def zero_grads(table: OptimTable, poison=False):
     """pcad_zero_grads: every gradient of the table set to zero in one launch, storage kept.  poison (tests): as adamw_step, on guarded
     NaN-filled copies of the gradients."""
     lib = load_bwd_library()
-    run, pairs = table, []
+    run, back = table, []
     if poison:
-        grads = []
-        for g in table.grads:
-            c, whole = _guarded_copy(torch.full_like(g, float("nan")))
-            pairs.append((c, whole))
-            grads.append(c)
+        grads = _guarded_copies(table.grads, back, blank=True)
         run = OptimTable(table.params, grads, table.masters, table.exp_avgs, table.exp_avg_sqs, table.decay, state=table.state)
     with torch.cuda.device(table.device):
         _check(lib.pcad_zero_grads(run.table.data_ptr(), run.chunk_map.data_ptr(), run.count, run.chunks, _stream_ptr()), "pcad_zero_grads")
-    if not poison:
-        return None
-    with torch.no_grad():
-        for g, (c, _) in zip(table.grads, pairs):
-            g.copy_(c)
-    return _guarded_copies_intact(pairs)
+    return _copy_back(back) if poison else None
 
 
 def grads_gather(table: OptimTable, flat: torch.Tensor, offsets: torch.Tensor, poison=False):
@@ -1515,35 +1504,27 @@ def grads_gather(table: OptimTable, flat: torch.Tensor, offsets: torch.Tensor, p
     lib = load_bwd_library()
     _require_gpu(flat, "flat")
     _require_gpu(offsets, "offsets")
-    total = table.flat_plan()[1]
-    if flat.dtype != torch.float32 or flat.dim() != 1 or not flat.is_contiguous() or flat.numel() < total or flat.device != table.device:
-        raise ValueError(f"flat must be a contiguous fp32 vector of at least {total} elements on {table.device}")
+    _check_flat(flat, table.flat_plan()[1], table.device)
     if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() < table.count or offsets.device != table.device:
         raise ValueError(f"offsets must be a contiguous int64 tensor of {table.count} elements on {table.device}")
-    run, pairs = flat, []
+    run, back = flat, []
     if poison:
-        run, whole = _guarded_copy(flat)
-        pairs.append((run, whole))
+        run, = _guarded_copies([flat], back)
     with torch.cuda.device(table.device):
         _check(lib.pcad_grads_gather(table.table.data_ptr(), table.chunk_map.data_ptr(), table.count, table.chunks, offsets.data_ptr(),
                                      run.data_ptr(), run.numel(), _stream_ptr()), "pcad_grads_gather")
-    if not poison:
-        return None
-    with torch.no_grad():
-        flat.copy_(run)
-    return _guarded_copies_intact(pairs)
+    return _copy_back(back) if poison else None
 
 
 # ---- fp32 main gradients: the weight gradient of a linear layer, accumulated in place (include/pcad_bwd.h pcad_linear_wgrad) ----
 WGRAD_MIN, WGRAD_MAX = 8, 8192      # include/pcad_bwd.h: N and K are multiples of 8 inside [8, 8192]
-WGRAD_GUARD = -1234.0               # the sentinel around a poisoned output (rows above and below, 4 columns left and right)
+WGRAD_GUARD = GUARD                 # the sentinel around a poisoned output (rows above and below, 4 columns left and right)
 
 _log = logging.getLogger(__name__)
 
 
 def linear_wgrad_slabs(M: int, N: int, K: int):
     """pcad_linear_wgrad_slabs (host only): -> (slabs, rows_per_slab) of the split of the M rows; a refused shape raises"""
-    import ctypes as C
     rows = C.c_int64(0)
     slabs = load_bwd_library().pcad_linear_wgrad_slabs(int(M), int(N), int(K), C.byref(rows))
     if slabs < 0:
@@ -1597,16 +1578,15 @@ def linear_wgrad(dy, x, out=None, accumulate=False, poison=False):
         run = whole[1:N + 1, 4:K + 4]
         run.copy_(out if accumulate else torch.full_like(out, float("nan")))
     nb = lib.pcad_linear_wgrad_scratch_bytes(M, N, K)
-    scratch = _bwd_scratch(nb, dev, poison)
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
-        _check(lib.pcad_linear_wgrad(dyr.data_ptr(), lddy, xr.data_ptr(), ldx, run.data_ptr(), run.stride(0), M, N, K, int(bool(accumulate)), _aligned(scratch), nb, _stream_ptr()), "pcad_linear_wgrad")
+        _check(lib.pcad_linear_wgrad(dyr.data_ptr(), lddy, xr.data_ptr(), ldx, run.data_ptr(), run.stride(0), M, N, K, int(bool(accumulate)),
+                                     scratch_ptr, nb, _stream_ptr()), "pcad_linear_wgrad")
     linear_wgrad.guards_ok = None
     if poison:
         with torch.no_grad():
             out.copy_(run)
-        inner = torch.zeros_like(whole, dtype=torch.bool)
-        inner[1:N + 1, 4:K + 4] = True
-        linear_wgrad.guards_ok = bool((whole[~inner] == WGRAD_GUARD).all())
+        linear_wgrad.guards_ok = _guards_intact([(run, whole)])
     return out
 
 
