@@ -15,7 +15,8 @@ overrides the adapter's base_model_name_or_path.  Hub ids resolve from local fil
 `train` fine-tunes `training.TrainableCaduceusForSequenceClassification` - frozen trunk, LoRA factors, `score` - with
 `optim.AdamW` and `pretrain`'s schedules, window order and checkpoint form; one process and one GPU under plain `python`, data-parallel under `torchrun` as `pretrain` is (world x
 `--gradient_accumulation_steps` micro-batches per step, one fused gradient all-reduce; the environment variable PCAD_DDP_BACKEND = nccl,
-the default, or gloo - no flag, as below; every rank evaluates the whole validation set, rank 0 logs and writes).  It takes the reference
+the default, or gloo - no flag, as below; the validation's batches of `--eval_batch_size` are dealt to the ranks in contiguous blocks and
+one gather per evaluation hands every rank all logits; rank 0 logs and writes).  It takes the reference
 `train()`'s flag names and defaults, except that `--bf16` defaults to false (float32, as `predict` / `evaluate` default) and means
 bf16 trunk and kernels with fp32 factors and score; `save_total_limit` is 5.  Additions: `--device`, `--pooling`, `--train_lora {1,0}`
 (0: the frozen-trunk mode), `--max_grad_norm` (1.0) and `--lora_dropout` (0.0; any other value is refused, as is `--use_wandb`).
@@ -34,7 +35,6 @@ from __future__ import annotations
 import json
 import logging
 import os
-import shutil
 import time
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -341,15 +341,7 @@ def _labels_for(labels: np.ndarray, task_type: str) -> np.ndarray:
     return np.asarray(labels).astype(np.float32)
 
 
-def _interval(strategy: str, steps: int, per_epoch: int, flag: str) -> int:
-    if strategy == "no":
-        return 0
-    if strategy == "steps":
-        return max(0, int(steps))
-    if strategy == "epoch":
-        return per_epoch
-    raise SystemExit(f"--{flag} must be one of no, steps, epoch (got {strategy!r})")
-
+_interval = pretrain.interval
 
 SAVE_TOTAL_LIMIT = 5          # the reference's TrainingArguments(save_total_limit=5)
 
@@ -379,19 +371,16 @@ class FinetuneTrainer(pretrain.Trainer):
         res["eval_runtime"] = round(time.time() - t0, 4)
         entry = dict(res, step=self.step, epoch=round(self.epoch(), 4))
         self.log_history.append(entry)
-        if self.rank == 0:                                      # every rank evaluates the whole set, with no communication: the same values
+        if self.rank == 0:                                      # the logits are gathered: every rank holds the same values
             logger.info(json.dumps(entry))
         return res
 
     def save_checkpoint(self):
-        path = os.path.join(self.a.output_dir, f"checkpoint-{self.step}")
+        path = self.checkpoint_path()
         self.model.save_adapter(path, self.a.model_name)
         torch.save(self.opt.state_dict(), os.path.join(path, "optimizer.pt"))
         pretrain._write_json(os.path.join(path, "trainer_state.json"), self.trainer_state())
-        kept = sorted((int(d.split("-")[1]), d) for d in os.listdir(self.a.output_dir)
-                      if d.startswith("checkpoint-") and d.split("-")[1].isdigit())
-        for _, d in kept[:-SAVE_TOTAL_LIMIT]:
-            shutil.rmtree(os.path.join(self.a.output_dir, d))
+        pretrain.rotate_checkpoints(self.a.output_dir, SAVE_TOTAL_LIMIT)
         return path
 
     def restore_inputs(self, path: str):
@@ -413,11 +402,13 @@ class FinetuneTrainer(pretrain.Trainer):
 
 
 def predict_logits_trainable(model, ids: np.ndarray, device: str, batch_size: int) -> np.ndarray:
-    """fp32 logits [N, num_labels] of the trainable model under torch.no_grad()"""
+    """fp32 logits [N, num_labels] of the trainable model under torch.no_grad(), one forward per batch of `batch_size` windows.  In a
+    process group the batches are dealt to the ranks in contiguous blocks (`sharding.batch_block`) - every forward sees
+    the rows it sees in a one-process run - and one gather hands every rank all rows."""
     t = torch.from_numpy(np.ascontiguousarray(ids))
     with torch.no_grad():
-        parts = [model(t[b0:b0 + batch_size].to(device)).logits for b0 in range(0, len(ids), batch_size)]
-    return torch.cat(parts, dim=0).float().cpu().numpy() if parts else np.zeros((0, model.num_labels), dtype=np.float32)
+        logits = sharding.gather_batch_rows(len(ids), batch_size, lambda lo, hi: model(t[lo:hi].to(device)).logits, int(model.num_labels), device)
+    return logits.cpu().numpy()
 
 
 RECOMPUTE_ENV = "PCAD_TRAIN_RECOMPUTE"

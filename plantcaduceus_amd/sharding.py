@@ -113,3 +113,27 @@ def all_gather_rows(local: torch.Tensor, n_total: int) -> torch.Tensor:
     if not (dist.is_available() and dist.is_initialized()):
         return local[:n_total]
     return _all_gather(local, ws)[:n_total]                 # also at world size 1 (a one-rank torchrun): same code path as N ranks
+
+
+def batch_block(n: int, batch: int, rank: int, world_size: int) -> Tuple[int, int, int]:
+    """The batch-block rule of an evaluation inside a training run.  The loss batches are the single-process grid of
+    `batch` consecutive rows, the last one short; with nb = ceil(n / batch) of them rank `rank` takes the contiguous block of batches
+    [rank * ceil(nb / W), ...), whole batches only.  -> (first row, one past the last row, rows_per_rank = ceil(nb / W) * batch).
+    Every rank before the one that holds row n - 1 has exactly rows_per_rank rows, and every rank after it has none."""
+    batch = max(1, int(batch))
+    nb = -(-int(n) // batch) if n > 0 else 0
+    b0, b1, per = shard_bounds(nb, rank, world_size)
+    return min(b0 * batch, n), min(b1 * batch, n), per * batch
+
+
+def gather_batch_rows(n: int, batch: int, run_batch, width: int, device, dtype=torch.float32) -> torch.Tensor:
+    """[n, width] in row order on every rank: `run_batch(lo, hi)` -> [hi - lo, width] is called once per loss batch of this rank's
+    `batch_block`, with exactly the rows a one-process run hands it, and ONE gather (`all_gather_blocks`, staged through the host for
+    gloo) reassembles the ranks' blocks.  A rank without a batch still takes part.  Outside a process group: every batch, no collective."""
+    rank, ws = world()
+    lo, hi, per = batch_block(n, batch, rank, ws)
+    parts = [run_batch(b0, min(b0 + batch, hi)).to(dtype) for b0 in range(lo, hi, max(1, int(batch)))]
+    local = torch.cat(parts, dim=0) if parts else torch.zeros((0, width), dtype=dtype, device=device)
+    if n <= 0 or not (dist.is_available() and dist.is_initialized()):       # n is the same on every rank: no rows, nothing to gather
+        return local
+    return all_gather_blocks(pad_rows(local, per))[:n]
