@@ -1,5 +1,5 @@
 /* pcad_bwd.h - C ABI of libpcad_bwd.so: the backward operators of a Caduceus block beyond the selective scan, and of the masked-LM
- * loss head and of the pooled sequence-classification head (training support).
+ * loss head and of the pooled sequence-classification head, and the dropout-masked LoRA down-projection (training support).
  *
  * A third library beside libpcad.so (include/pcad.h: the inference ABI) and libpcad_train.so (include/pcad_train.h: the selective
  * scan's backward), whose exported symbol sets stay as they are.  This one is OPEN: a later backward operator is added here - its
@@ -8,12 +8,12 @@
  * libpcad_bwd.so links libpcad.so (same directory) and shares its conventions: status codes (pcad_status), dtypes (pcad_dtype),
  * pcad_stream, and the calling thread's pcad_last_error() text.  Built by the same Makefile from csrc/bwd_api.hip, csrc/conv_bwd.hip,
  * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip, csrc/optim.hip (the optimizer step that uses the gradients and their gathering
- * into one buffer for a data-parallel run) and csrc/wgrad.hip (the weight gradient of a linear layer into an fp32 main gradient: the
- * last section below).
+ * into one buffer for a data-parallel run), csrc/wgrad.hip (the weight gradient of a linear layer into an fp32 main gradient) and
+ * csrc/lora.hip (the dropout-masked down-projection of a LoRA branch, forward and backward: the last section below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
- * pcad_last_error(); every output is overwritten, never accumulated (the one exception: pcad_linear_wgrad with accumulate != 0); no floating-point atomics - every sum has a fixed order, so two
+ * pcad_last_error(); every output is overwritten, never accumulated (the two stated exceptions: pcad_linear_wgrad with accumulate != 0, and pcad_lora_down_bwd, which updates dx in place); no floating-point atomics - every sum has a fixed order, so two
  * calls give the same bits; all in-tensor offsets are 64-bit; rows outside a strand are never read or written. */
 #ifndef PCAD_BWD_H
 #define PCAD_BWD_H
@@ -223,6 +223,53 @@ int64_t pcad_linear_wgrad_slabs(int64_t M, int N, int K, int64_t* rows_per_slab_
 size_t pcad_linear_wgrad_scratch_bytes(int64_t M, int N, int K);
 int pcad_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw,
                       int64_t M, int N, int K, int accumulate, void* scratch, size_t scratch_bytes, pcad_stream stream);
+
+/* ---- LoRA dropout: the masked rank-r down-projection of a LoRA branch and its backward ------------------------
+ * Replaces: `lora_A(F.dropout(x, p))` of a PEFT LoRA layer and its backward, without the dropped copy of x and without a mask tensor.
+ * The mask is a pure function of (seed, stream_id, row, column).  For a drop probability p in [0, 1):
+ *   T = floor(p 65536 + 0.5)   (T = 65536 is refused)        c = 65536 / (65536 - T) as fp32: the keep scale, unbiased for this mask
+ *   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with
+ *   counter = (k >> 3, m, stream_lo, stream_hi), key = (seed_lo, seed_hi) gives the words w0..w3
+ *   h = (w[(k & 7) >> 1] >> (16 (k & 1))) & 0xffff           keep(m, k) = (h >= T)
+ * m is the row index within the call, k the column.  One generator call covers 8 consecutive columns; the mask does not depend on K,
+ * on the leading dimension or on the dtype.  p = 0: T = 0, c = 1, everything is kept.
+ *
+ * Shared limits, each decided without a device (PCAD_ERR_INVALID naming the argument): r in {4, 8, 16}; K % 8 == 0, 8 <= K <= 8192;
+ * ldx, lddx multiples of 8 and >= K; x, dx, A, t, u, dA 16-byte aligned; 0 <= M < 2^32; p with T <= 65535; dtype PCAD_BF16 / PCAD_F32.
+ *
+ * pcad_lora_dropout_mask writes keep(m, k) as bytes (1 / 0) into keep_u8 [M, K], row stride ldk >= K bytes.  It exists so that the
+ * device generator can be compared bit for bit with a restatement; it is not on the training path. */
+int pcad_lora_dropout_mask(uint8_t* keep_u8, int64_t M, int K, int64_t ldk, double p, uint64_t seed, uint64_t stream_id, pcad_stream stream);
+
+/* t[m, j] = c sum_k keep(m, k) x[m, k] A[j, k]: fp32 products and sums, t fp32 [M, r] contiguous.
+ *   x [M, K] dtype, row stride ldx;  A fp32 [r, K] contiguous
+ * Per row the lane that owns columns 8 l .. 8 l + 7 of each 512-column chunk adds its products in column order, chunk after chunk; the
+ * 64 lanes' sums are added by the xor butterfly (32, 16, ... 1) and the total is multiplied by c once.  M == 0: nothing is done. */
+int pcad_lora_down(const void* x, int64_t ldx, const float* A, float* t, int64_t M, int K, int r, double p, uint64_t seed,
+                   uint64_t stream_id, int dtype, pcad_stream stream);
+
+/* The backward of pcad_lora_down for the same (p, seed, stream_id), with u = dL/dt fp32 [M, r] contiguous:
+ *   dA[j, k] = c sum_m keep(m, k) u[m, j] x[m, k]                                    fp32 [r, K] contiguous, overwritten
+ *   dx[m, k] = round_dtype(dx[m, k] + c keep(m, k) sum_j u[m, j] A[j, k])            [M, K] dtype, row stride lddx
+ * This entry is a stated exception to "every output is overwritten": dx is updated IN PLACE - the caller hands over dx0 = dy W, the
+ * gradient through the frozen weight, and receives the sum; a dropped element keeps dx0's bits.  dx or dA may be NULL (not
+ * computed), not both; neither changes the other's bits.
+ * The rows are cut into slabs by (M, K) and the constants of csrc/kernels.hpp alone - never by the device:
+ *   chunks = ceil(K / 512)     want = min(256, max(1, 1024 / chunks))   (integer division)
+ *   rows_per_slab = round_up(ceil(M / want), 64)     slabs = ceil(M / rows_per_slab)
+ * Within a slab and a 512-column chunk, wave w of 4 adds rows w, w + 4, ... in index order, the four waves' sums are added in wave
+ * order, the slab's partial goes to scratch [slab][r][K] and a second kernel adds the slabs in slab order and multiplies by c once.
+ * The sum over j runs in index order.  No floating-point atomics.
+ * pcad_lora_down_bwd_slabs returns slabs and stores rows_per_slab (host only; M == 0: 0 and 0; a refused shape: -1 and the message in
+ * pcad_last_error()).
+ *   scratch    pcad_lora_down_bwd_scratch_bytes(M, K, r) = round_up(slabs r K 4, 256) bytes (0 for a refused shape); needed only with
+ *              dA, may be NULL when that is 0
+ * M == 0: dA (when given) is written as zeros, nothing else is done. */
+int64_t pcad_lora_down_bwd_slabs(int64_t M, int K, int r, int64_t* rows_per_slab_out);
+size_t pcad_lora_down_bwd_scratch_bytes(int64_t M, int K, int r);
+int pcad_lora_down_bwd(const void* x, int64_t ldx, const float* A, const float* u, void* dx, int64_t lddx, float* dA, void* scratch,
+                       size_t scratch_bytes, int64_t M, int K, int r, double p, uint64_t seed, uint64_t stream_id, int dtype,
+                       pcad_stream stream);
 
 #ifdef __cplusplus
 }

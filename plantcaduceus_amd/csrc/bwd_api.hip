@@ -336,4 +336,95 @@ int pcad_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, 
     return PCAD_OK;
 }
 
+// ---- the dropout-masked down-projection of a LoRA branch (csrc/lora.hip) ----
+static int lora_p_check(const char* who, double p) {
+    const int64_t T = lora_threshold(p);
+    if (T < 0 || T > 65535)
+        return fail(PCAD_ERR_INVALID, "%s: p must be in [0, 1) with floor(p 65536 + 0.5) <= 65535 (p=%g)", who, p);
+    return PCAD_OK;
+}
+
+static int lora_shape_check(const char* who, int64_t M, int K, int r, bool with_r) {
+    if (M < 0 || M >= ((int64_t)1 << 32)) return fail(PCAD_ERR_INVALID, "%s: M must be in [0, 2^32) (M=%lld)", who, (long long)M);
+    if (K < 8 || K > LORA_MAX_K || K % 8) return fail(PCAD_ERR_INVALID, "%s: K must be a multiple of 8 in [8, %d] (K=%d)", who, LORA_MAX_K, K);
+    if (with_r && r != 4 && r != 8 && r != 16) return fail(PCAD_ERR_INVALID, "%s: r must be 4, 8 or 16 (r=%d)", who, r);
+    return PCAD_OK;
+}
+
+int pcad_lora_dropout_mask(uint8_t* keep_u8, int64_t M, int K, int64_t ldk, double p, uint64_t seed, uint64_t stream_id, pcad_stream stream) {
+    const char* who = "pcad_lora_dropout_mask";
+    if (int rc = lora_shape_check(who, M, K, 0, false)) return rc;
+    if (ldk < K) return fail(PCAD_ERR_INVALID, "%s: ldk must be >= K (ldk=%lld, K=%d)", who, (long long)ldk, K);
+    if (int rc = lora_p_check(who, p)) return rc;
+    if (!keep_u8 && M != 0) return fail(PCAD_ERR_INVALID, "%s: null keep_u8", who);
+    hipError_t err = launch_lora_dropout_mask(keep_u8, M, K, ldk, lora_mask(p, seed, stream_id), (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+// what pcad_lora_down and pcad_lora_down_bwd ask of a [M, K] operand in the model dtype
+static int lora_rows_check(const char* who, const char* name, const char* ldname, const void* ptr, int64_t ld, int K) {
+    if (ld < K || ld % 8) return fail(PCAD_ERR_INVALID, "%s: %s must be a multiple of 8 and >= K (%s=%lld, K=%d)", who, ldname, ldname, (long long)ld, K);
+    if (((uintptr_t)ptr) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, name);
+    return PCAD_OK;
+}
+
+int pcad_lora_down(const void* x, int64_t ldx, const float* A, float* t, int64_t M, int K, int r, double p, uint64_t seed, uint64_t stream_id,
+                   int dtype, pcad_stream stream) {
+    const char* who = "pcad_lora_down";
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (int rc = lora_shape_check(who, M, K, r, true)) return rc;
+    if (int rc = lora_p_check(who, p)) return rc;
+    if (!A) return fail(PCAD_ERR_INVALID, "%s: null A", who);
+    if (M != 0 && !x) return fail(PCAD_ERR_INVALID, "%s: null x", who);
+    if (M != 0 && !t) return fail(PCAD_ERR_INVALID, "%s: null t", who);
+    if (int rc = lora_rows_check(who, "x", "ldx", x, ldx, K)) return rc;
+    if (((uintptr_t)A) % 16) return fail(PCAD_ERR_INVALID, "%s: A must be 16-byte aligned", who);
+    if (((uintptr_t)t) % 16) return fail(PCAD_ERR_INVALID, "%s: t must be 16-byte aligned", who);
+    hipError_t err = launch_lora_down({.x = x, .ldx = ldx, .A = A, .t = t, .M = M, .K = K, .r = r, .mask = lora_mask(p, seed, stream_id), .dt = dtype},
+                                      (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int64_t pcad_lora_down_bwd_slabs(int64_t M, int K, int r, int64_t* rows_per_slab_out) {
+    int64_t rows = 0;
+    if (rows_per_slab_out) *rows_per_slab_out = 0;
+    if (lora_shape_check("pcad_lora_down_bwd_slabs", M, K, r, true)) return -1;
+    const int64_t slabs = lora_down_bwd_slabs(M, K, &rows);
+    if (rows_per_slab_out) *rows_per_slab_out = rows;
+    return slabs;
+}
+
+size_t pcad_lora_down_bwd_scratch_bytes(int64_t M, int K, int r) {
+    if (M < 0 || M >= ((int64_t)1 << 32) || K < 8 || K > LORA_MAX_K || K % 8 || (r != 4 && r != 8 && r != 16)) return 0;
+    return lora_down_bwd_bytes(M, K, r);
+}
+
+int pcad_lora_down_bwd(const void* x, int64_t ldx, const float* A, const float* u, void* dx, int64_t lddx, float* dA, void* scratch,
+                       size_t scratch_bytes, int64_t M, int K, int r, double p, uint64_t seed, uint64_t stream_id, int dtype, pcad_stream stream) {
+    const char* who = "pcad_lora_down_bwd";
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (int rc = lora_shape_check(who, M, K, r, true)) return rc;
+    if (int rc = lora_p_check(who, p)) return rc;
+    if (!dx && !dA) return fail(PCAD_ERR_INVALID, "%s: no output requested (dx and dA are both NULL)", who);
+    if (!A) return fail(PCAD_ERR_INVALID, "%s: null A", who);
+    if (M != 0 && !x) return fail(PCAD_ERR_INVALID, "%s: null x", who);
+    if (M != 0 && !u) return fail(PCAD_ERR_INVALID, "%s: null u", who);
+    if (int rc = lora_rows_check(who, "x", "ldx", x, ldx, K)) return rc;
+    if (dx)
+        if (int rc = lora_rows_check(who, "dx", "lddx", dx, lddx, K)) return rc;
+    const struct { const void* ptr; const char* name; } al[] = {{A, "A"}, {u, "u"}, {dA, "dA"}};
+    for (const auto& q : al)
+        if (((uintptr_t)q.ptr) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, q.name);
+    const size_t need = dA ? lora_down_bwd_bytes(M, K, r) : 0;
+    if (need > 0 && (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < need))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_lora_down_bwd_scratch_bytes large", who);
+    hipError_t err = launch_lora_down_bwd({.x = x, .ldx = ldx, .A = A, .u = u, .dx = dx, .lddx = lddx, .dA = dA, .scratch = scratch, .M = M,
+                                           .K = K, .r = r, .mask = lora_mask(p, seed, stream_id), .dt = dtype},
+                                          (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 }  // extern "C"

@@ -496,6 +496,57 @@ int64_t wgrad_slabs(int64_t M, int N, int K, int64_t* rows_per_slab);
 size_t wgrad_bytes(int64_t M, int N, int K);
 hipError_t launch_linear_wgrad(const LinearWgradLaunch& a, hipStream_t s);
 
+// lora.hip (libpcad_bwd.so): the dropout-masked down-projection of a LoRA branch and its backward (pcad_bwd.h
+// pcad_lora_down / pcad_lora_down_bwd / pcad_lora_dropout_mask).  The keep mask is a pure function of (seed, stream, row, column):
+// one Philox4x32-10 call per 8 consecutive columns of a row, 16 bits per element, keep = (bits >= T).
+//   x [M, K] dtype (row stride ldx), A fp32 [r, K], t / u fp32 [M, r], dx [M, K] dtype (row stride lddx), dA fp32 [r, K]
+//   K % 8 == 0, 8 <= K <= LORA_MAX_K, r in {4, 8, 16}, 0 <= M < 2^32
+// Forward: a wave owns LORA_FWD_ROWS rows and walks their LORA_CHUNK-column chunks in index order; a lane owns 8 consecutive columns
+// of a chunk; the r sums of a row are added over the lanes by the xor butterfly (32, 16, ... 1) and scaled by c once.
+// Backward: grid (chunks, slabs), a block of 4 waves owns one LORA_CHUNK-column chunk of one row slab; wave w takes the slab's rows
+// w, w + 4, ... in index order, the 4 waves' dA sums are added in wave order through LDS and go to scratch [slab][r][K]; a second
+// kernel adds the slabs in index order and scales by c once.  The rows are cut into slabs by (M, K) and these constants alone:
+//   chunks = ceil(K / LORA_CHUNK)     want = clamp(LORA_TARGET_BLOCKS / chunks, 1, LORA_MAX_SLABS)            (integer division)
+//   rows_per_slab = round_up(ceil(M / want), LORA_SLAB_ROWS)     slabs = ceil(M / rows_per_slab)             (M == 0: 0 and 0)
+// scratch: lora_down_bwd_bytes(M, K, r) = round_up(slabs r K 4, 256) bytes, 256-byte aligned.
+constexpr int LORA_CHUNK = 512;                   // columns a wave covers at once: 64 lanes x 8
+constexpr int LORA_FWD_ROWS = 4;                  // rows a wave of the forward walks together
+constexpr int LORA_TARGET_BLOCKS = 1024;          // blocks the backward's split aims for
+constexpr int LORA_MAX_SLABS = 256;
+constexpr int LORA_SLAB_ROWS = 64;                // rows_per_slab is a multiple of this
+constexpr int LORA_MAX_K = 8192;
+struct LoraMask {
+    uint32_t T;                       // drop threshold in [0, 65535]: floor(p 65536 + 0.5)
+    float c;                          // keep scale 65536 / (65536 - T), rounded once
+    uint32_t seed_lo, seed_hi, stream_lo, stream_hi;
+};
+LoraMask lora_mask(double p, uint64_t seed, uint64_t stream_id);     // the caller has checked p (lora_threshold(p) <= 65535)
+int64_t lora_threshold(double p);     // floor(p 65536 + 0.5), or -1 for a p that is negative or not finite
+struct LoraDownLaunch {
+    const void* x;  int64_t ldx;
+    const float* A;
+    float* t;
+    int64_t M;  int K, r;
+    LoraMask mask;
+    int dt;
+};
+struct LoraDownBwdLaunch {
+    const void* x;  int64_t ldx;
+    const float* A;
+    const float* u;
+    void* dx;  int64_t lddx;          // in place on dx0; nullptr: not computed
+    float* dA;                        // nullptr: not computed
+    void* scratch;
+    int64_t M;  int K, r;
+    LoraMask mask;
+    int dt;
+};
+int64_t lora_down_bwd_slabs(int64_t M, int K, int64_t* rows_per_slab);
+size_t lora_down_bwd_bytes(int64_t M, int K, int r);
+hipError_t launch_lora_dropout_mask(uint8_t* keep, int64_t M, int K, int64_t ldk, const LoraMask& mask, hipStream_t s);
+hipError_t launch_lora_down(const LoraDownLaunch& a, hipStream_t s);
+hipError_t launch_lora_down_bwd(const LoraDownBwdLaunch& a, hipStream_t s);
+
 // pack.hip --------------------------------------------------------------------------------------
 // rows (strand b, p_q) and (strand B + b, L - 1 - p_q) of a [2B*L, E] activation tensor -> out[(strand * P + q), E]
 struct GatherRowsLaunch {

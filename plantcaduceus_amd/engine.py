@@ -157,6 +157,15 @@ BWD_SIGNATURES = {
     "pcad_linear_wgrad_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "pcad_linear_wgrad": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the dropout-masked down-projection of a LoRA branch and its backward (plantcaduceus_amd.ops.lora_down / lora_down_bwd /
+    # lora_dropout_linear_fn)
+    "pcad_lora_dropout_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "pcad_lora_down": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
+                                 C.c_int, C.c_void_p]),
+    "pcad_lora_down_bwd_slabs": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "pcad_lora_down_bwd_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "pcad_lora_down_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
 }
 BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
 

@@ -19,7 +19,8 @@ the default, or gloo - no flag, as below; the validation's batches of `--eval_ba
 one gather per evaluation hands every rank all logits; rank 0 logs and writes).  It takes the reference
 `train()`'s flag names and defaults, except that `--bf16` defaults to false (float32, as `predict` / `evaluate` default) and means
 bf16 trunk and kernels with fp32 factors and score; `save_total_limit` is 5.  Additions: `--device`, `--pooling`, `--train_lora {1,0}`
-(0: the frozen-trunk mode), `--max_grad_norm` (1.0) and `--lora_dropout` (0.0; any other value is refused, as is `--use_wandb`).
+(0: the frozen-trunk mode), `--max_grad_norm` (1.0) and `--lora_dropout` (0.0; any other value is refused, as is `--use_wandb`).  The
+dropout on the LoRA branches (the reference's lora_dropout=0.1) is set by the environment variable PCAD_LORA_DROPOUT.
 `output_dir/checkpoint-<step>/` is an adapter directory plus `optimizer.pt` and `trainer_state.json`; `output_dir/` ends as the final
 adapter, which `predict --checkpoint_dir <output_dir> --lora-deltas apply` loads (after `--train_lora 0`: the default `auto`).
 Whether the blocks' activations are kept or recomputed in the backward (the same bits either way) is `recompute_policy`'s
@@ -356,6 +357,11 @@ class FinetuneTrainer(pretrain.Trainer):
         super().__init__(model, optimizer, source, None, a, max_steps, int(a.warmup_steps), rank, world)
         self.valid = valid
 
+    def before_micro_step(self, j: int, n: int):
+        """the dropout masks of micro-batch j of this step are those it has in the one-process run: a function of (seed, step n + j), so
+        that W ranks x accumulation A draw what one process with accumulation A W draws, and a resumed run needs no generator state"""
+        self.model.dropout_step = self.step * n + j
+
     def micro_step(self, ids, labels, _weights):
         dev = self.a.device
         out = self.model(ids.to(dev), labels.to(dev))
@@ -412,6 +418,25 @@ def predict_logits_trainable(model, ids: np.ndarray, device: str, batch_size: in
 
 
 RECOMPUTE_ENV = "PCAD_TRAIN_RECOMPUTE"
+DROPOUT_ENV = "PCAD_LORA_DROPOUT"
+
+
+def lora_dropout_from_env(env=None, train_lora: bool = True) -> float:
+    """The dropout rate of the LoRA branches from the environment variable PCAD_LORA_DROPOUT (`env`: a mapping, os.environ
+    when None): unset or empty 0.0; a number in [0, 1) whose threshold floor(p 65536 + 0.5) is at most 65535.  Anything else, and a
+    rate above 0 with --train_lora 0 (frozen factors have no branch to regularise), exits naming the variable."""
+    from .ops import lora_dropout_threshold
+    val = str((os.environ if env is None else env).get(DROPOUT_ENV, "")).strip()
+    if not val:
+        return 0.0
+    try:
+        p = float(val)
+        lora_dropout_threshold(p)
+    except ValueError:
+        raise SystemExit(f"{DROPOUT_ENV} must be a number in [0, 1), got {val!r}")
+    if p > 0 and not train_lora:
+        raise SystemExit(f"{DROPOUT_ENV}={val} with --train_lora 0: the factors are frozen at zero, there is no LoRA branch to drop out; unset one")
+    return p
 
 
 def recompute_policy(bytes_per_window: int, batch: int, free_bytes: int, env=None, train_lora: bool = True) -> bool:
@@ -456,8 +481,9 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     if use_wandb:
         raise SystemExit("--use_wandb is not supported: the log history is written to trainer_state.json")
     if float(lora_dropout) != 0.0:
-        raise SystemExit(f"--lora_dropout {lora_dropout} is not supported: the factors are trained in the merged form, which has no place "
-                         "for a dropout on the LoRA branch alone (DESIGN.md §4p); only 0.0 is accepted")
+        raise SystemExit(f"--lora_dropout {lora_dropout} is not accepted on the command line yet: set the environment variable "
+                         f"{DROPOUT_ENV}={lora_dropout} instead (DESIGN.md §4u); the flag itself takes only 0.0")
+    dropout = lora_dropout_from_env(os.environ, bool(int(train_lora)))
     if pooling not in ("mean", "first", "last"):
         raise SystemExit(f"--pooling {pooling} has no backward (max pooling's gradient needs a tie rule nothing pins): one of mean, first, last")
     if lr_scheduler_type not in pretrain.SCHEDULES:
@@ -482,7 +508,10 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     total = max_steps if max_steps > 0 else math.ceil(num_train_epochs * source.steps_per_epoch)
     model = TrainableCaduceusForSequenceClassification.from_pretrained(
         model_name, nl, problem_type, pooling_strategy=pooling, dtype=torch.bfloat16 if bf16 else torch.float32, device=device,
-        train_lora=bool(int(train_lora)), seed=seed)
+        train_lora=bool(int(train_lora)), seed=seed, lora_dropout=dropout)
+    model.dropout_seed = int(seed) % (1 << 64)
+    if dropout > 0:
+        logger.info("LoRA dropout (%s): %g, masks from seed %d and the micro-batch's index in the one-process run", DROPOUT_ENV, dropout, seed)
     per_window = 2 * ids.shape[1] * stored_bytes_per_strand_position(model.config, model.dtype, lora=True)
     free_bytes = torch.cuda.mem_get_info(device)[0]
     if recompute_policy(per_window, train_batch_size, free_bytes, os.environ, model.train_lora):

@@ -17,7 +17,8 @@ Differentiable (each a torch.autograd.Function on this project's backward kernel
 grad; otherwise the plain call, no graph): selective_scan_fn (include/pcad_train.h), causal_conv1d_fn / causal_conv1d_dir and
 rms_norm_fn (include/pcad_bwd.h), mamba_inner_fn as a composition of those around stock F.linear, mlm_loss_head_fn - the end of the
 masked LM's forward with labels (include/pcad_bwd.h pcad_loss_head_bwd) - and pooled_head_fn, the end of the sequence classifier's
-(include/pcad_bwd.h pcad_pooled_head_bwd); lora_linear_fn is a frozen linear with LoRA factors merged in, differentiated by torch matmuls.
+(include/pcad_bwd.h pcad_pooled_head_bwd); lora_linear_fn is a frozen linear with LoRA factors merged in, differentiated by torch matmuls;
+lora_dropout_linear_fn is the unmerged form with a dropout on the branch's input, on the masked rank-r kernels (pcad_lora_down(_bwd); §4u).
 plantcaduceus_amd.training composes the models from them.  linear_fn is F.linear for the masked LM's projections; for a weight that
 carries an fp32 `main_grad` its backward adds dy^T x to that buffer with linear_wgrad (include/pcad_bwd.h pcad_linear_wgrad).
 """
@@ -1332,6 +1333,222 @@ def lora_linear_fn(x, W, A, B, scale):
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, A, B)):
         return _LoraLinearFn.apply(x, W, A, B, float(scale))
     return F.linear(x, _lora_merged(W, A, B, scale, x.dtype))
+
+
+# ---- LoRA dropout: the unmerged form around the masked rank-r kernels (include/pcad_bwd.h pcad_lora_down / pcad_lora_down_bwd) ----
+LORA_RANKS = (4, 8, 16)             # include/pcad_bwd.h: the ranks the kernels are built for
+LORA_MIN_K, LORA_MAX_K = 8, 8192    # ... and K, a multiple of 8 inside this range
+LORA_MASK_GUARD = 0x5A              # the sentinel byte around a poisoned mask
+
+
+def lora_dropout_threshold(p: float) -> int:
+    """T = floor(p 65536 + 0.5) of a drop probability; ValueError outside [0, 65535] (p < 0, p too close to 1, not finite)"""
+    p = float(p)
+    T = int(p * 65536.0 + 0.5) if p == p and 0.0 <= p < 2.0 else -1
+    if not 0 <= T <= 65535:
+        raise ValueError(f"lora dropout p must be in [0, 1) with floor(p 65536 + 0.5) <= 65535, got {p}")
+    return T
+
+
+def lora_dropout_limits(K: int, r: int, p: float = 0.0):
+    """ValueError naming what of (K, r, p) lies outside the kernels' limits"""
+    if r not in LORA_RANKS:
+        raise ValueError(f"lora dropout: r must be one of {LORA_RANKS}, got {r}")
+    if K % 8 or not LORA_MIN_K <= K <= LORA_MAX_K:
+        raise ValueError(f"lora dropout: K must be a multiple of 8 in [{LORA_MIN_K}, {LORA_MAX_K}], got {K}")
+    lora_dropout_threshold(p)
+
+
+def lora_down_bwd_slabs(M: int, K: int, r: int):
+    """pcad_lora_down_bwd_slabs (host only): -> (slabs, rows_per_slab) of the backward's split of the M rows; a refused shape raises"""
+    rows = C.c_int64(0)
+    slabs = load_bwd_library().pcad_lora_down_bwd_slabs(int(M), int(K), int(r), C.byref(rows))
+    if slabs < 0:
+        _check(1, "pcad_lora_down_bwd_slabs")
+    return int(slabs), int(rows.value)
+
+
+def _u64(v: int) -> int:
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise ValueError(f"seed and stream are unsigned 64-bit values, got {v}")
+    return v
+
+
+def _lora_rows(t: torch.Tensor, what: str):
+    """t [..., K] bf16 / fp32 as M rows of K elements `ld` apart, in place when its layout allows it (unit stride inside a row, the
+    leading dimensions collapsing to one row stride that is a multiple of 8 and >= K, a 16-byte aligned start), else through
+    .contiguous().  -> (the tensor that owns the rows, M, ld)"""
+    _dt(t)
+    K = t.shape[-1]
+    M = t.numel() // K if K else 0
+    lead = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n != 1]
+    ok = t.dim() >= 2 and t.stride(-1) == 1 and all(a[1] == b[0] * b[1] for a, b in zip(lead, lead[1:]))
+    ld = lead[-1][1] if lead else K
+    if not ok or ld % 8 or ld < K or t.data_ptr() % 16:
+        t, ld = t.contiguous(), K
+    return t, M, ld
+
+
+def lora_dropout_mask(M: int, K: int, p: float, seed: int, stream: int, poison: bool = False):
+    """pcad_lora_dropout_mask: the keep mask of (p, seed, stream) as a bool [M, K] tensor on the current device.  poison (tests): the
+    kernel writes into a row-strided frame (K + 8 bytes per row) inside a buffer of sentinel bytes - one row above and below, 4 columns
+    left and right; lora_dropout_mask.guards_ok tells whether they are intact."""
+    lib = load_bwd_library()
+    if K % 8 or not LORA_MIN_K <= K <= LORA_MAX_K:
+        raise ValueError(f"lora dropout: K must be a multiple of 8 in [{LORA_MIN_K}, {LORA_MAX_K}], got {K}")
+    lora_dropout_threshold(p)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if poison:
+        whole = torch.full((M + 2, K + 8), LORA_MASK_GUARD, dtype=torch.uint8, device=dev)
+        run = whole[1:M + 1, 4:K + 4]
+    else:
+        whole, run = None, torch.empty((M, K), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_lora_dropout_mask(run.data_ptr(), M, K, run.stride(0) if M else K, float(p), _u64(seed), _u64(stream), _stream_ptr()),
+               "pcad_lora_dropout_mask")
+    lora_dropout_mask.guards_ok = None
+    if poison:
+        outside = torch.ones_like(whole, dtype=torch.bool)
+        outside[1:M + 1, 4:K + 4] = False
+        lora_dropout_mask.guards_ok = bool((whole[outside] == LORA_MASK_GUARD).all()) and bool((run <= 1).all())
+    return run != 0
+
+
+lora_dropout_mask.guards_ok = None
+
+
+def lora_down(x, A, p, seed, stream, poison=False):
+    """pcad_lora_down: t[m, j] = c sum_k keep(m, k) x[m, k] A[j, k] -> fp32 [M, r] over the M rows of x [..., K] (bf16 or fp32; a
+    row-strided view is read in place when its strides meet the limits, else copied); A fp32 [r, K].  Limits violated: ValueError.
+    poison (tests): t starts as NaN between sentinel rows; lora_down.guards_ok tells whether they are intact."""
+    _require_gpu(x, "x")
+    _require_gpu(A, "A")
+    lib = load_bwd_library()
+    if A.dtype != torch.float32 or A.dim() != 2 or A.shape[1] != x.shape[-1]:
+        raise ValueError(f"A must be fp32 [r, K = {x.shape[-1]}], got {A.dtype} {tuple(A.shape)}")
+    r, K = A.shape
+    lora_dropout_limits(K, r, p)
+    xr, M, ldx = _lora_rows(x, "x")
+    Ac = A.detach().contiguous()
+    t, whole = _guarded((M, r), torch.float32, x.device, poison=poison)
+    with torch.cuda.device(x.device):
+        _check(lib.pcad_lora_down(xr.data_ptr(), ldx, Ac.data_ptr(), t.data_ptr(), M, K, r, float(p), _u64(seed), _u64(stream), _dt(xr),
+                                  _stream_ptr()), "pcad_lora_down")
+    lora_down.guards_ok = _guards_intact([(t, whole)]) if poison else None
+    return t
+
+
+lora_down.guards_ok = None
+
+
+def lora_down_bwd(x, A, u, dx, p, seed, stream, want=("dx", "dA"), poison=False):
+    """pcad_lora_down_bwd: with u = dL/dt fp32 [M, r],
+        dA[j, k] = c sum_m keep(m, k) u[m, j] x[m, k]                          -> fp32 [r, K], a new tensor
+        dx[m, k] = round(dx[m, k] + c keep(m, k) sum_j u[m, j] A[j, k])        IN PLACE on dx [..., K] in x's dtype (the caller's dx0)
+    want: which of the two are computed.  -> (dx or None, dA or None).  dx must have unit stride inside a row and meet the kernel's
+    stride limits - it is written, so it is never copied.
+    poison (tests): the scratch starts as 0xFF bytes, dA as NaN between sentinels, and dx is updated on a copy inside a frame of
+    sentinels (one row above and below, 8 columns left and right) that is copied back; lora_down_bwd.guards_ok tells whether all
+    sentinels are intact."""
+    _require_gpu(x, "x")
+    lib = load_bwd_library()
+    want = tuple(want)
+    if not want or any(w not in ("dx", "dA") for w in want):
+        raise ValueError(f"want must name 'dx', 'dA' or both, got {want}")
+    r, K = A.shape
+    lora_dropout_limits(K, r, p)
+    xr, M, ldx = _lora_rows(x, "x")
+    dev = x.device
+    if A.dtype != torch.float32 or u.dtype != torch.float32 or tuple(u.shape) != (M, r) or K != x.shape[-1]:
+        raise ValueError(f"A must be fp32 [r, K], u fp32 [M, r] = [{M}, {r}]; got {A.dtype} {tuple(A.shape)}, {u.dtype} {tuple(u.shape)}")
+    Ac, uc = A.detach().contiguous(), u.contiguous()
+    run = dxr = whole_dx = None
+    lddx = K
+    if "dx" in want:
+        if dx is None or dx.dtype != x.dtype or dx.shape != x.shape or dx.device != dev:
+            raise ValueError(f"dx must be a {x.dtype} tensor of x's shape {tuple(x.shape)} on {dev}")
+        dxr, _, lddx = _lora_rows(dx, "dx")
+        if dxr.data_ptr() != dx.data_ptr():
+            raise ValueError("dx is updated in place: it needs unit stride inside a row, one row stride that is a multiple of 8 and a 16-byte aligned start")
+        run = dxr
+        if poison:
+            whole_dx = torch.full((M + 2, K + 16), GUARD, dtype=x.dtype, device=dev)
+            run = whole_dx[1:M + 1, 8:K + 8]
+            run.copy_(dx.reshape(M, K))
+            lddx = K + 16
+    dA, whole_dA = _guarded((r, K), torch.float32, dev, poison=poison) if "dA" in want else (None, None)
+    nb = lib.pcad_lora_down_bwd_scratch_bytes(M, K, r) if dA is not None else 0
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_lora_down_bwd(xr.data_ptr(), ldx, Ac.data_ptr(), uc.data_ptr(), _ptr(run), lddx, _ptr(dA), scratch_ptr, nb, M, K, r,
+                                      float(p), _u64(seed), _u64(stream), _dt(xr), _stream_ptr()), "pcad_lora_down_bwd")
+    lora_down_bwd.guards_ok = None
+    if poison:
+        if run is not None:
+            with torch.no_grad():
+                dx.copy_(run.reshape(dx.shape))
+        lora_down_bwd.guards_ok = _guards_intact([(dA, whole_dA)] + ([(run, whole_dx)] if run is not None else []))
+    return (dx if "dx" in want else None), dA
+
+
+lora_down_bwd.guards_ok = None
+
+
+def _lora_dropout_forward(x, w, A, B, scale, p, seed, stream):
+    """-> (y, t): y = F.linear(x, w) + (scale t B^T) in x's dtype, t = pcad_lora_down's fp32 [M, r]"""
+    t = lora_down(x, A, p, seed, stream)
+    y = F.linear(x, w)
+    return y + (float(scale) * (t @ B.t())).to(x.dtype).view(y.shape), t
+
+
+class _LoraDropoutLinearFn(torch.autograd.Function):
+    """y = x W^T + scale (c (keep x) A^T) B^T: a frozen linear with an UNMERGED LoRA branch whose input is dropped out by the mask of
+    (p, seed, stream) (include/pcad_bwd.h).  Saved: x, the cast W, A, B and the fp32 [M, r] down-projection t; the mask is regenerated
+    in the backward from (seed, stream, p) on ctx - there is no mask tensor and no dropped copy of x.  W gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, W, A, B, scale, p, seed, stream):
+        w = W.to(x.dtype)
+        y, t = _lora_dropout_forward(x, w, A, B, scale, p, seed, stream)
+        ctx.save_for_backward(x, w, A, B, t)
+        ctx.scale, ctx.mask = float(scale), (float(p), int(seed), int(stream))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w, A, B, t = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = dy.reshape(-1, dy.shape[-1])
+        gf = g.float()
+        dx = dA = dB = None
+        if need[3]:
+            dB = ctx.scale * (gf.t() @ t)
+        want = tuple(n for n, k in (("dx", need[0]), ("dA", need[2])) if k)
+        if want:
+            u = ctx.scale * (gf @ B)
+            dx0 = g.mm(w).view(x.shape) if need[0] else None
+            dx, dA = lora_down_bwd(x, A, u, dx0, *ctx.mask, want=want)
+        return dx, None, dA, dB, None, None, None, None
+
+
+def lora_dropout_linear_fn(x, W, A, B, scale, p, seed, stream):
+    """F.linear(x, W.to(x.dtype)) + (scale * F.linear(F.linear(dropout(x), A), B)).to(x.dtype) with the dropout mask of (p, seed, stream)
+    (DESIGN.md §4u): the unmerged LoRA form - the only one in which a dropout on the branch alone has a place.  x [..., K] bf16 or fp32
+    on the device, W [N, K] frozen, A [r, K] and B [N, r] fp32.  A torch.autograd.Function when x, A or B requires grad, else the plain
+    forward.  A non-contiguous x is read in place when its strides meet the kernels' limits, else copied.  r outside {4, 8, 16}, K not a
+    multiple of 8 in [8, 8192] or a p outside [0, 1): ValueError naming the limit - there is no torch fallback."""
+    _require_gpu(x, "x")
+    if A.dtype != torch.float32 or B.dtype != torch.float32 or A.dim() != 2 or B.dim() != 2 or B.shape[1] != A.shape[0]:
+        raise ValueError(f"A [r, K] and B [N, r] must be fp32, got {A.dtype} {tuple(A.shape)} and {B.dtype} {tuple(B.shape)}")
+    if tuple(W.shape) != (B.shape[0], A.shape[1]) or x.shape[-1] != A.shape[1]:
+        raise ValueError(f"W must be [N, K] = [{B.shape[0]}, {A.shape[1]}] and x [..., K], got {tuple(W.shape)} and {tuple(x.shape)}")
+    lora_dropout_limits(A.shape[1], A.shape[0], p)
+    _u64(seed), _u64(stream)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, A, B)):
+        return _LoraDropoutLinearFn.apply(x, W, A, B, float(scale), float(p), int(seed), int(stream))
+    return _lora_dropout_forward(x, W.to(x.dtype), A, B, scale, p, seed, stream)[0]
 
 
 # ---- the optimizer step (include/pcad_bwd.h pcad_optim_plan / pcad_adamw_step / pcad_zero_grads; DESIGN.md §4o) and the gathering of

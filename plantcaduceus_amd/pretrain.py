@@ -480,6 +480,10 @@ class Trainer:
         out.loss.backward()
         return out.loss.detach()
 
+    def before_micro_step(self, j: int, n: int):
+        """called before micro-batch j of the step's n (the index it has in the one-process run); nothing to do here - a trainer whose
+        model draws per-step randomness from a counter sets the counter (lora_predict.FinetuneTrainer)"""
+
     def train_step(self):
         """optimizer step number self.step (0-based): this rank's share of its micro-batches, the fused step, zero_grad; nothing is read
         back.  With a reducer the rank's sum of loss x scale travels in the reducer's loss slot and comes back as the global loss; a rank
@@ -490,7 +494,8 @@ class Trainer:
         self.opt.grad_scale = scale
         reducer = getattr(self.opt, "reducer", None)
         loss = None
-        for ids, labels, weights in ddp.share(batches, self.rank, self.world):
+        for j, (ids, labels, weights) in ddp.share(list(enumerate(batches)), self.rank, self.world):
+            self.before_micro_step(j, len(batches))
             l = self.micro_step(ids, labels, weights).float() * scale
             loss = l if loss is None else loss + l
         if reducer is not None:

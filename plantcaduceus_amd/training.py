@@ -210,14 +210,18 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
     B: 0); `score.weight` fp32 [num_labels, d_model], initialised as nn.Linear, handed to the kernel rounded to the model dtype with a
     straight-through gradient.  The weights the factors merge into are kept in fp32 whatever the model dtype, so that the merged weight
     is rounded once (adapters.merge_lora).  train_lora=False: the factors exist but do not require grad - the frozen-trunk mode, which
-    is what the reference's pinned fast path trains.  lora_dropout is 0.
+    is what the reference's pinned fast path trains.
+    lora_dropout=p > 0: in training mode with grad enabled every adapted projection runs the UNMERGED form
+    `ops.lora_dropout_linear_fn`, whose branch input is dropped out by a mask that is a pure function of (`dropout_seed`, stream, row,
+    column) with stream = dropout_step 2^16 + (layer 2 + dir) 3 + module; `forward` reads `dropout_step` once, hands it to the blocks
+    and increments it after a training forward.  Under `no_grad` or `eval()` the merged call runs, without dropout.
     gradient_checkpointing=True: each block keeps only its inputs and is run again in the backward; same bits.
     `forward(input_ids, labels=None)` -> `.loss`, `.logits`."""
 
     def __init__(self, config: CaduceusConfig, num_labels: int, problem_type: str, pooling_strategy: str = "mean",
                  dtype: torch.dtype = torch.float32, device="cuda", r: int = 8, lora_alpha: float = 32,
                  target_modules=("x_proj", "in_proj", "out_proj"), train_lora: bool = True, seed: int = 0,
-                 gradient_checkpointing: bool = False):
+                 gradient_checkpointing: bool = False, lora_dropout: float = 0.0):
         super().__init__()
         from .adapters import TARGETS
         if dtype not in _DT:
@@ -237,7 +241,13 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         self.dtype, self.r, self.lora_alpha, self.train_lora = dtype, int(r), float(lora_alpha), bool(train_lora)
         self.target_modules = tuple(sorted(target_modules))
         self.is_gradient_checkpointing = bool(gradient_checkpointing)
+        self.lora_dropout, self.dropout_seed, self.dropout_step = float(lora_dropout), 0, 0
+        ops.lora_dropout_threshold(self.lora_dropout)
         self.caduceus = _Backbone(config)
+        if self.lora_dropout > 0:                                # the masked kernels' limits hold for every adapted projection, or nothing is built
+            for mod in self.target_modules:
+                ops.lora_dropout_limits(getattr(self.caduceus.backbone.layers[0].mixer.submodule.mamba_fwd, mod).weight.shape[1], self.r,
+                                        self.lora_dropout)
         self.to(dtype=dtype)
         g = torch.Generator().manual_seed(int(seed))            # the factors' and the head's initial values
         for blk in self.caduceus.backbone.layers:
@@ -288,7 +298,7 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         from .adapters import ADAPTER_CONFIG
         os.makedirs(path, exist_ok=True)
         cfg = {"base_model_name_or_path": base_model_name_or_path, "r": self.r,
-               "lora_alpha": int(self.lora_alpha) if float(self.lora_alpha).is_integer() else self.lora_alpha, "lora_dropout": 0.0,
+               "lora_alpha": int(self.lora_alpha) if float(self.lora_alpha).is_integer() else self.lora_alpha, "lora_dropout": self.lora_dropout,
                "target_modules": list(self.target_modules), "task_type": "SEQ_CLS", "modules_to_save": ["classifier", "score"],
                "peft_type": "LORA", "bias": "none", "inference_mode": True}
         with open(os.path.join(path, ADAPTER_CONFIG), "w") as f:
@@ -320,28 +330,46 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         with torch.no_grad():
             return sequence_classification_loss(logits, labels, self.problem_type, self.num_labels)
 
-    def _linear(self, x, holder):
+    LORA_MODULES = ("in_proj", "x_proj", "out_proj")            # a module's index in the dropout stream formula
+
+    def dropout_stream(self, step: int, layer: int, reverse: bool, module: str) -> int:
+        """the mask stream of one adapted projection at one step: step 2^16 + (layer 2 + dir) 3 + module"""
+        return int(step) * 65536 + (int(layer) * 2 + int(bool(reverse))) * 3 + self.LORA_MODULES.index(module)
+
+    def _linear(self, x, holder, stream: Optional[int] = None):
         if hasattr(holder, "lora_A"):
+            if stream is not None and self.lora_dropout > 0 and self.training and torch.is_grad_enabled():
+                return ops.lora_dropout_linear_fn(x, holder.weight, holder.lora_A.weight, holder.lora_B.weight, self.lora_alpha / self.r,
+                                                  self.lora_dropout, self.dropout_seed, stream)
             return ops.lora_linear_fn(x, holder.weight, holder.lora_A.weight, holder.lora_B.weight, self.lora_alpha / self.r)
         return F.linear(x, holder.weight.to(x.dtype))
 
-    def _direction(self, hn, m, reverse: bool):
+    def _direction(self, hn, m, reverse: bool, layer: int = 0, step: Optional[int] = None):
         E, R, dt = self.config.d_inner, self.config.dt_rank, hn.dtype
-        xz = self._linear(hn, m.in_proj)                                                         # (2B, L, 2E)
+        stream = (lambda mod: None) if step is None else (lambda mod: self.dropout_stream(step, layer, reverse, mod))
+        xz = self._linear(hn, m.in_proj, stream("in_proj"))                                      # (2B, L, 2E)
         xc = ops.causal_conv1d_dir(xz[..., :E], m.conv1d.weight.reshape(E, -1), m.conv1d.bias, reverse)
-        x_dbl = self._linear(xc, m.x_proj)                                                       # (2B, L, R + 32)
+        x_dbl = self._linear(xc, m.x_proj, stream("x_proj"))                                     # (2B, L, R + 32)
         delta = F.linear(x_dbl[..., :R], m.dt_proj.weight.to(dt)).transpose(1, 2)                # (2B, E, L)
         y = ops.selective_scan_fn(xc.transpose(1, 2), delta, -torch.exp(m.A_log.float()), x_dbl[..., R:R + 16].transpose(1, 2),
                                   x_dbl[..., R + 16:].transpose(1, 2), m.D.float(), z=xz[..., E:].transpose(1, 2),
                                   delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse)
-        return self._linear(y.transpose(1, 2), m.out_proj)
+        return self._linear(y.transpose(1, 2), m.out_proj, stream("out_proj"))
 
-    def _block(self, blk, h, res):
-        """one block, (h, res) -> (h, res): the unit gradient checkpointing keeps the inputs of"""
+    def _block(self, blk, h, res, layer: int = 0, step: Optional[int] = None):
+        """one block, (h, res) -> (h, res): the unit gradient checkpointing keeps the inputs of.  layer / step: the block's index and
+        the forward's dropout step (None: no dropout) - plain arguments, so that a checkpointed block that runs again sees the same"""
         cfg = self.config
         hn, res = ops.rms_norm_fn(h, blk.norm.weight, None, res, cfg.norm_epsilon, prenorm=True, residual_in_fp32=cfg.residual_in_fp32)
         bi = blk.mixer.submodule
-        return self._direction(hn, bi.mamba_fwd, False) + self._direction(hn, bi.mamba_rev, True), res
+        return self._direction(hn, bi.mamba_fwd, False, layer, step) + self._direction(hn, bi.mamba_rev, True, layer, step), res
+
+    def _run_block(self, blk, h, res, layer: int = 0, step: Optional[int] = None):
+        if step is None:
+            return super()._run_block(blk, h, res)
+        if self.is_gradient_checkpointing and torch.is_grad_enabled():
+            return checkpoint(self._block, blk, h, res, layer, step, use_reentrant=False, preserve_rng_state=False)
+        return self._block(blk, h, res, layer, step)
 
     def forward(self, input_ids, labels=None) -> SequenceClassificationTrainingOutput:
         cfg = self.config
@@ -355,8 +383,12 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         strands = torch.cat([ids, comp[ids.flip(1)]], dim=0)                                     # [2B, L]
         h, res = F.embedding(strands, emb), None
         eps = cfg.norm_epsilon
-        for blk in self.caduceus.backbone.layers:
-            h, res = self._run_block(blk, h, res)
+        dropping = self.lora_dropout > 0 and self.training and torch.is_grad_enabled()
+        step = int(self.dropout_step) if dropping else None      # read once: every block of this forward, run again or not, sees this value
+        for i, blk in enumerate(self.caduceus.backbone.layers):
+            h, res = self._run_block(blk, h, res, i, step)
+        if dropping:
+            self.dropout_step = step + 1
         logits = ops.pooled_head_fn(h, res, self.caduceus.backbone.norm_f.weight, self.score.weight, self.pooling_strategy, eps)
         loss = sequence_classification_loss(logits, labels, self.problem_type, self.num_labels) if labels is not None else None
         return SequenceClassificationTrainingOutput(loss=loss, logits=logits)
