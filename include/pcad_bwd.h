@@ -9,7 +9,8 @@
  * pcad_stream, and the calling thread's pcad_last_error() text.  Built by the same Makefile from csrc/bwd_api.hip, csrc/conv_bwd.hip,
  * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip, csrc/optim.hip (the optimizer step that uses the gradients and their gathering
  * into one buffer for a data-parallel run), csrc/wgrad.hip (the weight gradient of a linear layer into an fp32 main gradient) and
- * csrc/lora.hip (the dropout-masked down-projection of a LoRA branch, forward and backward: the last section below).
+ * csrc/lora.hip (the dropout-masked down-projection of a LoRA branch, forward and backward) and csrc/scan_bwd_seg.hip (the selective
+ * scan's backward in segments: the last section below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
@@ -270,6 +271,44 @@ size_t pcad_lora_down_bwd_scratch_bytes(int64_t M, int K, int r);
 int pcad_lora_down_bwd(const void* x, int64_t ldx, const float* A, const float* u, void* dx, int64_t lddx, float* dA, void* scratch,
                        size_t scratch_bytes, int64_t M, int K, int r, double p, uint64_t seed, uint64_t stream_id, int dtype,
                        pcad_stream stream);
+
+/* ---- The selective scan's backward in segments: long strands at a small batch ---------------------------------
+ * pcad_selective_scan_bwd (include/pcad_train.h) gives one wave to (strand, 64 channels), and that wave walks all L steps alone; a call
+ * of few long strands leaves most of the device idle.  This entry computes the same gradients - the formulas, operands, alignment
+ * rules and refusals of pcad_selective_scan_bwd, every output overwritten - with every strand cut into segments that are walked in
+ * parallel, one wave per (strand, segment, 64 channels).  csrc/scan_bwd_seg.hip; the kernel of the walk itself is the one of
+ * libpcad_train.so (csrc/scan_bwd_kernel.hpp).
+ *
+ * Segment rule, T = 8 walk steps (the steps per stored state): steps = T ceil(ceil(L / segments) / T) steps per segment, so that
+ * segments start on the boundaries of the stored states; G = ceil(L / steps) <= segments segments exist, segment g owns the walk
+ * steps [g steps, min(L, (g + 1) steps)).  pcad_selective_scan_bwd_seg_steps returns steps (host only; 0: L < 1 or segments outside
+ * [1, 64]).
+ *
+ * Both recurrences are linear in what they carry, with the same coefficients a_s[n] = exp(d_s A[c,n]):
+ *   h_s = a_s h_{s-1} + d_s u_s B_s                       (the state, walked up)
+ *   kc_{s-1} = a_s (dy_s C_s + kc_s)                      (kc_s = a_{s+1} k_{s+1}: the adjoint handed down)
+ *   phase 1, per (strand, segment, 64 channels), all in parallel: from h = 0 up the segment -> e_g[n] and Dsum_g = sum d_s (g < G - 1);
+ *            from kc = 0 down the segment -> kappa_g[n] (g > 0);  P_g[n] = exp(A[c,n] Dsum_g)
+ *   phase 2, per (strand, channel, n), serial over the segments in a fixed order: H_0 = 0, H_{g+1} = P_g H_g + e_g ascending;
+ *            K_{G-1} = 0, K_{g-1} = P_g K_g + kappa_g descending
+ *   phase 3, the two-pass walk of pcad_selective_scan_bwd per (strand, segment, 64 channels): the states from H_g instead of zero, the
+ *            adjoint from K_g instead of zero; dA, dD and dbias partials per (strand, segment), added in index order
+ * All fp32.  The results differ from pcad_selective_scan_bwd's by fp32 rounding only (the carried values are re-associated), and a call
+ * gives the same bits every time for given segments.  With G == 1 (segments == 1, or L <= steps) the unsegmented kernel runs and the
+ * results are pcad_selective_scan_bwd's bit for bit.
+ *   segments   1 .. 64 (else PCAD_ERR_INVALID)
+ *   scratch    pcad_selective_scan_bwd_seg_scratch_bytes(S, L, E, segments) bytes (0 for a refused shape), 256-byte aligned: the sections of
+ *              pcad_selective_scan_bwd's scratch - the states at the chunk boundaries, where H_g takes the slot of segment g's first
+ *              chunk, and the partial sums, dA / dD / dbias now one row per (strand, segment) - followed by e [S, G, 16, E],
+ *              kappa [S, G, 16, E] (K_{g-1} overwrites kappa_g in phase 2) and Dsum [S, G, E]
+ * S == 0 or L == 0: OK, nothing is done. */
+int pcad_selective_scan_bwd_seg_steps(int L, int segments);
+size_t pcad_selective_scan_bwd_seg_scratch_bytes(int S, int L, int E, int segments);
+int pcad_selective_scan_bwd_seg(const void* u, const void* delta, const void* z, int64_t ldz, const float* bc,
+                                const float* A, const float* Dskip, const float* delta_bias, const void* dout,
+                                void* du, void* ddelta, void* dz, float* dbc, float* dA, float* dD, float* ddelta_bias,
+                                void* scratch, size_t scratch_bytes, int S, int L, int E, int reverse, int dtype, int segments,
+                                pcad_stream stream);
 
 #ifdef __cplusplus
 }

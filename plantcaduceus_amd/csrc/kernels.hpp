@@ -364,6 +364,14 @@ struct ScanBwdLaunch {
 size_t scan_bwd_bytes(int S, int L, int E);
 hipError_t launch_scan_bwd(const ScanBwdLaunch& a, hipStream_t s);
 
+// scan_bwd_seg.hip (libpcad_bwd.so, pcad_bwd.h pcad_selective_scan_bwd_seg): the same operator with every strand cut into
+// up to `segments` segments of scan_bwd_seg_steps(L, segments) walk steps (a multiple of SCAN_BWD_CHUNK; 0: L < 1 or segments outside
+// [1, SCAN_BWD_MAX_SEGMENTS]), one wave per (strand, segment, 64 channels).  scratch: scan_bwd_seg_bytes(S, L, E, segments) bytes.
+constexpr int SCAN_BWD_MAX_SEGMENTS = 64;
+int scan_bwd_seg_steps(int L, int segments);
+size_t scan_bwd_seg_bytes(int S, int L, int E, int segments);
+hipError_t launch_scan_bwd_seg(const ScanBwdLaunch& a, int segments, hipStream_t s);
+
 // conv_bwd.hip, norm_bwd.hip (libpcad_bwd.so, include/pcad_bwd.h) --------------------
 // Both backward kernels keep their parameter-gradient partials in registers, store them once per unit of work to the caller's
 // scratch as rows of `n` floats, and launch_sum_partials adds the P rows into out[n]: the rows of each of 32 slices of P in index order, the

@@ -166,6 +166,11 @@ BWD_SIGNATURES = {
     "pcad_lora_down_bwd_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "pcad_lora_down_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
+    # the selective scan's backward in segments (plantcaduceus_amd.ops.selective_scan_bwd(segments > 1))
+    "pcad_selective_scan_bwd_seg_steps": (C.c_int, [C.c_int, C.c_int]),
+    "pcad_selective_scan_bwd_seg_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pcad_selective_scan_bwd_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 13 + [C.c_size_t] +
+                                    [C.c_int] * 6 + [C.c_void_p]),
 }
 BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
 

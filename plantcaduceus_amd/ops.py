@@ -446,17 +446,65 @@ def _acc_mode(accumulate_into, gate_sum) -> int:
 
 
 SCAN_BWD_CHUNK = 8       # csrc/kernels.hpp SCAN_BWD_CHUNK: walk steps between two states the backward stores (and re-runs at once)
+SCAN_BWD_MAX_SEGMENTS = 64      # csrc/kernels.hpp SCAN_BWD_MAX_SEGMENTS
+# the shortest segment the "auto" policy cuts a strand into: a multiple of SCAN_BWD_CHUNK, the shortest length at which doubling the
+# segments was not slower for shapes below the slot count (profiles/scan_bwd_seg_timing.txt)
+SCAN_BWD_SEG_MIN_STEPS = 128
 
 
-def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False, poison=False):
+def scan_bwd_seg_steps(L: int, segments: int) -> int:
+    """include/pcad_bwd.h pcad_selective_scan_bwd_seg_steps restated on the host: walk steps per segment, 0 = refused"""
+    if L < 1 or not 1 <= segments <= SCAN_BWD_MAX_SEGMENTS:
+        return 0
+    T = SCAN_BWD_CHUNK
+    return T * (-(-(-(-L // segments)) // T))
+
+
+def scan_bwd_auto_segments(S: int, L: int, E: int, wave_slots: Optional[int] = None) -> int:
+    """The `segments="auto"` policy of selective_scan_bwd, a pure function of the shape: the smallest power of two G <= 64 with
+    S * (E / 64) * G >= wave_slots (one wave walks 64 channels of one segment), halved while a segment would be shorter than
+    SCAN_BWD_SEG_MIN_STEPS.  wave_slots: the waves the device keeps busy at once, by default 8 x its compute units."""
+    if wave_slots is None:
+        wave_slots = 8 * torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    waves = max(1, S * (E // 64))
+    G = 1
+    while G < SCAN_BWD_MAX_SEGMENTS and waves * G < wave_slots:
+        G *= 2
+    while G > 1 and scan_bwd_seg_steps(L, G) < SCAN_BWD_SEG_MIN_STEPS:
+        G //= 2
+    return G
+
+
+def _check_segments(segments):
+    """`segments` as a caller gives it -> "auto" or an int in [1, 64]; anything else raises ValueError"""
+    if isinstance(segments, str):
+        if segments == "auto":
+            return segments
+    elif 1 <= int(segments) <= SCAN_BWD_MAX_SEGMENTS:
+        return int(segments)
+    raise ValueError(f'segments must be an int in [1, {SCAN_BWD_MAX_SEGMENTS}] or "auto", got {segments!r}')
+
+
+def _resolve_segments(segments, S: int, L: int, E: int) -> int:
+    G = _check_segments(segments)
+    return scan_bwd_auto_segments(S, L, E) if G == "auto" else G
+
+
+def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False, poison=False, segments=1, seg_entry=False):
     """pcad_selective_scan_bwd on selective_scan_fn's operands (upstream layouts; D, z, delta_bias may be None) and dout (B, E, L).
     -> namespace(du, ddelta, dz (B, E, L) in u's dtype (dz None without z); dB, dC fp32 (B, 16, L); dA fp32 (E, 16); dD, ddelta_bias fp32
     (E); guards_ok).  poison (tests): the scratch starts as 0xFF bytes and every output as NaN inside a larger buffer with one row of
-    sentinels before and after it; guards_ok tells whether all sentinels are intact afterwards."""
+    sentinels before and after it; guards_ok tells whether all sentinels are intact afterwards.
+    segments: 1 is that entry (libpcad_train.so); 2..64 is pcad_selective_scan_bwd_seg (include/pcad_bwd.h, libpcad_bwd.so; DESIGN.md
+    §4v), every strand cut into that many segments walked in parallel; "auto" resolves through scan_bwd_auto_segments.
+    seg_entry (tests): the segmented entry even with segments == 1."""
     _require_gpu(u, "u")
-    lib = load_train_library()
     Bsz, E, L = u.shape
     dt, dev = u.dtype, u.device
+    with torch.cuda.device(dev):
+        G = _resolve_segments(segments, Bsz, L, E)
+    seg = (G,) if G > 1 or seg_entry else ()
+    lib, name = (load_bwd_library(), "pcad_selective_scan_bwd_seg") if seg else (load_train_library(), "pcad_selective_scan_bwd")
     u_tm, z_tm, bc, A32, Dv, db = _scan_common(u, B, C, A, D, z, delta_bias)
     d_tm = delta.to(dt).transpose(1, 2).contiguous()
     g_tm = dout.to(dt).transpose(1, 2).contiguous()
@@ -466,14 +514,14 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False,
     du, dd, dz, dbc, dA, dD, dbias = [o[0] for o in outs]
     if z_tm is None:
         dz = None
-    nb = lib.pcad_selective_scan_bwd_scratch_bytes(Bsz, L, E)
+    nb = getattr(lib, name + "_scratch_bytes")(Bsz, L, E, *seg)
     scratch, scratch_ptr = _scratch(nb, dev, poison)
     with torch.cuda.device(dev):
-        _check(lib.pcad_selective_scan_bwd(u_tm.data_ptr(), d_tm.data_ptr(), _ptr(z_tm), E,
-                                           bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), g_tm.data_ptr(),
-                                           du.data_ptr(), dd.data_ptr(), _ptr(dz), dbc.data_ptr(),
-                                           dA.data_ptr(), dD.data_ptr(), dbias.data_ptr(), scratch_ptr, nb, Bsz, L, E,
-                                           int(bool(reverse)), _dt(u_tm), _stream_ptr()), "pcad_selective_scan_bwd")
+        _check(getattr(lib, name)(u_tm.data_ptr(), d_tm.data_ptr(), _ptr(z_tm), E,
+                                  bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(), db.data_ptr(), g_tm.data_ptr(),
+                                  du.data_ptr(), dd.data_ptr(), _ptr(dz), dbc.data_ptr(),
+                                  dA.data_ptr(), dD.data_ptr(), dbias.data_ptr(), scratch_ptr, nb, Bsz, L, E,
+                                  int(bool(reverse)), _dt(u_tm), *seg, _stream_ptr()), name)
     return SimpleNamespace(du=du.transpose(1, 2), ddelta=dd.transpose(1, 2), dz=dz.transpose(1, 2) if dz is not None else None,
                            dB=dbc[..., :16].transpose(1, 2), dC=dbc[..., 16:].transpose(1, 2), dA=dA, dD=dD, ddelta_bias=dbias,
                            guards_ok=_guards_intact(outs))
@@ -583,20 +631,22 @@ class _RmsNormFn(torch.autograd.Function):
 
 
 class _SelectiveScanFn(torch.autograd.Function):
-    """selective_scan_fn with a backward: the forward is the plain call, the backward pcad_selective_scan_bwd (include/pcad_train.h, libpcad_train.so).
-    Only the inputs are saved; the kernel recomputes the states."""
+    """selective_scan_fn with a backward: the forward is the plain call, the backward pcad_selective_scan_bwd (include/pcad_train.h, libpcad_train.so)
+    or, with segments > 1, pcad_selective_scan_bwd_seg (include/pcad_bwd.h, libpcad_bwd.so).  Only the inputs are saved; the kernel
+    recomputes the states."""
 
     @staticmethod
-    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, reverse):
+    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, reverse, segments=1):
         ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias)
         ctx.reverse = bool(reverse)
+        ctx.segments = segments
         return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, None, False)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
         u, delta, A, B, C, D, z, delta_bias = ctx.saved_tensors
-        g = selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, ctx.reverse)
+        g = selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, ctx.reverse, segments=ctx.segments)
         need = ctx.needs_input_grad
         return (g.du if need[0] else None,
                 g.ddelta.to(delta.dtype) if need[1] else None,
@@ -606,18 +656,21 @@ class _SelectiveScanFn(torch.autograd.Function):
                 g.dD.to(D.dtype) if D is not None and need[5] else None,
                 g.dz.to(z.dtype) if z is not None and need[6] else None,
                 g.ddelta_bias.to(delta_bias.dtype) if delta_bias is not None and need[7] else None,
-                None)
+                None, None)
 
 
 def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
-                      return_last_state=False, reverse=False, accumulate_into=None, gate_sum=False):
+                      return_last_state=False, reverse=False, accumulate_into=None, gate_sum=False, segments=1):
     """u, delta, z: (B, E, L); A: (E, 16); B, C: (B, 16, L); D, delta_bias: (E).  Returns (B, E, L).
     accumulate_into: add this call's gated output to an earlier one (bi-directional "add"); with gate_sum=True the
     earlier output is taken as UNGATED (its call had z=None) and SiLU(z) is applied once to the sum (the engine's form).
     When any of u, delta, A, B, C, D, z, delta_bias requires grad the call is differentiable (pcad_selective_scan_bwd; either
     direction): each gradient comes back in its input's shape and dtype.  accumulate_into / gate_sum are inference forms and are
-    refused then - the bidirectional sum is two calls added in torch."""
+    refused then - the bidirectional sum is two calls added in torch.
+    segments (1, 2..64 or "auto"; selective_scan_bwd): how many segments the BACKWARD cuts every strand into; the forward is the same
+    call, and the same bits, whatever it is."""
     _require_gpu(u, "u")
+    segments = _check_segments(segments)
     if not delta_softplus:
         raise NotImplementedError("the Caduceus path always uses delta_softplus=True")
     if return_last_state:
@@ -626,7 +679,7 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
         if accumulate_into is not None or gate_sum:
             raise NotImplementedError("accumulate_into / gate_sum are inference forms: with an input that requires grad, add the "
                                       "two directions' outputs in torch")
-        return _SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, reverse)
+        return _SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, reverse, segments)
     return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum)
 
 
@@ -679,7 +732,7 @@ def _scan_dtproj(u_tm, dt_low, R, dt_proj_weight, z_tm, bc, A32, Dv, db, y, Bsz,
 
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                    A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True,
-                   reverse=False):
+                   reverse=False, scan_bwd_segments=1):
     """`mamba_ssm.ops.selective_scan_interface.mamba_inner_fn` (mamba-ssm 2.2.2, reference env/requirements.txt:10) - the ONE call
     `Mamba.forward`'s fast path makes after in_proj - under its own signature, on the engine's kernels:
 
@@ -702,7 +755,8 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
     torch autograd: causal_conv1d_dir (pcad_causal_conv1d_silu_bwd), F.linear for x_proj, dt_proj and out_proj (differentiated by stock
     PyTorch-ROCm), selective_scan_fn (pcad_selective_scan_bwd).  That path stores xc, x_dbl, delta and y in the model dtype - upstream's
     own rounding points - so its forward value agrees with the fused inference path within test_mamba_inner_fn's bars (3e-5 fp32,
-    2^-7 bf16 against the oracle), not bit for bit.  With nothing requiring grad the function is unchanged."""
+    2^-7 bf16 against the oracle), not bit for bit.  With nothing requiring grad the function is unchanged.
+    scan_bwd_segments goes to selective_scan_fn's `segments` on that path (the scan's backward only; no forward bit changes)."""
     _require_gpu(xz, "xz")
     if B is not None or C is not None:
         raise NotImplementedError("constant B / C are not on the Caduceus path (Mamba.forward passes None: input-dependent B, C)")
@@ -730,7 +784,7 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
         x_dbl = linear_fn(xc, x_proj_weight)                                                     # (B, L, R + 32)
         delta = linear_fn(x_dbl[..., :R], delta_proj_weight).transpose(1, 2)                     # (B, E, L)
         y = selective_scan_fn(xc.transpose(1, 2), delta, A, x_dbl[..., R:R + 16].transpose(1, 2), x_dbl[..., R + 16:].transpose(1, 2), D,
-                              z=xz[:, E:], delta_bias=delta_bias, delta_softplus=True, reverse=reverse)
+                              z=xz[:, E:], delta_bias=delta_bias, delta_softplus=True, reverse=reverse, segments=scan_bwd_segments)
         return linear_fn(y.transpose(1, 2), out_proj_weight)
     x_tm = xz[:, :E].transpose(1, 2).contiguous()                    # the engine is token-major (test plumbing: it never transposes)
     z_tm = xz[:, E:].transpose(1, 2).contiguous()

@@ -10,7 +10,7 @@ of a node under `torchrun` (below).
         --num_train_epochs 3 | --max_steps N  --lr_scheduler_type linear|cosine|constant|constant_with_warmup \\
         --warmup_steps K | --warmup_ratio R  --mlm_probability 0.15 --soft_masked_loss_weights_train 1.0 \\
         --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16 \\
-        [--gradient_checkpointing] [--fp32_grad_accumulation] [--ddp_backend nccl|gloo] \\
+        [--gradient_checkpointing] [--fp32_grad_accumulation] [--scan_bwd_segments N|auto] [--ddp_backend nccl|gloo] \\
         [--eval_strategy no|steps|epoch --eval_steps N --per_device_eval_batch_size 8 --max_eval_samples M] \\
         [--save_strategy steps|epoch|no --save_total_limit K --load_best_model_at_end --metric_for_best_model loss]
     torchrun --nproc-per-node W -m plantcaduceus_amd.pretrain ... (the same flags)
@@ -42,6 +42,9 @@ parameters.  `--gradient_checkpointing` (`TrainingArguments`' name and default) 
 the backward: the same bits for about an eighth of the stored activations.  `--fp32_grad_accumulation` (bf16 only) brings
 the gradients back to the reference's fp32: one fp32 buffer holds them, the projections' weight gradients are added to it unrounded by
 `pcad_linear_wgrad`, and micro-batches - and ranks - are summed in fp32.  Checkpoints, resume and logs are unchanged.
+`--scan_bwd_segments N|auto` (or the environment variable PCAD_TRAIN_SCAN_SEGMENTS, which `lora_predict train` reads too) cuts every
+strand of the selective scan's backward into segments walked in parallel - for long windows at a small batch, where one wave per
+(strand, 64 channels) leaves most of the device idle.  Off by default; the forward's bits do not depend on it.
 
 Under `torchrun` with world size W an optimizer step consumes the `--gradient_accumulation_steps` x W micro-batches that
 one process with that accumulation would consume, in the same window order and with the same masks: every rank draws all of them (the
@@ -87,6 +90,7 @@ import torch
 logger = logging.getLogger(__name__)
 
 SCHEDULES = ("linear", "cosine", "constant", "constant_with_warmup")
+SCAN_SEGMENTS_ENV = "PCAD_TRAIN_SCAN_SEGMENTS"
 
 
 def lr_lambda(kind: str, step: int, warmup: int, total: int) -> float:
@@ -398,12 +402,30 @@ def build_parser():
     p.add_argument("--fp32_grad_accumulation", action="store_true",
                    help="with --dtype bfloat16: keep the gradients in one fp32 buffer; the projections' weight gradients are added to it "
                         "unrounded by the weight-gradient MFMA kernel, so micro-batches are summed in fp32 (DESIGN.md §4s)")
+    p.add_argument("--scan_bwd_segments", default=None,
+                   help="segments per strand of the selective scan's backward: 1 (off), 2..64 or auto (DESIGN.md §4v); the "
+                        f"environment's {SCAN_SEGMENTS_ENV} when absent")
     p.add_argument("--ddp_backend", default=None, choices=("nccl", "gloo"),
                    help="under torchrun: nccl (RCCL, one rank per device; the default) or gloo (ranks may share a device; one host "
                         "synchronisation per step); the environment's PCAD_DDP_BACKEND when absent (DESIGN.md §4r)")
     p.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
     p.add_argument("--device", default="cuda:0")
     return p
+
+
+def scan_segments_from_env(env=None):
+    """The segments of the selective scan's backward from the environment variable PCAD_TRAIN_SCAN_SEGMENTS (`env`: a
+    mapping, os.environ when None; a bare value is taken too): unset, empty or `1` -> 1 (off); `2`..`64` -> that many; `auto` -> "auto"
+    (ops.scan_bwd_auto_segments per call).  Anything else exits naming the variable."""
+    val = env if isinstance(env, str) else (os.environ if env is None else env).get(SCAN_SEGMENTS_ENV, "")
+    val = str(val).strip().lower()
+    if not val:
+        return 1
+    if val == "auto":
+        return "auto"
+    if val.isdigit() and 1 <= int(val) <= 64:
+        return int(val)
+    raise SystemExit(f"{SCAN_SEGMENTS_ENV} must be 1 (off), 2..64 or auto, got {val!r}")
 
 
 def load_tokenizer(a):
@@ -425,14 +447,18 @@ def build_model(a, dtype: torch.dtype, source: Optional[str] = None):
     from .training import TrainableCaduceusForMaskedLM
     path = source or a.model_name_or_path
     recompute = bool(getattr(a, "gradient_checkpointing", False))
+    flag = getattr(a, "scan_bwd_segments", None)
+    segments = scan_segments_from_env(os.environ if flag is None else str(flag))
+    logger.info("Segments of the scan's backward (--scan_bwd_segments / %s): %s", SCAN_SEGMENTS_ENV, "off" if segments == 1 else segments)
     if path:
-        return TrainableCaduceusForMaskedLM.from_pretrained(path, dtype=dtype, device=a.device, gradient_checkpointing=recompute)
+        return TrainableCaduceusForMaskedLM.from_pretrained(path, dtype=dtype, device=a.device, gradient_checkpointing=recompute,
+                                                            scan_bwd_segments=segments)
     if not a.config_name:
         raise SystemExit("pass --model_name_or_path or --config_name")
     cfg_path = os.path.join(a.config_name, "config.json") if os.path.isdir(a.config_name) else a.config_name
     with open(cfg_path) as f:
         cfg = config_from_dict(json.load(f))
-    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device, gradient_checkpointing=recompute)
+    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device, gradient_checkpointing=recompute, scan_bwd_segments=segments)
     model.load_state_dict(synthetic_state_dict(cfg, seed=a.seed, stress=False))
     return model
 

@@ -98,12 +98,21 @@ class _Recompute:
             return checkpoint(self._block, blk, h, res, use_reentrant=False, preserve_rng_state=False)
         return self._block(blk, h, res)
 
+    scan_bwd_segments = 1
+
+    def _set_scan_bwd_segments(self, segments):
+        """scan_bwd_segments (1, 2..64 or "auto"): how many segments every scan's BACKWARD cuts a strand into.  An
+        attribute of the model that every scan call reads, so a block that gradient checkpointing runs again uses the same value."""
+        self.scan_bwd_segments = ops._check_segments(segments)
+
 
 class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
-    """`TrainableCaduceusForMaskedLM(config, dtype=torch.float32, device="cuda", gradient_checkpointing=False)`: parameters under the
-    reference's names with requires_grad=True; `forward(input_ids, labels, loss_weights=None)` -> `.loss`, `.sums` (and `.token_nll` with return_token_nll=True)."""
+    """`TrainableCaduceusForMaskedLM(config, dtype=torch.float32, device="cuda", gradient_checkpointing=False, scan_bwd_segments=1)`: parameters under the
+    reference's names with requires_grad=True; `forward(input_ids, labels, loss_weights=None)` -> `.loss`, `.sums` (and `.token_nll` with return_token_nll=True).
+    scan_bwd_segments (1, 2..64 or "auto"): the segmented backward of every selective scan; the forward's bits do not depend on it."""
 
-    def __init__(self, config: CaduceusConfig, dtype: torch.dtype = torch.float32, device="cuda", gradient_checkpointing: bool = False):
+    def __init__(self, config: CaduceusConfig, dtype: torch.dtype = torch.float32, device="cuda", gradient_checkpointing: bool = False,
+                 scan_bwd_segments=1):
         super().__init__()
         if dtype not in _DT:
             raise ValueError(f"unsupported dtype {dtype}: the kernels compute in bf16 or fp32")
@@ -114,6 +123,7 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
             raise NotImplementedError(f"padded vocabulary of {config.padded_vocab_size} rows: the loss head evaluates 8")
         self.config = config
         self.is_gradient_checkpointing = bool(gradient_checkpointing)
+        self._set_scan_bwd_segments(scan_bwd_segments)
         self.caduceus = _Backbone(config)
         self.lm_head = _LMHead(config)
         self.tie_weights()
@@ -127,7 +137,7 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, config=None, torch_dtype=None, dtype=None, device="cuda",
-                        gradient_checkpointing: bool = False, **kwargs):
+                        gradient_checkpointing: bool = False, scan_bwd_segments=1, **kwargs):
         """A snapshot directory or hub id, read by the loader of the inference classes (config.json + safetensors / bin with the
         reference's key names; tied keys restored)."""
         hub_kw = {k: kwargs[k] for k in ("revision", "cache_dir", "local_files_only", "token") if k in kwargs}
@@ -138,7 +148,8 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
         want = dtype if dtype is not None else torch_dtype
         if isinstance(want, str):
             want = getattr(torch, want) if want != "auto" else None
-        model = cls(config, dtype=want or torch.float32, device=device, gradient_checkpointing=gradient_checkpointing)
+        model = cls(config, dtype=want or torch.float32, device=device, gradient_checkpointing=gradient_checkpointing,
+                    scan_bwd_segments=scan_bwd_segments)
         model.load_state_dict(load_state_dict(path))
         return model
 
@@ -173,11 +184,10 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
         xz = ops.linear_fn(hn, bi.mamba_fwd.in_proj.weight).transpose(1, 2)      # (2B, 2E, L); in_proj is tied
         return self._inner(xz, bi.mamba_fwd, False) + self._inner(xz, bi.mamba_rev, True), res
 
-    @staticmethod
-    def _inner(xz, m, reverse: bool):
+    def _inner(self, xz, m, reverse: bool):
         return ops.mamba_inner_fn(xz, m.conv1d.weight, m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.out_proj.weight, None,
                                   -torch.exp(m.A_log.float()), None, None, D=m.D.float(), delta_bias=m.dt_proj.bias.float(),
-                                  delta_softplus=True, reverse=reverse)
+                                  delta_softplus=True, reverse=reverse, scan_bwd_segments=self.scan_bwd_segments)
 
 
 # ---- fine-tuning: frozen trunk + LoRA factors + score -----------------------------------------------------------------
@@ -216,12 +226,13 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
     column) with stream = dropout_step 2^16 + (layer 2 + dir) 3 + module; `forward` reads `dropout_step` once, hands it to the blocks
     and increments it after a training forward.  Under `no_grad` or `eval()` the merged call runs, without dropout.
     gradient_checkpointing=True: each block keeps only its inputs and is run again in the backward; same bits.
+    scan_bwd_segments (1, 2..64 or "auto"): the segmented backward of every selective scan; no forward bit depends on it.
     `forward(input_ids, labels=None)` -> `.loss`, `.logits`."""
 
     def __init__(self, config: CaduceusConfig, num_labels: int, problem_type: str, pooling_strategy: str = "mean",
                  dtype: torch.dtype = torch.float32, device="cuda", r: int = 8, lora_alpha: float = 32,
                  target_modules=("x_proj", "in_proj", "out_proj"), train_lora: bool = True, seed: int = 0,
-                 gradient_checkpointing: bool = False, lora_dropout: float = 0.0):
+                 gradient_checkpointing: bool = False, lora_dropout: float = 0.0, scan_bwd_segments=1):
         super().__init__()
         from .adapters import TARGETS
         if dtype not in _DT:
@@ -241,6 +252,7 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         self.dtype, self.r, self.lora_alpha, self.train_lora = dtype, int(r), float(lora_alpha), bool(train_lora)
         self.target_modules = tuple(sorted(target_modules))
         self.is_gradient_checkpointing = bool(gradient_checkpointing)
+        self._set_scan_bwd_segments(scan_bwd_segments)
         self.lora_dropout, self.dropout_seed, self.dropout_step = float(lora_dropout), 0, 0
         ops.lora_dropout_threshold(self.lora_dropout)
         self.caduceus = _Backbone(config)
@@ -353,7 +365,7 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         delta = F.linear(x_dbl[..., :R], m.dt_proj.weight.to(dt)).transpose(1, 2)                # (2B, E, L)
         y = ops.selective_scan_fn(xc.transpose(1, 2), delta, -torch.exp(m.A_log.float()), x_dbl[..., R:R + 16].transpose(1, 2),
                                   x_dbl[..., R + 16:].transpose(1, 2), m.D.float(), z=xz[..., E:].transpose(1, 2),
-                                  delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse)
+                                  delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse, segments=self.scan_bwd_segments)
         return self._linear(y.transpose(1, 2), m.out_proj, stream("out_proj"))
 
     def _block(self, blk, h, res, layer: int = 0, step: Optional[int] = None):
