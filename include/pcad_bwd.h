@@ -10,7 +10,7 @@
  * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip, csrc/optim.hip (the optimizer step that uses the gradients and their gathering
  * into one buffer for a data-parallel run), csrc/wgrad.hip (the weight gradient of a linear layer into an fp32 main gradient) and
  * csrc/lora.hip (the dropout-masked down-projection of a LoRA branch, forward and backward) and csrc/scan_bwd_seg.hip (the selective
- * scan's backward in segments: the last section below).
+ * scan's backward in segments) and csrc/scan_fwd_seg.hip (the scan's training forward in segments: the last two sections below).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
@@ -307,6 +307,30 @@ size_t pcad_selective_scan_bwd_seg_scratch_bytes(int S, int L, int E, int segmen
 int pcad_selective_scan_bwd_seg(const void* u, const void* delta, const void* z, int64_t ldz, const float* bc,
                                 const float* A, const float* Dskip, const float* delta_bias, const void* dout,
                                 void* du, void* ddelta, void* dz, float* dbc, float* dA, float* dD, float* ddelta_bias,
+                                void* scratch, size_t scratch_bytes, int S, int L, int E, int reverse, int dtype, int segments,
+                                pcad_stream stream);
+
+/* ---- The selective scan's training forward in segments ----------------------------------------------------------
+ * The forward of pcad_selective_scan (include/pcad.h) on plain rows with an explicit delta - the call the training path makes -, with
+ * every strand cut by the rule above (steps = pcad_selective_scan_bwd_seg_steps(L, segments), G = ceil(L / steps) segments: the forward's
+ * cuts are the backward's) and one wave per (strand, segment, 64 channels).  csrc/scan_fwd_seg.hip.  Per strand and channel c, walk
+ * step s visiting row t = s (reverse 0) or L - 1 - s (reverse 1):
+ *   d_t = softplus(delta_t + delta_bias_c)     h_s[n] = exp(d_t A[c,n]) h_{s-1}[n] + d_t u_t B_t[n]     y_t = sum_n h_s[n] C_t[n] + Dskip_c u_t
+ *   out_t = y_t silu(z_t)  (z given)  or  y_t
+ *   phase 1, per (strand, segment g < G - 1, 64 channels): from h = 0 up the segment -> e_g[n] and Dsum_g = sum d_s
+ *   phase 2, per (strand, channel, n), serial over g ascending: H_0 = 0, H_{g+1} = exp2(A[c,n] log2(e) Dsum_g) H_g + e_g
+ *   phase 3, per (strand, segment, 64 channels): the walk from H_g; out_t rounded once to dtype and stored once
+ * u and delta are read in dtype, everything in between is fp32.  No floating-point atomics: a call gives the same bits every time for
+ * given segments.  The result differs from pcad_selective_scan's by fp32 rounding - also with G == 1 (segments == 1, or L <= steps),
+ * which runs phase 3 alone from a zero state: a different kernel from pcad_selective_scan's.
+ *   u, delta, y  [S, L, E] dtype;  z [S, L, ldz >= E] dtype or NULL (ungated);  bc fp32 [S L, 32] = B_t | C_t, 16-byte aligned
+ *   A fp32 [E, 16] (raw, = -exp(A_log));  Dskip, delta_bias fp32 [E];  E % 64 == 0;  segments 1 .. 64
+ *   scratch    pcad_selective_scan_fwd_seg_scratch_bytes(S, L, E, segments) bytes (0 for a refused shape), 256-byte aligned, two sections
+ *              each a multiple of 256 bytes: e / H [S, G, 16, E] (H_g overwrites e_g in phase 2) and Dsum [S, G, E]
+ * PCAD_ERR_INVALID also when S G E / 64 waves or S 16 E / 256 blocks do not fit a 32-bit grid.  S == 0 or L == 0: OK, nothing is done. */
+size_t pcad_selective_scan_fwd_seg_scratch_bytes(int S, int L, int E, int segments);
+int pcad_selective_scan_fwd_seg(const void* u, const void* delta, const void* z, int64_t ldz, const float* bc,
+                                const float* A, const float* Dskip, const float* delta_bias, void* y,
                                 void* scratch, size_t scratch_bytes, int S, int L, int E, int reverse, int dtype, int segments,
                                 pcad_stream stream);
 

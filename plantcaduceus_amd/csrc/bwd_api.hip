@@ -466,4 +466,36 @@ int pcad_selective_scan_bwd_seg(const void* u, const void* delta, const void* z,
     return PCAD_OK;
 }
 
+// ---- the segmented training forward of the selective scan (csrc/scan_fwd_seg.hip) ----
+size_t pcad_selective_scan_fwd_seg_scratch_bytes(int S, int L, int E, int segments) {
+    if (S <= 0 || L <= 0 || E <= 0 || E % 64 || segments < 1 || segments > SCAN_BWD_MAX_SEGMENTS) return 0;
+    return scan_fwd_seg_bytes(S, L, E, segments);
+}
+
+int pcad_selective_scan_fwd_seg(const void* u, const void* delta, const void* z, int64_t ldz, const float* bc, const float* A,
+                                const float* Dskip, const float* delta_bias, void* y, void* scratch, size_t scratch_bytes, int S, int L,
+                                int E, int reverse, int dtype, int segments, pcad_stream stream) {
+    const char* who = "pcad_selective_scan_fwd_seg";
+    const struct { const void* p; const char* name; } req[] = {
+        {u, "u"}, {delta, "delta"}, {bc, "bc"}, {A, "A"}, {Dskip, "Dskip"}, {delta_bias, "delta_bias"}, {y, "y"}};
+    for (const auto& r : req)
+        if (!r.p) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (S < 0 || L < 0 || E <= 0 || E % 64) return fail(PCAD_ERR_INVALID, "%s: E must be a multiple of 64 (E=%d); S, L >= 0", who, E);
+    if (segments < 1 || segments > SCAN_BWD_MAX_SEGMENTS)
+        return fail(PCAD_ERR_INVALID, "%s: segments must be in [1, %d] (segments=%d)", who, SCAN_BWD_MAX_SEGMENTS, segments);
+    if (z && ldz < E) return fail(PCAD_ERR_INVALID, "%s: ldz must be >= E", who);
+    if (((uintptr_t)bc) % 16) return fail(PCAD_ERR_INVALID, "%s: bc must be 16-byte aligned", who);
+    if (S == 0 || L == 0) return PCAD_OK;
+    if (!scan_fwd_seg_grid_ok(S, L, E, segments))
+        return fail(PCAD_ERR_INVALID, "%s: S * segments * E / 64 and S * 16 * E / 256 must fit a 32-bit grid", who);
+    if (!scratch || ((uintptr_t)scratch) % 256 || scratch_bytes < scan_fwd_seg_bytes(S, L, E, segments))
+        return fail(PCAD_ERR_WORKSPACE, "%s: scratch must be 256-byte aligned and pcad_selective_scan_fwd_seg_scratch_bytes large", who);
+    hipError_t err = launch_scan_fwd_seg({.u = u, .delta = delta, .z = z, .ldz = ldz, .bc = bc, .A = A, .Dskip = Dskip, .dbias = delta_bias, .y = y,
+                                          .scratch = scratch, .S = S, .L = L, .E = E, .dt = dtype, .reverse = reverse != 0},
+                                         segments, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 }  // extern "C"

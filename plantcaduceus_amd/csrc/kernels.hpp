@@ -372,6 +372,22 @@ int scan_bwd_seg_steps(int L, int segments);
 size_t scan_bwd_seg_bytes(int S, int L, int E, int segments);
 hipError_t launch_scan_bwd_seg(const ScanBwdLaunch& a, int segments, hipStream_t s);
 
+// scan_fwd_seg.hip (libpcad_bwd.so, pcad_bwd.h pcad_selective_scan_fwd_seg): the FORWARD of launch_scan's unfused plain-layout
+// form (explicit delta, A raw) cut by the same rule, scan_bwd_seg_steps, one wave per (strand, segment, 64 channels); y [S, L, E] in dtype
+// dt is overwritten.  scratch: scan_fwd_seg_bytes(S, L, E, segments) bytes.  scan_fwd_seg_grid_ok: whether its grids fit 31 bits.
+struct ScanFwdSegLaunch {
+    const void *u, *delta;
+    const void* z = nullptr;  int64_t ldz = 0;
+    const float *bc, *A, *Dskip, *dbias;
+    void* y;
+    void* scratch;
+    int S, L, E, dt;
+    bool reverse = false;
+};
+size_t scan_fwd_seg_bytes(int S, int L, int E, int segments);
+bool scan_fwd_seg_grid_ok(int S, int L, int E, int segments);
+hipError_t launch_scan_fwd_seg(const ScanFwdSegLaunch& a, int segments, hipStream_t s);
+
 // conv_bwd.hip, norm_bwd.hip (libpcad_bwd.so, include/pcad_bwd.h) --------------------
 // Both backward kernels keep their parameter-gradient partials in registers, store them once per unit of work to the caller's
 // scratch as rows of `n` floats, and launch_sum_partials adds the P rows into out[n]: the rows of each of 32 slices of P in index order, the

@@ -171,6 +171,10 @@ BWD_SIGNATURES = {
     "pcad_selective_scan_bwd_seg_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "pcad_selective_scan_bwd_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 13 + [C.c_size_t] +
                                     [C.c_int] * 6 + [C.c_void_p]),
+    # the selective scan's training forward in segments (plantcaduceus_amd.ops.selective_scan_fwd_seg)
+    "pcad_selective_scan_fwd_seg_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pcad_selective_scan_fwd_seg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t] +
+                                    [C.c_int] * 6 + [C.c_void_p]),
 }
 BWD_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libpcad_bwd.so")
 

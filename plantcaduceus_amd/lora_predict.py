@@ -28,6 +28,7 @@ choice, logged at the start: the environment variable PCAD_TRAIN_RECOMPUTE=1 / 0
 stored bytes for a micro-batch exceed half of the device's free memory.  The command has no flag for it: the flag set is the reference's.
 Likewise PCAD_TRAIN_SCAN_SEGMENTS (`pretrain.scan_segments_from_env`: unset or 1 off, 2..64, or auto) cuts every strand of the selective
 scan's backward into segments walked in parallel - long windows at a small --train_batch_size; logged at the start.
+PCAD_TRAIN_SCAN_FWD_SEGMENTS (the same helper and values) does so for the scan's forward: a setting of its own, logged too.
 
 Under torchrun the windows are sharded over the ranks (plantcad2_eval._sharded_rows); rank 0 writes / prints.  Metrics are
 computed on the host without sklearn (the reference's compute_metrics_* :517-563 restated; pinned against sklearn / scipy in
@@ -487,6 +488,7 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
                          f"{DROPOUT_ENV}={lora_dropout} instead (DESIGN.md §4u); the flag itself takes only 0.0")
     dropout = lora_dropout_from_env(os.environ, bool(int(train_lora)))
     segments = pretrain.scan_segments_from_env(os.environ)
+    fwd_segments = pretrain.scan_segments_from_env(os.environ, pretrain.SCAN_FWD_SEGMENTS_ENV)
     if pooling not in ("mean", "first", "last"):
         raise SystemExit(f"--pooling {pooling} has no backward (max pooling's gradient needs a tie rule nothing pins): one of mean, first, last")
     if lr_scheduler_type not in pretrain.SCHEDULES:
@@ -511,11 +513,13 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     total = max_steps if max_steps > 0 else math.ceil(num_train_epochs * source.steps_per_epoch)
     model = TrainableCaduceusForSequenceClassification.from_pretrained(
         model_name, nl, problem_type, pooling_strategy=pooling, dtype=torch.bfloat16 if bf16 else torch.float32, device=device,
-        train_lora=bool(int(train_lora)), seed=seed, lora_dropout=dropout, scan_bwd_segments=segments)
+        train_lora=bool(int(train_lora)), seed=seed, lora_dropout=dropout, scan_bwd_segments=segments,
+        scan_fwd_segments=fwd_segments)
     model.dropout_seed = int(seed) % (1 << 64)
     if dropout > 0:
         logger.info("LoRA dropout (%s): %g, masks from seed %d and the micro-batch's index in the one-process run", DROPOUT_ENV, dropout, seed)
     logger.info("Segments of the scan's backward (%s): %s", pretrain.SCAN_SEGMENTS_ENV, "off" if segments == 1 else segments)
+    logger.info("Segments of the scan's forward (%s): %s", pretrain.SCAN_FWD_SEGMENTS_ENV, "off" if fwd_segments == 1 else fwd_segments)
     per_window = 2 * ids.shape[1] * stored_bytes_per_strand_position(model.config, model.dtype, lora=True)
     free_bytes = torch.cuda.mem_get_info(device)[0]
     if recompute_policy(per_window, train_batch_size, free_bytes, os.environ, model.train_lora):

@@ -475,6 +475,23 @@ def scan_bwd_auto_segments(S: int, L: int, E: int, wave_slots: Optional[int] = N
     return G
 
 
+# the fewest segments that must be needed to fill the wave slots before the "auto" policy cuts the FORWARD at all: the segmented forward
+# walks every step twice (local pass, then walk) at 1.8x the plain kernel's time per step, so 2 segments are slower than none at every
+# shape and 4 about even; shapes whose strands fill the slots with 4 or fewer lost or gained nothing (profiles/scan_fwd_seg_timing.txt,
+# S = 32)
+SCAN_FWD_SEG_MIN_FILL = 8
+
+
+def scan_fwd_auto_segments(S: int, L: int, E: int, wave_slots: Optional[int] = None) -> int:
+    """The `fwd_segments="auto"` policy, a pure function of the shape: scan_bwd_auto_segments' value, except 1 where fewer than
+    SCAN_FWD_SEG_MIN_FILL segments already fill the wave slots (S * (E / 64) * SCAN_FWD_SEG_MIN_FILL / 2 >= wave_slots)."""
+    if wave_slots is None:
+        wave_slots = 8 * torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    if max(1, S * (E // 64)) * (SCAN_FWD_SEG_MIN_FILL // 2) >= wave_slots:
+        return 1
+    return scan_bwd_auto_segments(S, L, E, wave_slots)
+
+
 def _check_segments(segments):
     """`segments` as a caller gives it -> "auto" or an int in [1, 64]; anything else raises ValueError"""
     if isinstance(segments, str):
@@ -485,9 +502,9 @@ def _check_segments(segments):
     raise ValueError(f'segments must be an int in [1, {SCAN_BWD_MAX_SEGMENTS}] or "auto", got {segments!r}')
 
 
-def _resolve_segments(segments, S: int, L: int, E: int) -> int:
+def _resolve_segments(segments, S: int, L: int, E: int, policy=scan_bwd_auto_segments) -> int:
     G = _check_segments(segments)
-    return scan_bwd_auto_segments(S, L, E) if G == "auto" else G
+    return policy(S, L, E) if G == "auto" else G
 
 
 def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False, poison=False, segments=1, seg_entry=False):
@@ -525,6 +542,31 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, reverse=False,
     return SimpleNamespace(du=du.transpose(1, 2), ddelta=dd.transpose(1, 2), dz=dz.transpose(1, 2) if dz is not None else None,
                            dB=dbc[..., :16].transpose(1, 2), dC=dbc[..., 16:].transpose(1, 2), dA=dA, dD=dD, ddelta_bias=dbias,
                            guards_ok=_guards_intact(outs))
+
+
+def selective_scan_fwd_seg(u, delta, A, B, C, D, z, delta_bias, reverse=False, segments=1, poison=False):
+    """pcad_selective_scan_fwd_seg (include/pcad_bwd.h, libpcad_bwd.so) on selective_scan_fn's operands (upstream layouts; D,
+    z, delta_bias may be None): the training forward's scan with every strand cut into `segments` segments (1..64 or "auto", resolved
+    by scan_fwd_auto_segments) walked in parallel, on the backward's cut rule.  -> namespace(out (B, E, L) in u's dtype; segments: the
+    resolved count; guards_ok).  segments == 1 runs this entry's own walk from a zero state - not pcad_selective_scan's bits, which is
+    why selective_scan_fn never routes 1 here.  poison (tests): as selective_scan_bwd."""
+    _require_gpu(u, "u")
+    Bsz, E, L = u.shape
+    dt, dev = u.dtype, u.device
+    with torch.cuda.device(dev):
+        G = _resolve_segments(segments, Bsz, L, E, scan_fwd_auto_segments)
+    lib, name = load_bwd_library(), "pcad_selective_scan_fwd_seg"
+    u_tm, z_tm, bc, A32, Dv, db = _scan_common(u, B, C, A, D, z, delta_bias)
+    d_tm = delta.to(dt).transpose(1, 2).contiguous()
+    outs = [_guarded((Bsz, L, E), dt, dev, "row", poison)]
+    y = outs[0][0]
+    nb = lib.pcad_selective_scan_fwd_seg_scratch_bytes(Bsz, L, E, G)
+    scratch, scratch_ptr = _scratch(nb, dev, poison)
+    with torch.cuda.device(dev):
+        _check(lib.pcad_selective_scan_fwd_seg(u_tm.data_ptr(), d_tm.data_ptr(), _ptr(z_tm), E, bc.data_ptr(), A32.data_ptr(), Dv.data_ptr(),
+                                               db.data_ptr(), y.data_ptr(), scratch_ptr, nb, Bsz, L, E, int(bool(reverse)), _dt(u_tm), G,
+                                               _stream_ptr()), name)
+    return SimpleNamespace(out=y.transpose(1, 2), segments=G, guards_ok=_guards_intact(outs))
 
 
 CONV_BWD_SEG = 64        # csrc/kernels.hpp CONV_BWD_SEG: walk steps one lane of the conv backward owns (one row of dw | db partials each)
@@ -631,16 +673,17 @@ class _RmsNormFn(torch.autograd.Function):
 
 
 class _SelectiveScanFn(torch.autograd.Function):
-    """selective_scan_fn with a backward: the forward is the plain call, the backward pcad_selective_scan_bwd (include/pcad_train.h, libpcad_train.so)
-    or, with segments > 1, pcad_selective_scan_bwd_seg (include/pcad_bwd.h, libpcad_bwd.so).  Only the inputs are saved; the kernel
-    recomputes the states."""
+    """selective_scan_fn with a backward: the forward is the plain call - with fwd_segments > 1 pcad_selective_scan_fwd_seg (include/pcad_bwd.h;
+    DESIGN.md §4w) -, the backward pcad_selective_scan_bwd (include/pcad_train.h, libpcad_train.so) or, with segments > 1,
+    pcad_selective_scan_bwd_seg (include/pcad_bwd.h, libpcad_bwd.so).  Only the inputs are saved; the kernel recomputes the states."""
 
     @staticmethod
-    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, reverse, segments=1):
+    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, reverse, segments=1, fwd_segments=1):
         ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias)
         ctx.reverse = bool(reverse)
         ctx.segments = segments
-        return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, None, False)
+        ctx.fwd_segments = fwd_segments
+        return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, None, False, fwd_segments)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -656,11 +699,11 @@ class _SelectiveScanFn(torch.autograd.Function):
                 g.dD.to(D.dtype) if D is not None and need[5] else None,
                 g.dz.to(z.dtype) if z is not None and need[6] else None,
                 g.ddelta_bias.to(delta_bias.dtype) if delta_bias is not None and need[7] else None,
-                None, None)
+                None, None, None)
 
 
 def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
-                      return_last_state=False, reverse=False, accumulate_into=None, gate_sum=False, segments=1):
+                      return_last_state=False, reverse=False, accumulate_into=None, gate_sum=False, segments=1, fwd_segments=1):
     """u, delta, z: (B, E, L); A: (E, 16); B, C: (B, 16, L); D, delta_bias: (E).  Returns (B, E, L).
     accumulate_into: add this call's gated output to an earlier one (bi-directional "add"); with gate_sum=True the
     earlier output is taken as UNGATED (its call had z=None) and SiLU(z) is applied once to the sum (the engine's form).
@@ -668,9 +711,13 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
     direction): each gradient comes back in its input's shape and dtype.  accumulate_into / gate_sum are inference forms and are
     refused then - the bidirectional sum is two calls added in torch.
     segments (1, 2..64 or "auto"; selective_scan_bwd): how many segments the BACKWARD cuts every strand into; the forward is the same
-    call, and the same bits, whatever it is."""
+    call, and the same bits, whatever it is.
+    fwd_segments (1, 2..64 or "auto": scan_fwd_auto_segments, the backward's policy cut back where few segments fill the device): how many segments the FORWARD cuts every strand into, with or without
+    grad.  Resolved to 1 it is today's pcad_selective_scan call, bit for bit; above 1 it is pcad_selective_scan_fwd_seg,
+    whose result differs by fp32 rounding and is bit-reproducible for a given count.  Not with accumulate_into / gate_sum."""
     _require_gpu(u, "u")
     segments = _check_segments(segments)
+    fwd_segments = _check_segments(fwd_segments)
     if not delta_softplus:
         raise NotImplementedError("the Caduceus path always uses delta_softplus=True")
     if return_last_state:
@@ -679,13 +726,20 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
         if accumulate_into is not None or gate_sum:
             raise NotImplementedError("accumulate_into / gate_sum are inference forms: with an input that requires grad, add the "
                                       "two directions' outputs in torch")
-        return _SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, reverse, segments)
-    return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum)
+        return _SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, reverse, segments, fwd_segments)
+    return _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum, fwd_segments)
 
 
-def _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum):
-    lib = load_library()
+def _selective_scan_forward(u, delta, A, B, C, D, z, delta_bias, reverse, accumulate_into, gate_sum, fwd_segments=1):
     Bsz, E, L = u.shape
+    if fwd_segments != 1:
+        if accumulate_into is not None or gate_sum:               # whatever "auto" would resolve to: the refusal does not depend on the shape
+            raise NotImplementedError("accumulate_into / gate_sum are not built for the segmented forward (fwd_segments other than 1)")
+        with torch.cuda.device(u.device):
+            G = _resolve_segments(fwd_segments, Bsz, L, E, scan_fwd_auto_segments)
+        if G > 1 and L > scan_bwd_seg_steps(L, G):                # one effective segment: today's call, and its bits
+            return selective_scan_fwd_seg(u, delta, A, B, C, D, z, delta_bias, reverse, G).out
+    lib = load_library()
     u_tm, z_tm, bc, A32, Dv, db = _scan_common(u, B, C, A, D, z, delta_bias)
     d_tm = delta.to(u.dtype).transpose(1, 2).contiguous()
     y = accumulate_into.transpose(1, 2).contiguous() if accumulate_into is not None else torch.empty_like(u_tm)
@@ -732,7 +786,7 @@ def _scan_dtproj(u_tm, dt_low, R, dt_proj_weight, z_tm, bc, A32, Dv, db, y, Bsz,
 
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                    A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True,
-                   reverse=False, scan_bwd_segments=1):
+                   reverse=False, scan_bwd_segments=1, scan_fwd_segments=1):
     """`mamba_ssm.ops.selective_scan_interface.mamba_inner_fn` (mamba-ssm 2.2.2, reference env/requirements.txt:10) - the ONE call
     `Mamba.forward`'s fast path makes after in_proj - under its own signature, on the engine's kernels:
 
@@ -756,7 +810,9 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
     PyTorch-ROCm), selective_scan_fn (pcad_selective_scan_bwd).  That path stores xc, x_dbl, delta and y in the model dtype - upstream's
     own rounding points - so its forward value agrees with the fused inference path within test_mamba_inner_fn's bars (3e-5 fp32,
     2^-7 bf16 against the oracle), not bit for bit.  With nothing requiring grad the function is unchanged.
-    scan_bwd_segments goes to selective_scan_fn's `segments` on that path (the scan's backward only; no forward bit changes)."""
+    scan_bwd_segments goes to selective_scan_fn's `segments` on that path (the scan's backward only; no forward bit changes), and
+    scan_fwd_segments to its `fwd_segments` (the scan's forward in segments; 1: no bit changes).  Both are read on the
+    grad path only."""
     _require_gpu(xz, "xz")
     if B is not None or C is not None:
         raise NotImplementedError("constant B / C are not on the Caduceus path (Mamba.forward passes None: input-dependent B, C)")
@@ -784,7 +840,8 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
         x_dbl = linear_fn(xc, x_proj_weight)                                                     # (B, L, R + 32)
         delta = linear_fn(x_dbl[..., :R], delta_proj_weight).transpose(1, 2)                     # (B, E, L)
         y = selective_scan_fn(xc.transpose(1, 2), delta, A, x_dbl[..., R:R + 16].transpose(1, 2), x_dbl[..., R + 16:].transpose(1, 2), D,
-                              z=xz[:, E:], delta_bias=delta_bias, delta_softplus=True, reverse=reverse, segments=scan_bwd_segments)
+                              z=xz[:, E:], delta_bias=delta_bias, delta_softplus=True, reverse=reverse, segments=scan_bwd_segments,
+                              fwd_segments=scan_fwd_segments)
         return linear_fn(y.transpose(1, 2), out_proj_weight)
     x_tm = xz[:, :E].transpose(1, 2).contiguous()                    # the engine is token-major (test plumbing: it never transposes)
     z_tm = xz[:, E:].transpose(1, 2).contiguous()

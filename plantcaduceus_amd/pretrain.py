@@ -10,7 +10,8 @@ of a node under `torchrun` (below).
         --num_train_epochs 3 | --max_steps N  --lr_scheduler_type linear|cosine|constant|constant_with_warmup \\
         --warmup_steps K | --warmup_ratio R  --mlm_probability 0.15 --soft_masked_loss_weights_train 1.0 \\
         --logging_steps 500 --save_steps 500 --seed 42 --resume_from_checkpoint <dir> --dtype float32|bfloat16 \\
-        [--gradient_checkpointing] [--fp32_grad_accumulation] [--scan_bwd_segments N|auto] [--ddp_backend nccl|gloo] \\
+        [--gradient_checkpointing] [--fp32_grad_accumulation] [--scan_bwd_segments N|auto] [--scan_fwd_segments N|auto] \\
+        [--ddp_backend nccl|gloo] \\
         [--eval_strategy no|steps|epoch --eval_steps N --per_device_eval_batch_size 8 --max_eval_samples M] \\
         [--save_strategy steps|epoch|no --save_total_limit K --load_best_model_at_end --metric_for_best_model loss]
     torchrun --nproc-per-node W -m plantcaduceus_amd.pretrain ... (the same flags)
@@ -45,6 +46,9 @@ the gradients back to the reference's fp32: one fp32 buffer holds them, the proj
 `--scan_bwd_segments N|auto` (or the environment variable PCAD_TRAIN_SCAN_SEGMENTS, which `lora_predict train` reads too) cuts every
 strand of the selective scan's backward into segments walked in parallel - for long windows at a small batch, where one wave per
 (strand, 64 channels) leaves most of the device idle.  Off by default; the forward's bits do not depend on it.
+`--scan_fwd_segments N|auto` (or PCAD_TRAIN_SCAN_FWD_SEGMENTS, likewise read by `lora_predict train`) does the same for the scan's training
+FORWARD: its own setting, which neither the backward's flag nor its variable turns on.  Off by default: no bit changes; on,
+the scans' outputs differ by fp32 rounding and a run is reproducible for a given value.
 
 Under `torchrun` with world size W an optimizer step consumes the `--gradient_accumulation_steps` x W micro-batches that
 one process with that accumulation would consume, in the same window order and with the same masks: every rank draws all of them (the
@@ -91,6 +95,7 @@ logger = logging.getLogger(__name__)
 
 SCHEDULES = ("linear", "cosine", "constant", "constant_with_warmup")
 SCAN_SEGMENTS_ENV = "PCAD_TRAIN_SCAN_SEGMENTS"
+SCAN_FWD_SEGMENTS_ENV = "PCAD_TRAIN_SCAN_FWD_SEGMENTS"
 
 
 def lr_lambda(kind: str, step: int, warmup: int, total: int) -> float:
@@ -405,6 +410,9 @@ def build_parser():
     p.add_argument("--scan_bwd_segments", default=None,
                    help="segments per strand of the selective scan's backward: 1 (off), 2..64 or auto (DESIGN.md §4v); the "
                         f"environment's {SCAN_SEGMENTS_ENV} when absent")
+    p.add_argument("--scan_fwd_segments", default=None,
+                   help="segments per strand of the selective scan's training forward: 1 (off), 2..64 or auto (DESIGN.md §4w); the "
+                        f"environment's {SCAN_FWD_SEGMENTS_ENV} when absent")
     p.add_argument("--ddp_backend", default=None, choices=("nccl", "gloo"),
                    help="under torchrun: nccl (RCCL, one rank per device; the default) or gloo (ranks may share a device; one host "
                         "synchronisation per step); the environment's PCAD_DDP_BACKEND when absent (DESIGN.md §4r)")
@@ -413,11 +421,12 @@ def build_parser():
     return p
 
 
-def scan_segments_from_env(env=None):
+def scan_segments_from_env(env=None, name=SCAN_SEGMENTS_ENV):
     """The segments of the selective scan's backward from the environment variable PCAD_TRAIN_SCAN_SEGMENTS (`env`: a
     mapping, os.environ when None; a bare value is taken too): unset, empty or `1` -> 1 (off); `2`..`64` -> that many; `auto` -> "auto"
-    (ops.scan_bwd_auto_segments per call).  Anything else exits naming the variable."""
-    val = env if isinstance(env, str) else (os.environ if env is None else env).get(SCAN_SEGMENTS_ENV, "")
+    (ops.scan_bwd_auto_segments per call).  Anything else exits naming the variable.  name: the variable to read instead -
+    SCAN_FWD_SEGMENTS_ENV for the forward's segments, which are a setting of their own."""
+    val = env if isinstance(env, str) else (os.environ if env is None else env).get(name, "")
     val = str(val).strip().lower()
     if not val:
         return 1
@@ -425,7 +434,7 @@ def scan_segments_from_env(env=None):
         return "auto"
     if val.isdigit() and 1 <= int(val) <= 64:
         return int(val)
-    raise SystemExit(f"{SCAN_SEGMENTS_ENV} must be 1 (off), 2..64 or auto, got {val!r}")
+    raise SystemExit(f"{name} must be 1 (off), 2..64 or auto, got {val!r}")
 
 
 def load_tokenizer(a):
@@ -450,15 +459,20 @@ def build_model(a, dtype: torch.dtype, source: Optional[str] = None):
     flag = getattr(a, "scan_bwd_segments", None)
     segments = scan_segments_from_env(os.environ if flag is None else str(flag))
     logger.info("Segments of the scan's backward (--scan_bwd_segments / %s): %s", SCAN_SEGMENTS_ENV, "off" if segments == 1 else segments)
+    fwd_flag = getattr(a, "scan_fwd_segments", None)
+    fwd_segments = scan_segments_from_env(os.environ if fwd_flag is None else str(fwd_flag), SCAN_FWD_SEGMENTS_ENV)
+    logger.info("Segments of the scan's forward (--scan_fwd_segments / %s): %s", SCAN_FWD_SEGMENTS_ENV,
+                "off" if fwd_segments == 1 else fwd_segments)
     if path:
         return TrainableCaduceusForMaskedLM.from_pretrained(path, dtype=dtype, device=a.device, gradient_checkpointing=recompute,
-                                                            scan_bwd_segments=segments)
+                                                            scan_bwd_segments=segments, scan_fwd_segments=fwd_segments)
     if not a.config_name:
         raise SystemExit("pass --model_name_or_path or --config_name")
     cfg_path = os.path.join(a.config_name, "config.json") if os.path.isdir(a.config_name) else a.config_name
     with open(cfg_path) as f:
         cfg = config_from_dict(json.load(f))
-    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device, gradient_checkpointing=recompute, scan_bwd_segments=segments)
+    model = TrainableCaduceusForMaskedLM(cfg, dtype=dtype, device=a.device, gradient_checkpointing=recompute, scan_bwd_segments=segments,
+                                         scan_fwd_segments=fwd_segments)
     model.load_state_dict(synthetic_state_dict(cfg, seed=a.seed, stress=False))
     return model
 

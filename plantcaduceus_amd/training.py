@@ -105,14 +105,23 @@ class _Recompute:
         attribute of the model that every scan call reads, so a block that gradient checkpointing runs again uses the same value."""
         self.scan_bwd_segments = ops._check_segments(segments)
 
+    scan_fwd_segments = 1
+
+    def _set_scan_fwd_segments(self, segments):
+        """scan_fwd_segments (1, 2..64 or "auto"): how many segments every scan's FORWARD cuts a strand into.  An attribute
+        as scan_bwd_segments is: a block that gradient checkpointing runs again reads the same value, so it computes the same bits."""
+        self.scan_fwd_segments = ops._check_segments(segments)
+
 
 class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
-    """`TrainableCaduceusForMaskedLM(config, dtype=torch.float32, device="cuda", gradient_checkpointing=False, scan_bwd_segments=1)`: parameters under the
+    """`TrainableCaduceusForMaskedLM(config, dtype=torch.float32, device="cuda", gradient_checkpointing=False, scan_bwd_segments=1, scan_fwd_segments=1)`: parameters under the
     reference's names with requires_grad=True; `forward(input_ids, labels, loss_weights=None)` -> `.loss`, `.sums` (and `.token_nll` with return_token_nll=True).
-    scan_bwd_segments (1, 2..64 or "auto"): the segmented backward of every selective scan; the forward's bits do not depend on it."""
+    scan_bwd_segments (1, 2..64 or "auto"): the segmented backward of every selective scan; the forward's bits do not depend on it.
+    scan_fwd_segments (1, 2..64 or "auto"): the segmented forward of every selective scan; 1 changes no bit, above 1 the scans'
+    outputs differ by fp32 rounding and are reproducible for a given value."""
 
     def __init__(self, config: CaduceusConfig, dtype: torch.dtype = torch.float32, device="cuda", gradient_checkpointing: bool = False,
-                 scan_bwd_segments=1):
+                 scan_bwd_segments=1, scan_fwd_segments=1):
         super().__init__()
         if dtype not in _DT:
             raise ValueError(f"unsupported dtype {dtype}: the kernels compute in bf16 or fp32")
@@ -124,6 +133,7 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
         self.config = config
         self.is_gradient_checkpointing = bool(gradient_checkpointing)
         self._set_scan_bwd_segments(scan_bwd_segments)
+        self._set_scan_fwd_segments(scan_fwd_segments)
         self.caduceus = _Backbone(config)
         self.lm_head = _LMHead(config)
         self.tie_weights()
@@ -137,7 +147,7 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, config=None, torch_dtype=None, dtype=None, device="cuda",
-                        gradient_checkpointing: bool = False, scan_bwd_segments=1, **kwargs):
+                        gradient_checkpointing: bool = False, scan_bwd_segments=1, scan_fwd_segments=1, **kwargs):
         """A snapshot directory or hub id, read by the loader of the inference classes (config.json + safetensors / bin with the
         reference's key names; tied keys restored)."""
         hub_kw = {k: kwargs[k] for k in ("revision", "cache_dir", "local_files_only", "token") if k in kwargs}
@@ -149,7 +159,7 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
         if isinstance(want, str):
             want = getattr(torch, want) if want != "auto" else None
         model = cls(config, dtype=want or torch.float32, device=device, gradient_checkpointing=gradient_checkpointing,
-                    scan_bwd_segments=scan_bwd_segments)
+                    scan_bwd_segments=scan_bwd_segments, scan_fwd_segments=scan_fwd_segments)
         model.load_state_dict(load_state_dict(path))
         return model
 
@@ -187,7 +197,8 @@ class TrainableCaduceusForMaskedLM(_Recompute, nn.Module):
     def _inner(self, xz, m, reverse: bool):
         return ops.mamba_inner_fn(xz, m.conv1d.weight, m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.out_proj.weight, None,
                                   -torch.exp(m.A_log.float()), None, None, D=m.D.float(), delta_bias=m.dt_proj.bias.float(),
-                                  delta_softplus=True, reverse=reverse, scan_bwd_segments=self.scan_bwd_segments)
+                                  delta_softplus=True, reverse=reverse, scan_bwd_segments=self.scan_bwd_segments,
+                                  scan_fwd_segments=self.scan_fwd_segments)
 
 
 # ---- fine-tuning: frozen trunk + LoRA factors + score -----------------------------------------------------------------
@@ -227,12 +238,14 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
     and increments it after a training forward.  Under `no_grad` or `eval()` the merged call runs, without dropout.
     gradient_checkpointing=True: each block keeps only its inputs and is run again in the backward; same bits.
     scan_bwd_segments (1, 2..64 or "auto"): the segmented backward of every selective scan; no forward bit depends on it.
+    scan_fwd_segments (1, 2..64 or "auto"): the segmented forward of every selective scan, with or without grad; 1 changes no bit.
     `forward(input_ids, labels=None)` -> `.loss`, `.logits`."""
 
     def __init__(self, config: CaduceusConfig, num_labels: int, problem_type: str, pooling_strategy: str = "mean",
                  dtype: torch.dtype = torch.float32, device="cuda", r: int = 8, lora_alpha: float = 32,
                  target_modules=("x_proj", "in_proj", "out_proj"), train_lora: bool = True, seed: int = 0,
-                 gradient_checkpointing: bool = False, lora_dropout: float = 0.0, scan_bwd_segments=1):
+                 gradient_checkpointing: bool = False, lora_dropout: float = 0.0, scan_bwd_segments=1,
+                 scan_fwd_segments=1):
         super().__init__()
         from .adapters import TARGETS
         if dtype not in _DT:
@@ -253,6 +266,7 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         self.target_modules = tuple(sorted(target_modules))
         self.is_gradient_checkpointing = bool(gradient_checkpointing)
         self._set_scan_bwd_segments(scan_bwd_segments)
+        self._set_scan_fwd_segments(scan_fwd_segments)
         self.lora_dropout, self.dropout_seed, self.dropout_step = float(lora_dropout), 0, 0
         ops.lora_dropout_threshold(self.lora_dropout)
         self.caduceus = _Backbone(config)
@@ -365,7 +379,8 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
         delta = F.linear(x_dbl[..., :R], m.dt_proj.weight.to(dt)).transpose(1, 2)                # (2B, E, L)
         y = ops.selective_scan_fn(xc.transpose(1, 2), delta, -torch.exp(m.A_log.float()), x_dbl[..., R:R + 16].transpose(1, 2),
                                   x_dbl[..., R + 16:].transpose(1, 2), m.D.float(), z=xz[..., E:].transpose(1, 2),
-                                  delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse, segments=self.scan_bwd_segments)
+                                  delta_bias=m.dt_proj.bias.float(), delta_softplus=True, reverse=reverse, segments=self.scan_bwd_segments,
+                                  fwd_segments=self.scan_fwd_segments)
         return self._linear(y.transpose(1, 2), m.out_proj, stream("out_proj"))
 
     def _block(self, blk, h, res, layer: int = 0, step: Optional[int] = None):

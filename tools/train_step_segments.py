@@ -1,7 +1,8 @@
-"""Time one training step (forward + backward) of both trainable models with the scan's backward unsegmented (scan_bwd_segments = 1: the
-default path, bit for bit) and on "auto" (DESIGN.md §4v), in one process on one device: tools/train_memory.py's configuration - synthetic
-weights at PlantCAD2 Small's geometry, L = 8 192, fp32 and bf16, recompute off - at one and four windows.  HIP events around
-forward + backward, one untimed step first, median over --reps steps; the legs of a (model, dtype, batch) alternate off, auto.
+"""Time one training step (forward + backward) of both trainable models with the scan unsegmented (scan_bwd_segments = scan_fwd_segments
+= 1: the default path, bit for bit), with its backward on "auto" (DESIGN.md §4v), and with its backward and its forward on "auto" (§4w), in
+one process on one device: tools/train_memory.py's configuration - synthetic weights at PlantCAD2 Small's geometry, L = 8 192, fp32 and
+bf16, recompute off - at one and four windows.  HIP events around forward + backward, one untimed step first, median over --reps steps;
+the legs of a (model, dtype, batch) run in the order off, backward auto, both auto.
 
     python tools/train_step_segments.py [--out profiles/train_step_segments.txt (the default)] [--reps 3] [--batches 1,4] [--L 8192]
 """
@@ -32,11 +33,11 @@ def main():
     cfg = make_config(a.size)
     sd = synthetic_state_dict(cfg, stress=False)
     L = a.L
-    lines = [f"# one training step (forward + backward), scan backward unsegmented and on auto, {torch.cuda.get_device_name(0)}, "
+    lines = [f"# one training step (forward + backward), scan unsegmented, backward on auto, backward and forward on auto, {torch.cuda.get_device_name(0)}, "
              f"build {engine.load_library().pcad_build_hash().decode()}",
              f"# {a.size}: D={cfg.d_model} E={cfg.d_inner} R={cfg.dt_rank} n_layer={cfg.n_layer}, L={L}; synthetic weights; recompute off; "
              f"HIP events, median of {a.reps} steps after one untimed step; SCAN_BWD_SEG_MIN_STEPS = {ops.SCAN_BWD_SEG_MIN_STEPS}",
-             "model      dtype     windows  segments(auto)  off_ms    auto_ms   auto/off"]
+             "model      dtype     windows  segments(auto)  off_ms    auto_ms   auto/off  both_ms  both/off  both/auto"]
     for kind in ("masked LM", "LoRA"):
         for dt in (torch.float32, torch.bfloat16):
             model = build(kind, cfg, sd, dt)
@@ -46,13 +47,14 @@ def main():
                 with torch.cuda.device(DEV):
                     G = ops.scan_bwd_auto_segments(2 * nb, L, cfg.d_inner)
                 ms = {}
-                for setting in (1, "auto"):
-                    model.scan_bwd_segments = setting
+                for setting, (bwd, fwd) in ((1, (1, 1)), ("auto", ("auto", 1)), ("both", ("auto", "auto"))):
+                    model.scan_bwd_segments, model.scan_fwd_segments = bwd, fwd
                     step(model, batch)
                     ms[setting] = timed(model, batch, a.reps)
-                model.scan_bwd_segments = 1
+                model.scan_bwd_segments = model.scan_fwd_segments = 1
                 model.zero_grad(set_to_none=True)
-                lines.append(f"{kind:9s}  {str(dt).split('.')[-1]:8s}  {nb:7d}  {G:14d}  {ms[1]:8.1f}  {ms['auto']:8.1f}  {ms['auto'] / ms[1]:9.3f}")
+                lines.append(f"{kind:9s}  {str(dt).split('.')[-1]:8s}  {nb:7d}  {G:14d}  {ms[1]:8.1f}  {ms['auto']:8.1f}  {ms['auto'] / ms[1]:9.3f}"
+                             f"  {ms['both']:7.1f}  {ms['both'] / ms[1]:8.3f}  {ms['both'] / ms['auto']:9.3f}")
                 print(lines[-1], flush=True)
                 del batch
             del model
