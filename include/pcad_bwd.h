@@ -10,7 +10,8 @@
  * csrc/norm_bwd.hip, csrc/loss_bwd.hip, csrc/pool_bwd.hip, csrc/optim.hip (the optimizer step that uses the gradients and their gathering
  * into one buffer for a data-parallel run), csrc/wgrad.hip (the weight gradient of a linear layer into an fp32 main gradient) and
  * csrc/lora.hip (the dropout-masked down-projection of a LoRA branch, forward and backward) and csrc/scan_bwd_seg.hip (the selective
- * scan's backward in segments) and csrc/scan_fwd_seg.hip (the scan's training forward in segments: the last two sections below).
+ * scan's backward in segments) and csrc/scan_fwd_seg.hip (the scan's training forward in segments: the last two sections below) and
+ * csrc/pool_feat.hip (the score head on cached pooled vectors).
  *
  * Common to every entry: no allocation, no synchronisation, all work goes on `stream`; the scratch is the caller's, *_scratch_bytes
  * large and 256-byte aligned (too small / misaligned: PCAD_ERR_WORKSPACE); PCAD_ERR_INVALID names the offending argument through
@@ -115,6 +116,32 @@ size_t pcad_pooled_head_bwd_scratch_bytes(int B, int L, int D, int pooling);
 int pcad_pooled_head_bwd(const void* h, const void* res, const float* norm_weight, const float* score_w, const float* pooled,
                          const float* dlogits, void* dh, void* dres, float* dnorm_weight, float* dscore_w, void* scratch, size_t scratch_bytes,
                          int B, int L, int D, int num_labels, float eps, int pooling, int dtype, int res_dtype, pcad_stream stream);
+
+/* ---- The score head on cached pooled vectors: frozen-trunk fine-tuning --------------------------------------------
+ * With a frozen trunk a window's pooled vectors - pcad_pooled_head's / pcad_forward_pooled's pooled_out [2, D] - never change, so they
+ * are computed once and kept; these two entries are what is left of the head.  csrc/pool_feat.hip.  No scratch.
+ *
+ * pcad_pooled_logits: logits[b, n] = round(round(round(pooled[b, 0] . W[n]) + round(pooled[b, 1] . W[n])) / 2), the roundings to `dtype`
+ * (the model dtype), fp32 accumulation.  It restates the logits half of pcad_pooled_head's second stage - one block of 256 lanes per
+ * window, wave w of 4 takes labels w, w + 4, ..., lane l adds the products of columns l, l + 64, ... in index order, the 64 lanes' sums
+ * are added by the xor butterfly (32, 16, ... 1) - so that the logits of cached vectors are the bits pcad_forward_pooled writes.
+ *   pooled fp32 [B, 2, D];  score_w fp32 [num_labels, D] (the dtype-rounded weight);  logits fp32 [B, num_labels]
+ *   D % 8 == 0, D <= 2048;  1 <= num_labels <= PCAD_MAX_LABELS;  dtype PCAD_BF16 / PCAD_F32;  pooled, score_w 16-byte aligned
+ * B == 0: OK, nothing is done (pooled and logits may then be NULL). */
+int pcad_pooled_logits(const float* pooled, const float* score_w, float* logits, int B, int D, int num_labels, int dtype,
+                       pcad_stream stream);
+
+/* The backward of pcad_pooled_logits.  Every rounding of the forward is the identity in the derivative, so there is no dtype; all fp32:
+ *   dscore_w[n, :]   = 1/2 sum_b dlogits[b, n] (pooled[b, 0, :] + pooled[b, 1, :])        (b in index order)
+ *   dpooled[b, s, :] = 1/2 sum_n dlogits[b, n] W[n, :]                                    (n in index order; the same for both strands)
+ * dscore_w is formed operation for operation as pcad_pooled_head_bwd forms it: the same bits.  dpooled has no 1 / L: the pooling is
+ * upstream of `pooled`.
+ *   pooled, score_w as above;  dlogits fp32 [B, num_labels];  dscore_w fp32 [num_labels, D] or NULL;  dpooled fp32 [B, 2, D] or NULL
+ *   dscore_w and dpooled may each be NULL (not computed), not both; neither changes the other's bits
+ *   pooled, score_w, dscore_w, dpooled 16-byte aligned;  D and num_labels as above
+ * B == 0: OK, nothing is done - dscore_w is NOT written (pooled and dlogits may then be NULL). */
+int pcad_pooled_logits_bwd(const float* pooled, const float* score_w, const float* dlogits, float* dscore_w, float* dpooled,
+                           int B, int D, int num_labels, pcad_stream stream);
 
 /* ---- The optimizer step: AdamW with global-norm gradient clipping over a whole parameter set ----------------
  * Replaces: torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step + zero_grad, in three (one) launches however many tensors there are.

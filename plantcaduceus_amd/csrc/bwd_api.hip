@@ -160,6 +160,56 @@ int pcad_pooled_head_bwd(const void* h, const void* res, const float* norm_weigh
     return PCAD_OK;
 }
 
+// ---- the score head on cached pooled vectors (csrc/pool_feat.hip) ----
+// what pcad_pooled_logits and pcad_pooled_logits_bwd refuse in (B, D, num_labels)
+static int pooled_logits_shape_check(const char* who, int B, int D, int num_labels) {
+    if (B < 0) return fail(PCAD_ERR_INVALID, "%s: B must be >= 0 (B=%d)", who, B);
+    if (D <= 0 || D % 8) return fail(PCAD_ERR_INVALID, "%s: D must be a positive multiple of 8 (D=%d)", who, D);
+    if (D > 2048) return fail(PCAD_ERR_INVALID, "%s: D must be <= 2048 (D=%d)", who, D);
+    if (num_labels < 1 || num_labels > PCAD_MAX_LABELS)
+        return fail(PCAD_ERR_INVALID, "%s: num_labels must be in [1, %d] (num_labels=%d)", who, PCAD_MAX_LABELS, num_labels);
+    return PCAD_OK;
+}
+
+int pcad_pooled_logits(const float* pooled, const float* score_w, float* logits, int B, int D, int num_labels, int dtype, pcad_stream stream) {
+    const char* who = "pcad_pooled_logits";
+    const struct { const void* p; const char* name; } req[] = {{score_w, "score_w"}, {pooled, "pooled"}, {logits, "logits"}};
+    for (const auto& r : req)
+        if (!r.p && (B != 0 || r.p == score_w)) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);      // no windows: pooled and logits are not touched and may be NULL
+    if (dtype != PCAD_F32 && dtype != PCAD_BF16) return fail(PCAD_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    if (int rc = pooled_logits_shape_check(who, B, D, num_labels)) return rc;
+    const struct { const void* p; const char* name; } al[] = {{pooled, "pooled"}, {score_w, "score_w"}};
+    for (const auto& r : al)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    if (((uintptr_t)logits) % 4) return fail(PCAD_ERR_INVALID, "%s: logits must be 4-byte aligned", who);
+    if (B == 0) return PCAD_OK;
+    hipError_t err = launch_pooled_logits({.pooled = pooled, .score_w = score_w, .logits = logits, .B = B, .D = D, .NL = num_labels, .dt = dtype},
+                                          (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
+int pcad_pooled_logits_bwd(const float* pooled, const float* score_w, const float* dlogits, float* dscore_w, float* dpooled, int B, int D,
+                           int num_labels, pcad_stream stream) {
+    const char* who = "pcad_pooled_logits_bwd";
+    const struct { const void* p; const char* name; } req[] = {{score_w, "score_w"}, {pooled, "pooled"}, {dlogits, "dlogits"}};
+    for (const auto& r : req)
+        if (!r.p && (B != 0 || r.p == score_w)) return fail(PCAD_ERR_INVALID, "%s: null %s", who, r.name);      // no windows: pooled and dlogits are not read and may be NULL
+    if (!dscore_w && !dpooled) return fail(PCAD_ERR_INVALID, "%s: no output requested (dscore_w and dpooled are both NULL)", who);
+    if (int rc = pooled_logits_shape_check(who, B, D, num_labels)) return rc;
+    const struct { const void* p; const char* name; } al[] = {{pooled, "pooled"}, {score_w, "score_w"}, {dscore_w, "dscore_w"}, {dpooled, "dpooled"}};
+    for (const auto& r : al)
+        if (((uintptr_t)r.p) % 16) return fail(PCAD_ERR_INVALID, "%s: %s must be 16-byte aligned", who, r.name);
+    if (((uintptr_t)dlogits) % 4) return fail(PCAD_ERR_INVALID, "%s: dlogits must be 4-byte aligned", who);
+    if (B == 0) return PCAD_OK;
+    if ((int64_t)B + num_labels > 0x7fffffff) return fail(PCAD_ERR_INVALID, "%s: B + num_labels must fit a 32-bit grid (B=%d)", who, B);
+    hipError_t err = launch_pooled_logits_bwd({.pooled = pooled, .score_w = score_w, .dlogits = dlogits, .dscore_w = dscore_w, .dpooled = dpooled,
+                                               .B = B, .D = D, .NL = num_labels},
+                                              (hipStream_t)stream);
+    if (err != hipSuccess) return fail(PCAD_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+    return PCAD_OK;
+}
+
 // what pcad_optim_plan and pcad_grads_flat_plan refuse in record i; *chunks_out: the record's chunk count (0 for n == 0)
 static int optim_record_check(const char* who, const pcad_optim_tensor& t, int64_t i, int64_t* chunks_out) {
     *chunks_out = 0;

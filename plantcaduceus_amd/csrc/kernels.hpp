@@ -477,6 +477,28 @@ struct PooledHeadBwdLaunch {
 size_t pooled_head_bwd_bytes(int B, int L, int D, int pooling);
 hipError_t launch_pooled_head_bwd(const PooledHeadBwdLaunch& a, hipStream_t s);
 
+// pool_feat.hip (libpcad_bwd.so): the score head on cached pooled vectors (pcad_bwd.h pcad_pooled_logits /
+// pcad_pooled_logits_bwd).  The forward restates the logits half of pool.hip's stage 2 (one block of 256 per window), the backward
+// pool_bwd.hip's prep kernel without the mean's / L (one block per window for dpooled, one per label for dscore_w).  D % 8 == 0,
+// D <= 2048, 1 <= NL <= 256; B == 0: nothing is launched.  No scratch.
+struct PooledLogitsLaunch {
+    const float* pooled = nullptr;    // [B, 2, D] fp32: launch_pooled_head's pooled_out
+    const float* score_w = nullptr;   // [NL, D] fp32 (the dtype-rounded weight)
+    float* logits = nullptr;          // [B, NL] fp32
+    int B = 0, D = 0, NL = 0;
+    int dt = BF16;                    // the model dtype: fixes the rounding points
+};
+hipError_t launch_pooled_logits(const PooledLogitsLaunch& a, hipStream_t s);
+struct PooledLogitsBwdLaunch {
+    const float* pooled = nullptr;    // [B, 2, D] fp32 (read for dscore_w only)
+    const float* score_w = nullptr;   // [NL, D] fp32 (read for dpooled only)
+    const float* dlogits = nullptr;   // [B, NL] fp32
+    float* dscore_w = nullptr;        // [NL, D] fp32 or null
+    float* dpooled = nullptr;         // [B, 2, D] fp32 or null; not both null
+    int B = 0, D = 0, NL = 0;
+};
+hipError_t launch_pooled_logits_bwd(const PooledLogitsBwdLaunch& a, hipStream_t s);
+
 // optim.hip (libpcad_bwd.so): one AdamW step with global-norm clipping over a table of tensors (pcad_bwd.h pcad_adamw_step) and
 // the zeroing of its gradients (pcad_zero_grads).  table: device array of pcad_optim_tensor; map: device int32 [chunks, 2] = (tensor,
 // chunk within the tensor), as pcad_optim_plan fills it; one block per chunk of OPTIM_CHUNK elements, chunks never straddle two tensors.

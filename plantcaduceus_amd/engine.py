@@ -144,6 +144,9 @@ BWD_SIGNATURES = {
     "pcad_pooled_head_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "pcad_pooled_head_bwd": (C.c_int, [C.c_void_p] * 11 + [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p]),
+    # the score head on cached pooled vectors (plantcaduceus_amd.ops.pooled_logits / pooled_logits_bwd / pooled_logits_fn)
+    "pcad_pooled_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pcad_pooled_logits_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     # the optimizer step (plantcaduceus_amd.ops.OptimTable / adamw_step / zero_grads)
     "pcad_optim_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "pcad_adamw_step_scratch_bytes": (C.c_size_t, [C.c_int64]),

@@ -29,6 +29,10 @@ stored bytes for a micro-batch exceed half of the device's free memory.  The com
 Likewise PCAD_TRAIN_SCAN_SEGMENTS (`pretrain.scan_segments_from_env`: unset or 1 off, 2..64, or auto) cuts every strand of the selective
 scan's backward into segments walked in parallel - long windows at a small --train_batch_size; logged at the start.
 PCAD_TRAIN_SCAN_FWD_SEGMENTS (the same helper and values) does so for the scan's forward: a setting of its own, logged too.
+PCAD_TRAIN_FEATURES=cache (unset or `off`: nothing changes) is the frozen-trunk mode on cached features: it needs
+`--train_lora 0`, runs the trunk ONCE per training and validation window on the inference engine before the first step - in fixed blocks of
+max(1, 2^18 // L) consecutive windows, or PCAD_TRAIN_FEATURE_BATCH -, keeps the pooled vectors [N, 2, D] on the device and trains and
+evaluates the score head on them (`ops.pooled_logits_fn`); a run that schedules fewer samples than half the training set is refused.
 
 Under torchrun the windows are sharded over the ranks (plantcad2_eval._sharded_rows); rank 0 writes / prints.  Metrics are
 computed on the host without sklearn (the reference's compute_metrics_* :517-563 restated; pinned against sklearn / scipy in
@@ -337,6 +341,16 @@ class LabelledBatches(pretrain.WindowOrder):
         return [(torch.from_numpy(self.ids[idx].copy()), torch.from_numpy(self.labels[idx].copy()), None) for idx in self.windows(step)]
 
 
+class LabelledIndexBatches(LabelledBatches):
+    """`LabelledBatches` for a run on cached features: the same windows for the same (seed, step) - `windows(step)` is
+    the parent's - handed out as dataset indices instead of ids, so that the micro-step gathers their rows from the cache."""
+
+    def step_batches(self, step: int):
+        """-> [(window indices int64 [b], labels [b] or [b, NL], None)] CPU tensors"""
+        return [(torch.from_numpy(np.asarray(idx, dtype=np.int64).copy()), torch.from_numpy(self.labels[idx].copy()), None)
+                for idx in self.windows(step)]
+
+
 def _labels_for(labels: np.ndarray, task_type: str) -> np.ndarray:
     if task_type == "classification":
         return np.asarray(labels).astype(np.int64).reshape(-1)
@@ -408,6 +422,107 @@ class FinetuneTrainer(pretrain.Trainer):
                 self.evaluate()
             if every_save and self.step % every_save == 0:
                 self.checkpoint()
+
+
+class FeatureTrainer(FinetuneTrainer):
+    """`FinetuneTrainer` on cached pooled features: `source` is a `LabelledIndexBatches`, `features` the training
+    windows' cache fp32 [N, 2, D] on the device and `valid` (features [Nv, 2, D], labels).  The micro-step gathers its rows and runs
+    the score head alone; the evaluation takes its logits from the cached validation features.  No trunk forward runs here."""
+
+    def __init__(self, model, optimizer, source, a, max_steps: int, features: torch.Tensor, valid=None, rank: int = 0, world: int = 1):
+        super().__init__(model, optimizer, source, a, max_steps, valid, rank, world)
+        self.features = features
+
+    def before_micro_step(self, j: int, n: int):
+        """nothing is drawn: the mode has no LoRA branch"""
+
+    def micro_step(self, idx, labels, _weights):
+        dev = self.a.device
+        out = self.model(pooled=self.features.index_select(0, idx.to(dev)), labels=labels.to(dev))
+        out.loss.backward()
+        return out.loss.detach()
+
+    def eval_logits(self) -> np.ndarray:
+        feats, bs = self.valid[0], max(1, int(self.a.eval_batch_size))
+        with torch.no_grad():
+            parts = [self.model.logits_from_features(feats[b0:b0 + bs]) for b0 in range(0, feats.shape[0], bs)]
+        nl = int(self.model.num_labels)
+        return (torch.cat(parts, dim=0) if parts else torch.zeros((0, nl), dtype=torch.float32)).cpu().numpy()
+
+    def evaluate(self):
+        labels = self.valid[1]
+        t0 = time.time()
+        logits = self.eval_logits()                              # every rank holds the whole cache: the same values everywhere, no gather
+        res = {"eval_loss": eval_loss(self.model, logits, labels, self.a.task_type, self.a.eval_batch_size)}
+        res.update({"eval_" + k: v for k, v in METRICS[self.a.task_type](logits, labels).items()})
+        res["eval_runtime"] = round(time.time() - t0, 4)
+        entry = dict(res, step=self.step, epoch=round(self.epoch(), 4))
+        self.log_history.append(entry)
+        if self.rank == 0:
+            logger.info(json.dumps(entry))
+        return res
+
+
+FEATURES_ENV = "PCAD_TRAIN_FEATURES"
+FEATURE_BATCH_ENV = "PCAD_TRAIN_FEATURE_BATCH"
+FEATURE_BLOCK_POSITIONS = 2 ** 18        # windows x positions of one block of the feature pass: 32 windows at L = 8 192
+
+
+def train_features_from_env(env=None, train_lora: bool = True) -> bool:
+    """Whether `train` runs on cached pooled features, from the environment variable PCAD_TRAIN_FEATURES (`env`: a
+    mapping, os.environ when None): unset, empty or `off` - no; `cache` - yes, which needs --train_lora 0 (with trained factors the
+    features move every step).  Anything else, and `cache` with --train_lora 1, exits naming the variable (and the flag)."""
+    val = str((os.environ if env is None else env).get(FEATURES_ENV, "")).strip().lower()
+    if val in ("", "off"):
+        return False
+    if val != "cache":
+        raise SystemExit(f"{FEATURES_ENV} must be off or cache, got {val!r}")
+    if train_lora:
+        raise SystemExit(f"{FEATURES_ENV}=cache needs --train_lora 0: with trained LoRA factors the trunk's features change every step and "
+                         "cannot be cached; unset one")
+    return True
+
+
+def feature_block_windows(L: int, env=None) -> int:
+    """Windows per block of the feature pass: max(1, 2^18 // L) - a function of L alone, so that a window always meets the same
+    companions - unless PCAD_TRAIN_FEATURE_BATCH (a positive integer) overrides it."""
+    val = str((os.environ if env is None else env).get(FEATURE_BATCH_ENV, "")).strip()
+    if not val:
+        return max(1, FEATURE_BLOCK_POSITIONS // max(1, int(L)))
+    try:
+        fb = int(val)
+    except ValueError:
+        fb = 0
+    if fb < 1:
+        raise SystemExit(f"{FEATURE_BATCH_ENV} must be a positive integer, got {val!r}")
+    return fb
+
+
+def check_feature_budget(scheduled: int, n_train: int):
+    """The feature pass costs one trunk forward per training window; a run that schedules fewer samples than half of them would pay
+    more forwards for the pass than the plain path pays in all: exit naming the two numbers and the variable."""
+    if 2 * int(scheduled) < int(n_train):
+        raise SystemExit(f"{FEATURES_ENV}=cache: the run schedules {int(scheduled)} samples (steps x batch x accumulation x world), fewer than "
+                         f"half of the {int(n_train)} training windows the feature pass would send through the trunk; unset {FEATURES_ENV}")
+
+
+def feature_pass(n: int, fb: int, run_block, width: int, device) -> torch.Tensor:
+    """[n, width] fp32 on every rank: `run_block(lo, hi)` -> [hi - lo, width] over FIXED blocks of `fb` consecutive dataset indices (the
+    last one short), dealt to the ranks in contiguous runs of whole blocks and reassembled by one gather
+    (`sharding.gather_batch_rows`).  A window's block - its companions in the forward - depends on (index, fb) alone, never on the
+    training order, the world size or a resume, so its row's bits do not either."""
+    return sharding.gather_batch_rows(int(n), int(fb), run_block, int(width), device)
+
+
+def cache_features(model, ids: np.ndarray, device, fb: int) -> torch.Tensor:
+    """the frozen trunk's pooled vectors of every window of `ids` [N, L] -> fp32 [N, 2, D] on `device`: `feature_pass` over
+    `model.pooled_features`"""
+    D = int(model.config.d_model)
+    t = torch.from_numpy(np.ascontiguousarray(ids))
+    rows = feature_pass(len(ids), fb, lambda lo, hi: model.pooled_features(t[lo:hi].to(device)).reshape(hi - lo, 2 * D), 2 * D, device)
+    from .zero_shot import check_model_inputs
+    check_model_inputs(model.feature_engine())                   # an id outside the vocabulary raises here, on every rank
+    return rows.reshape(len(ids), 2, D).contiguous()
 
 
 def predict_logits_trainable(model, ids: np.ndarray, device: str, batch_size: int) -> np.ndarray:
@@ -487,6 +602,7 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
         raise SystemExit(f"--lora_dropout {lora_dropout} is not accepted on the command line yet: set the environment variable "
                          f"{DROPOUT_ENV}={lora_dropout} instead (DESIGN.md §4u); the flag itself takes only 0.0")
     dropout = lora_dropout_from_env(os.environ, bool(int(train_lora)))
+    cached = train_features_from_env(os.environ, bool(int(train_lora)))
     segments = pretrain.scan_segments_from_env(os.environ)
     fwd_segments = pretrain.scan_segments_from_env(os.environ, pretrain.SCAN_FWD_SEGMENTS_ENV)
     if pooling not in ("mean", "first", "last"):
@@ -501,7 +617,8 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     ids, labels, _ = read_tokenized(train_dir)
     if labels is None:
         raise SystemExit(f"{train_dir} has no label / labels column to train on")
-    source = LabelledBatches(ids, _labels_for(labels, task_type), train_batch_size, gradient_accumulation_steps * world, seed)
+    source = (LabelledIndexBatches if cached else LabelledBatches)(ids, _labels_for(labels, task_type), train_batch_size,
+                                                                   gradient_accumulation_steps * world, seed)
     valid = None
     if valid_dir:
         vids, vlabels, _ = read_tokenized(valid_dir)
@@ -511,6 +628,8 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
             vids, vlabels = vids[:eval_num_samples], vlabels[:eval_num_samples]
         valid = (vids, vlabels)
     total = max_steps if max_steps > 0 else math.ceil(num_train_epochs * source.steps_per_epoch)
+    if cached:
+        check_feature_budget(total * train_batch_size * gradient_accumulation_steps * world, len(ids))
     model = TrainableCaduceusForSequenceClassification.from_pretrained(
         model_name, nl, problem_type, pooling_strategy=pooling, dtype=torch.bfloat16 if bf16 else torch.float32, device=device,
         train_lora=bool(int(train_lora)), seed=seed, lora_dropout=dropout, scan_bwd_segments=segments,
@@ -535,7 +654,27 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     a = SimpleNamespace(output_dir=output_dir, model_name=model_name, task_type=task_type, device=device, learning_rate=learning_rate,
                         lr_scheduler_type=lr_scheduler_type, warmup_steps=warmup_steps, eval_batch_size=eval_batch_size, eval_strategy=eval_strategy,
                         eval_steps=eval_steps, save_strategy=save_strategy, save_steps=save_steps, logging_steps=logging_steps)
-    tr = FinetuneTrainer(model, opt, source, a, total, valid, rank, world)
+    feature_runtime = None
+    if cached:
+        # the trunk runs once per window, on the inference engine, before the first step; a resumed run runs the pass again
+        fb = feature_block_windows(ids.shape[1], os.environ)
+        model.feature_engine({} if bf16 else {"f32_gemm_split": 1})     # the options `predict` runs the trunk with (load_model)
+        torch.cuda.synchronize(device)
+        t_pass = time.time()
+        features = cache_features(model, ids, device, fb)
+        if valid is not None:
+            valid = (cache_features(model, valid[0], device, fb), valid[1])
+        torch.cuda.synchronize(device)
+        feature_runtime = time.time() - t_pass
+        n_valid = 0 if valid is None else int(valid[0].shape[0])
+        cache_bytes = (len(ids) + n_valid) * 2 * int(model.config.d_model) * 4
+        logger.info("Training on cached trunk features (%s=cache): %d training + %d validation windows through the inference engine in blocks "
+                    "of %d (%s), %.3f s; the cache holds %d bytes on %s; no trunk forward runs after this", FEATURES_ENV, len(ids), n_valid, fb,
+                    FEATURE_BATCH_ENV, feature_runtime, cache_bytes, device)
+        model.feature_engine().release_workspace()
+        tr = FeatureTrainer(model, opt, source, a, total, features, valid, rank, world)
+    else:
+        tr = FinetuneTrainer(model, opt, source, a, total, valid, rank, world)
     if resume_from_checkpoint:
         logger.info("Resuming training from checkpoint: %s", resume_from_checkpoint)
         tr.resume(resume_from_checkpoint)
@@ -555,6 +694,9 @@ def train(train_dir: str, valid_dir: str, output_dir: str = "/tmp/pcv2-ft", mode
     metrics = {"epoch": tr.epoch(), "train_loss": float(tr.total_loss) / max(1, tr.step), "train_runtime": round(runtime, 4),
                "train_samples": int(source.n), "train_samples_per_second": round(windows / runtime, 3) if runtime > 0 else 0.0,
                "train_steps_per_second": round(done / runtime, 3) if runtime > 0 else 0.0, "skipped_steps": opt.state()["skipped"]}
+    if cached:
+        metrics["feature_pass_runtime"] = round(feature_runtime, 4)
+        metrics["feature_windows"] = int(len(ids) + (0 if valid is None else valid[0].shape[0]))      # over all ranks
     if rank == 0:
         pretrain._write_json(os.path.join(output_dir, "train_results.json"), metrics)
         pretrain._write_json(os.path.join(output_dir, "trainer_state.json"), tr.trainer_state())

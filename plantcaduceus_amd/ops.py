@@ -17,7 +17,8 @@ Differentiable (each a torch.autograd.Function on this project's backward kernel
 grad; otherwise the plain call, no graph): selective_scan_fn (include/pcad_train.h), causal_conv1d_fn / causal_conv1d_dir and
 rms_norm_fn (include/pcad_bwd.h), mamba_inner_fn as a composition of those around stock F.linear, mlm_loss_head_fn - the end of the
 masked LM's forward with labels (include/pcad_bwd.h pcad_loss_head_bwd) - and pooled_head_fn, the end of the sequence classifier's
-(include/pcad_bwd.h pcad_pooled_head_bwd); lora_linear_fn is a frozen linear with LoRA factors merged in, differentiated by torch matmuls;
+(include/pcad_bwd.h pcad_pooled_head_bwd) - with pooled_logits_fn, that head's score part alone on cached pooled vectors
+(pcad_pooled_logits(_bwd); §4x); lora_linear_fn is a frozen linear with LoRA factors merged in, differentiated by torch matmuls;
 lora_dropout_linear_fn is the unmerged form with a dropout on the branch's input, on the masked rank-r kernels (pcad_lora_down(_bwd); §4u).
 plantcaduceus_amd.training composes the models from them.  linear_fn is F.linear for the masked LM's projections; for a weight that
 carries an fp32 `main_grad` its backward adds dy^T x to that buffer with linear_wgrad (include/pcad_bwd.h pcad_linear_wgrad).
@@ -1400,6 +1401,84 @@ def pooled_head_fn(h, res, norm_weight, score_w, pooling="mean", eps=1e-5, B: Op
         # of score_w to the model dtype happens inside it, so that an fp32 score_w receives the kernel's fp32 dscore_w bit for bit
         return _PooledHeadFn.apply(h, res, norm_weight.float(), score_w.float(), pooling, float(eps), B, L)
     return pooled_head(h, res, norm_weight, score_w, pooling, eps, B=B, L=L)
+
+
+# ---- the score head on cached pooled vectors (include/pcad_bwd.h pcad_pooled_logits / pcad_pooled_logits_bwd) ----
+def _pooled_logits_operands(pooled, score_w, dtype):
+    """pooled fp32 [B, 2, D] on the GPU and score_w [NL, D] -> (pooled, the weight rounded to the model dtype `dtype` as fp32, B, D, NL)"""
+    _require_gpu(pooled, "pooled")
+    if dtype not in _DT:
+        raise ValueError(f"unsupported dtype {dtype}: the model dtype is bf16 or fp32")
+    if pooled.dim() != 3 or pooled.shape[1] != 2 or pooled.dtype != torch.float32:
+        raise ValueError(f"pooled must be fp32 [B, 2, D], got {pooled.dtype} {tuple(pooled.shape)}")
+    D = pooled.shape[2]
+    if score_w.dim() != 2 or score_w.shape[1] != D or not 1 <= score_w.shape[0] <= MAX_LABELS:
+        raise ValueError(f"score_w must be [1..{MAX_LABELS}, {D}], got {tuple(score_w.shape)}")
+    # score_w is rounded to the model dtype here, as pooled_head and Engine.forward_pooled round it
+    W = score_w.detach().to(pooled.device).to(dtype).float().contiguous()
+    return pooled.detach().contiguous(), W, pooled.shape[0], D, W.shape[0]
+
+
+def pooled_logits(pooled, score_w, dtype):
+    """pcad_pooled_logits: the logits of cached pooled vectors - pooled fp32 [B, 2, D] (pooled_head's / Engine.forward_pooled's
+    want_pooled output), score_w [NL, D] (rounded to the model dtype `dtype` here) -> logits fp32 [B, NL], the bits the head that
+    produced `pooled` writes for the same weight."""
+    lib = load_bwd_library()
+    pl, W, B, D, NL = _pooled_logits_operands(pooled, score_w, dtype)
+    lg = torch.empty((B, NL), dtype=torch.float32, device=pl.device)
+    with torch.cuda.device(pl.device):
+        _check(lib.pcad_pooled_logits(_ptr(pl) or None, W.data_ptr(), _ptr(lg) or None, B, D, NL, _DT[dtype], _stream_ptr()), "pcad_pooled_logits")
+    return lg
+
+
+def pooled_logits_bwd(pooled, score_w, dlogits, want=("dscore_w",), poison=False):
+    """pcad_pooled_logits_bwd: pooled fp32 [B, 2, D], score_w [NL, D] as the forward took it (already rounded: there is no dtype here),
+    dlogits fp32 [B, NL].  want: some of dscore_w, dpooled; the other is passed as NULL and comes back as None.
+    -> namespace(dscore_w fp32 (NL, D); dpooled fp32 (B, 2, D); guards_ok).  poison (tests): as selective_scan_bwd."""
+    lib = load_bwd_library()
+    pl, W, B, D, NL = _pooled_logits_operands(pooled, score_w, torch.float32)
+    g = _WantedGrads(want, {"dscore_w": ((NL, D), torch.float32, (NL, D)), "dpooled": ((B, 2, D), torch.float32, (B, 2, D))}, pl.device, poison)
+    gl = dlogits.detach().to(pl.device, torch.float32).contiguous()
+    if gl.numel() != B * NL:
+        raise ValueError(f"dlogits must be [B, NL] = [{B}, {NL}], got {tuple(dlogits.shape)}")
+    with torch.cuda.device(pl.device):
+        _check(lib.pcad_pooled_logits_bwd(_ptr(pl) or None, W.data_ptr(), _ptr(gl) or None, g.ptr("dscore_w"), g.ptr("dpooled") or None, B, D, NL,
+                                          _stream_ptr()), "pcad_pooled_logits_bwd")
+    return g.result(pooled_logits_bwd)
+
+
+pooled_logits_bwd.last_outputs = ()    # the output set of the latest call
+
+
+class _PooledLogitsFn(torch.autograd.Function):
+    """pooled_logits with a backward: pcad_pooled_logits_bwd.  score_w arrives in fp32 and UNROUNDED, as in _PooledHeadFn: forward and
+    backward round it to the model dtype themselves and dscore_w is returned as the kernel wrote it, straight through the rounding."""
+
+    @staticmethod
+    def forward(ctx, pooled, score_w, dtype):
+        ctx.save_for_backward(pooled, score_w)
+        ctx.dtype = dtype
+        return pooled_logits(pooled, score_w, dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        pooled, score_w = ctx.saved_tensors
+        want = tuple(k for k, n in zip(("dpooled", "dscore_w"), ctx.needs_input_grad[:2]) if n)
+        if not want:
+            return None, None, None
+        g = pooled_logits_bwd(pooled, score_w.to(ctx.dtype).float(), dlogits, want=want)
+        return g.dpooled, g.dscore_w, None
+
+
+def pooled_logits_fn(pooled, score_w, dtype):
+    """The score head on cached pooled vectors: pooled fp32 [B, 2, D], score_w [NL, D], the model dtype -> logits fp32 [B, NL].  With
+    grad mode on and pooled or score_w requiring grad the call is differentiable (pcad_pooled_logits_bwd): an fp32 score_w receives the
+    kernel's fp32 dscore_w bit for bit, straight through its rounding to the model dtype; a gradient nobody needs is not computed.
+    Otherwise it is the plain call."""
+    if torch.is_grad_enabled() and (pooled.requires_grad or score_w.requires_grad):
+        return _PooledLogitsFn.apply(pooled, score_w.float(), dtype)
+    return pooled_logits(pooled, score_w, dtype)
 
 
 def _lora_merged(W, A, B, scale, dtype):

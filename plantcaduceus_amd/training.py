@@ -239,7 +239,9 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
     gradient_checkpointing=True: each block keeps only its inputs and is run again in the backward; same bits.
     scan_bwd_segments (1, 2..64 or "auto"): the segmented backward of every selective scan; no forward bit depends on it.
     scan_fwd_segments (1, 2..64 or "auto"): the segmented forward of every selective scan, with or without grad; 1 changes no bit.
-    `forward(input_ids, labels=None)` -> `.loss`, `.logits`."""
+    `forward(input_ids, labels=None)` -> `.loss`, `.logits`.  With train_lora=False the trunk's output of a window never changes:
+    `pooled_features(input_ids)` runs it once on the inference engine (`feature_engine`) and `forward(pooled=..., labels=...)` is the
+    score head on such cached rows (`ops.pooled_logits_fn`)."""
 
     def __init__(self, config: CaduceusConfig, num_labels: int, problem_type: str, pooling_strategy: str = "mean",
                  dtype: torch.dtype = torch.float32, device="cuda", r: int = 8, lora_alpha: float = 32,
@@ -288,6 +290,7 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
                         with torch.no_grad():
                             holder.lora_A.weight.copy_((torch.rand((self.r, in_f), generator=g) * 2 - 1) / in_f ** 0.5)
                             holder.lora_B.weight.zero_()
+        self._feature_engine, self.feature_windows = None, 0     # feature_engine() / pooled_features(): the frozen-trunk mode on cached features
         self.score = _Weight(self.num_labels, config.d_model)
         with torch.no_grad():                                                # nn.Linear's reset_parameters: U(+-1/sqrt(in))
             self.score.weight.copy_((torch.rand((self.num_labels, config.d_model), generator=g) * 2 - 1) / config.d_model ** 0.5)
@@ -398,7 +401,46 @@ class TrainableCaduceusForSequenceClassification(_Recompute, nn.Module):
             return checkpoint(self._block, blk, h, res, layer, step, use_reentrant=False, preserve_rng_state=False)
         return self._block(blk, h, res, layer, step)
 
-    def forward(self, input_ids, labels=None) -> SequenceClassificationTrainingOutput:
+    def feature_engine(self, engine_options=None):
+        """The inference engine bound to the frozen trunk's base weights in the tied form, as CaduceusForSequenceClassification binds
+        them (every trunk tensor in the model dtype; the factors are not bound) - built at the first call and kept; `engine_options`
+        (a mapping, e.g. {"f32_gemm_split": 1}) is read then and only then.  Allowed only with train_lora=False: with
+        trained factors the two directions untie and the trunk's output moves with every step, so nothing about it can be kept."""
+        if self.train_lora:
+            raise ValueError("feature_engine needs train_lora=False: with trained LoRA factors the trunk's features change every step "
+                             "(and the directions untie); the frozen-trunk mode alone can run the trunk on the inference engine")
+        if self._feature_engine is None:
+            import copy
+            from .engine import Engine
+            emb = self.caduceus.backbone.embeddings.word_embeddings.embedding.weight
+            _require_gpu(emb, "the model")
+            cfg = copy.copy(self.config)
+            cfg.engine_options = dict(engine_options or {})
+            sd = {"caduceus." + k: (v.to(self.dtype) if v.is_floating_point() else v) for k, v in self.caduceus.state_dict().items()
+                  if ".lora_" not in k}
+            self._feature_engine = Engine(cfg, sd, self.dtype, emb.device)
+        return self._feature_engine
+
+    def pooled_features(self, input_ids) -> torch.Tensor:
+        """the frozen trunk's pooled vectors fp32 [B, 2, D] of the windows input_ids [B, L], from `feature_engine()` under no_grad with
+        this model's pooling; `feature_windows` counts the windows sent through the engine"""
+        eng = self.feature_engine()
+        with torch.no_grad():
+            _, pooled = eng.forward_pooled(input_ids, self.pooling_strategy, self.score.weight, want_pooled=True)
+        self.feature_windows += int(input_ids.shape[0])
+        return pooled
+
+    def logits_from_features(self, pooled) -> torch.Tensor:
+        """logits fp32 [B, NL] of cached `pooled_features` rows: the engine's own head arithmetic, differentiable in `score`"""
+        return ops.pooled_logits_fn(pooled, self.score.weight, self.dtype)
+
+    def forward(self, input_ids=None, labels=None, *, pooled=None) -> SequenceClassificationTrainingOutput:
+        if (input_ids is None) == (pooled is None):
+            raise ValueError("exactly one of input_ids [B, L] and pooled [B, 2, D] (cached pooled_features rows)")
+        if pooled is not None:
+            logits = self.logits_from_features(pooled)
+            loss = sequence_classification_loss(logits, labels, self.problem_type, self.num_labels) if labels is not None else None
+            return SequenceClassificationTrainingOutput(loss=loss, logits=logits)
         cfg = self.config
         emb = self.caduceus.backbone.embeddings.word_embeddings.embedding.weight
         _require_gpu(emb, "the model")
